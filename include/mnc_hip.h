@@ -131,6 +131,23 @@ MNC_API int mnc_mask_voting(const float* boxes, const float* masks, const float*
                             int image_height, int image_width, float* out_mask, int* out_box, float* out_score,
                             int* class_count, int* result_num, int device_id);
 
+/* cpu_mask_voting (lib/transform/mask_transform.py:107-210; cfg.TEST.USE_GPU_MASK_MERGE = False) in ONE call, host pointers:
+ * the arguments of mnc_mask_voting (the library orders each class itself: order = NULL semantics) plus the binarisation
+ * threshold (cfg.BINARIZE_THRESH).  Rows, candidate sets and weights are those of mnc_mask_voting with one difference: the kept
+ * boxes of a class are re-sorted by the reference's ind_scores.argsort()[::-1] (:173-175), pinned as a stable ascending sort
+ * reversed -- equal scores come out in reverse keep order -- before the max_per_image cut.  The voting is image-space: every
+ * box rounded half to even, its mask resized to the rounded box with cv2.resize INTER_LINEAR (oracle/host.py:
+ * resize_bilinear_cv_to), binarised with >= float32(binarize_thresh), weighted and summed in float64 on an image canvas in
+ * candidate order; the result box is the extent of {canvas >= binarize_thresh} (none: the centre pixel (W // 2, H // 2)), the
+ * mask that region cast to float32 and resized to S x S with the same rule.  The canvas is never stored (csrc/mv_image.hip).
+ * Every rounded box must have x1 <= x2 and y1 <= y2 (the reference's cv2.resize raises otherwise): MNC_ERR_INVALID.  Boxes are
+ * expected inside the image, as clipped boxes are.  Outputs as mnc_mask_voting's, bit-identical to the reference's
+ * cpu_mask_voting with the tie order above. */
+MNC_API int mnc_mask_voting_image(const float* boxes, const float* masks, const float* scores, int n, int num_classes,
+                                  int mask_size, int max_per_image, float nms_thresh, float iou_thresh, double binarize_thresh,
+                                  int image_height, int image_width, float* out_mask, int* out_box, float* out_score,
+                                  int* class_count, int* result_num, int device_id);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * b3  utils.cython_bbox.bbox_overlaps (lib/utils/bbox.pyx:15-55): float64 IoU with +1 widths, [N][K] row-major.
  *     A host function in the reference (Cython) and here (C); it is not a GPU kernel and has no GPU counterpart.
@@ -580,6 +597,18 @@ MNC_API int mnc_mask_voting_dev(mnc_ctx* ctx, const float* d_boxes, const float*
 MNC_API int mnc_vote_instances(mnc_ctx* ctx, const float* d_boxes, const float* d_masks, const float* d_scores, int n,
                                int num_classes, int mask_size, int max_per_image, float nms_thresh, float iou_thresh,
                                int image_height, int image_width, float* d_records, int record_cap, int* d_counts);
+/* Voting rules of mnc_vote_instances_ex / mnc_net_set_voting: gpu_mask_voting (the default) or cpu_mask_voting
+ * (cfg.TEST.USE_GPU_MASK_MERGE = False; mnc_mask_voting_image). */
+#define MNC_VOTE_MV 0
+#define MNC_VOTE_IMAGE 1
+/* mnc_vote_instances with the voting rule chosen by `mode`: MNC_VOTE_MV is mnc_vote_instances itself (binarize_thresh unused:
+ * the rule's 0.4 is compiled in, as in the reference kernel), MNC_VOTE_IMAGE is cpu_mask_voting, records bit-identical to
+ * mnc_mask_voting_image.  Same record layout, counts and limits; rounded boxes with x2 < x1 or y2 < y1 (which clipped boxes
+ * never give) cover no pixel. */
+MNC_API int mnc_vote_instances_ex(mnc_ctx* ctx, int mode, const float* d_boxes, const float* d_masks, const float* d_scores,
+                                  int n, int num_classes, int mask_size, int max_per_image, float nms_thresh, float iou_thresh,
+                                  double binarize_thresh, int image_height, int image_width, float* d_records, int record_cap,
+                                  int* d_counts);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */
@@ -657,6 +686,12 @@ MNC_API int mnc_net_set_param(mnc_net* net, const char* layer, int index, const 
  * "MNCW0001", uint32 n, then n x { uint16 name_len, name, uint8 blob index, uint8 ndim, uint32 dims[ndim], float32 data }.
  * Entries with a blob index > 1 (a third blob of a layer, e.g. BatchNorm's moving-average factor) are read over and ignored. */
 MNC_API int mnc_net_load_file(mnc_net* net, const char* path);
+/* The voting rule of the net's last stage: MNC_VOTE_MV (gpu_mask_voting, what every net starts with) or MNC_VOTE_IMAGE
+ * (cpu_mask_voting, cfg.TEST.USE_GPU_MASK_MERGE = False; binarize_thresh = cfg.BINARIZE_THRESH, unused by MNC_VOTE_MV) -- see
+ * mnc_vote_instances_ex.  A per-net setting (a net made by mnc_net_create_shared starts with MNC_VOTE_MV), not a field of
+ * mnc_net_config.  A change drops the net's captured graph (the next image of a size runs direct and re-captures); an image in
+ * flight is waited for first. */
+MNC_API int mnc_net_set_voting(mnc_net* net, int mode, double binarize_thresh);
 /* One image.  bgr_host: uint8 [H][W][3] (BGR, as cv2.imread gives the reference).  records_host: [record_cap][6 + S*S] float32
  * = (x1, y1, x2, y2, score, class id, mask) of the voted instances, rows past the count zero; counts_host [num_classes]:
  * [0] = number of instances, [c] = instances of class c.  record_cap <= (num_classes-1) * max_per_image. */

@@ -308,5 +308,9 @@ int detect_tail_launch(mnc_ctx* ctx, const float* d_rois1, int R1, const float* 
 int mv_launch(hipStream_t stream, const float* d_boxes, int box_dim, const float* d_masks, int S, const int* d_inds,
               const int* d_begins, const int* d_ends, const float* d_wts, int H, int W, int R, int* d_bounds,
               float* d_out_mask, int* d_out_box);
+// mv_image.hip: the image-space voting kernels (cpu_mask_voting's rule) of rows [0, *d_rcount), records written as mv's
+int mv_image_launch(hipStream_t stream, const float* d_boxes, const float* d_masks, int S, const int* d_inds, const int* d_begins,
+                    const int* d_ends, const float* d_wts, int H, int W, double thresh, int R, const int* d_rcount, int grid_rows,
+                    int* d_bounds, float* d_records, const float* d_rscore, const int* d_rows, int record_cap);
 
 }  // namespace mnc

@@ -273,8 +273,40 @@ constexpr int kSelThreads = 1024;
 constexpr int kSelCap = 8192;        // kept boxes over all classes the in-LDS selection sorts (20 classes x 100: 2000)
 constexpr int kSelMaxClasses = 1024;
 
+// cpu_mask_voting's order of a class's kept boxes (mask_transform.py:173-175): ind_scores.argsort()[::-1], pinned as a stable
+// ascending sort, reversed.  The keep list (keep order: descending score, NaN last -- mv_order_kernel) is thereby reversed within
+// every run of equal scores, and the NaN run, reversed, comes first.  -> the keep-list position of entry k (< N = the class's
+// full keep count) of that order; binary searches over the keep list.
+__device__ int tie_reversed_pos(const float* __restrict__ scores, int n, int C, int c, const int* __restrict__ order,
+                                const int* __restrict__ keep, int N, int k) {
+  auto sc = [&](int t) { return scores[(long)order[(long)c * n + keep[(long)c * n + t]] * C + c + 1]; };
+  int lo = 0, hi = N;                               // f = first NaN position (NaNs form the tail)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const float v = sc(mid);
+    if (v != v) hi = mid; else lo = mid + 1;
+  }
+  const int f = lo, q = N - f;
+  if (k < q) return N - 1 - k;
+  const int jp = k - q;                             // position within the descending prefix [0, f)
+  const float v = sc(jp);
+  lo = 0; hi = jp;                                  // s = first position whose score is not > v
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sc(mid) > v) lo = mid + 1; else hi = mid;
+  }
+  const int s0 = lo;
+  lo = jp + 1; hi = f;                              // e = first position whose score is < v
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sc(mid) < v) hi = mid; else lo = mid + 1;
+  }
+  return s0 + lo - 1 - jp;
+}
+
 // The host part of gpu_mask_voting between the per-class NMS and the candidate sets (mask_transform.py:242-258), on the device,
-// ONE workgroup:  pool = kept scores of all classes (class-major, keep order; num[c] <= max_per_image already);
+// ONE workgroup:  pool = the first min(num[c], max_per_image) kept scores of every class (class-major, keep order -- or, with
+// tie_reverse, cpu_mask_voting's order: tie_reversed_pos; the `mv` rule's scan stops at max_per_image survivors already);
 //   thresh = np.sort(pool)[::-1][min(len(pool), max_per_image) - 1]      (NaN sorts FIRST in that order, as numpy's does)
 //   rows   = [(box, class) for class-major kept boxes with score >= thresh]            (NaN >= x is false)
 // Outputs: rows [R][2] = (box index, class - 1), rscore [R], counts[0] = R, counts[c] = rows of class c (1..B).
@@ -286,7 +318,7 @@ __global__ __launch_bounds__(kSelThreads) void mv_select_kernel(const float* __r
                                                                 int max_per_image, int NP, int* __restrict__ pool_box,
                                                                 float* __restrict__ pool_score, int* __restrict__ pool_cls,
                                                                 int* __restrict__ rows, float* __restrict__ rscore,
-                                                                int* __restrict__ counts) {
+                                                                int* __restrict__ counts, int tie_reverse) {
   extern __shared__ unsigned s_key[];
   __shared__ int s_off[kSelMaxClasses + 1];
   __shared__ int s_cc[kSelMaxClasses];
@@ -295,7 +327,7 @@ __global__ __launch_bounds__(kSelThreads) void mv_select_kernel(const float* __r
   for (int c = tid; c < B; c += kSelThreads) s_cc[c] = 0;
   if (tid == 0) {
     int acc = 0;
-    for (int c = 0; c < B; ++c) { s_off[c] = acc; acc += num[c]; }
+    for (int c = 0; c < B; ++c) { s_off[c] = acc; acc += min(num[c], max_per_image); }
     s_off[B] = acc;
   }
   __syncthreads();
@@ -312,7 +344,8 @@ __global__ __launch_bounds__(kSelThreads) void mv_select_kernel(const float* __r
         const int mid = (lo + hi + 1) >> 1;
         if (s_off[mid] <= j) lo = mid; else hi = mid - 1;
       }
-      const int c = lo, k = j - s_off[c];
+      const int c = lo;
+      const int k = tie_reverse ? tie_reversed_pos(scores, n, C, c, order, keep, num[c], j - s_off[c]) : j - s_off[c];
       const int bi = order[(long)c * n + keep[(long)c * n + k]];   // keep lists index the sorted order; the voting wants box indices
       const float v = scores[(long)bi * C + c + 1];
       pool_box[j] = bi; pool_cls[j] = c; pool_score[j] = v;
@@ -511,10 +544,13 @@ static size_t vote_ws_layout(char* base, int n, int C, int S, int keep_cap, Vote
 //   per-class order (unless order_ready) -> 20 batched NMS problems -> kept box indices -> threshold + result rows
 //   (mv_select_kernel) -> candidate sets -> fused voting kernels -> records.
 // d_records [record_cap][6+S*S] (record_cap <= B*keep_cap), d_counts [C].
+// mode MNC_VOTE_IMAGE: cpu_mask_voting instead -- every class's NMS runs to the end (its tie order may pull kept boxes from beyond
+// the first max_per_image), the selection takes cpu_mask_voting's order, and the image-space kernels (mv_image.hip) vote.
 static int vote_async(hipStream_t s, const VoteWs& w, const float* d_boxes, const float* d_masks, const float* d_scores,
                       bool order_ready, int n, int C, int S, int max_per_image, float nms_thresh, float iou_thresh, int H, int W,
-                      float* d_records, int record_cap, int* d_counts) {
+                      float* d_records, int record_cap, int* d_counts, int mode = MNC_VOTE_MV, double binarize_thresh = 0.4) {
   const int B = C - 1;
+  const bool image = mode == MNC_VOTE_IMAGE;
   const int keep_cap = max_per_image < n ? max_per_image : n;
   const int Rmax = B * keep_cap;
   if (!order_ready) {
@@ -523,16 +559,22 @@ static int vote_async(hipStream_t s, const VoteWs& w, const float* d_boxes, cons
     hipLaunchKernelGGL(mv_order_kernel, dim3(B), dim3(np2 < 1024 ? np2 : 1024), (size_t)np2 * 8, s, d_scores, n, C, np2, w.order);
   }
   nms_mask_launch(s, d_boxes, w.order, n, 4, nms_thresh, w.bits, B);
-  nms_scan_launch(s, w.bits, n, keep_cap, w.keep, w.num, B);
+  nms_scan_launch(s, w.bits, n, image ? n : keep_cap, w.keep, w.num, B);
   int NP = 64;
   while (NP < Rmax) NP <<= 1;
   hipLaunchKernelGGL(mv_select_kernel, dim3(1), dim3(kSelThreads), (size_t)NP * 4, s, d_scores, n, C, w.order, w.keep, w.num,
-                     max_per_image, NP, w.pool_box, w.pool_score, w.pool_cls, w.rows, w.rscore, d_counts);
+                     max_per_image, NP, w.pool_box, w.pool_score, w.pool_cls, w.rows, w.rscore, d_counts, image ? 1 : 0);
   // the row count R = d_counts[0] stays on the device: R <= max_per_image unless scores tie at the threshold, so that many
   // workgroups stride over the rows
   const int grid_rows = Rmax < max_per_image ? Rmax : max_per_image;
   hipLaunchKernelGGL(mv_candidates_kernel, dim3(grid_rows), dim3(64), 0, s, d_boxes, d_scores, n, C, w.rows, d_counts, Rmax,
                      iou_thresh, w.cinds, w.cw, w.cbegin, w.cend, w.bounds);
+  if (image) {
+    mv_image_launch(s, d_boxes, d_masks, S, w.cinds, w.cbegin, w.cend, w.cw, H, W, binarize_thresh, Rmax, d_counts, grid_rows,
+                    w.bounds, d_records, w.rscore, w.rows, record_cap);
+    MNC_HIP_TRY(hipGetLastError());
+    return MNC_OK;
+  }
   // (round 6: the resampling kernel writes the records too -- mv_pack_kernel's launch is gone)
   mv_launch_impl(s, d_boxes, 4, d_masks, S, w.cinds, w.cbegin, w.cend, w.cw, H, W, Rmax, d_counts, grid_rows, w.bounds, w.omask,
                  w.obox, /*bounds_ready=*/true, d_records, w.rscore, w.rows, record_cap);
@@ -723,11 +765,67 @@ int mnc_mask_voting(const float* boxes, const float* masks, const float* scores,
   return MNC_OK;
 }
 
+// cpu_mask_voting in one call on HOST arrays (see include/mnc_hip.h): mnc_mask_voting's sequence with the image-space rule.
+int mnc_mask_voting_image(const float* boxes, const float* masks, const float* scores, int n, int num_classes, int mask_size,
+                          int max_per_image, float nms_thresh, float iou_thresh, double binarize_thresh, int image_height,
+                          int image_width, float* out_mask, int* out_box, float* out_score, int* class_count, int* result_num,
+                          int device_id) {
+  MNC_REQUIRE(result_num && class_count, "mnc_mask_voting_image: null output pointer");
+  int rc = vote_check_args("mnc_mask_voting_image", n, num_classes, mask_size, max_per_image, image_height, image_width);
+  if (rc) return rc;
+  const int B = num_classes - 1, S = mask_size, C = num_classes;
+  *result_num = 0;
+  for (int c = 0; c < B; ++c) class_count[c] = 0;
+  if (n == 0) { clear_error(); return MNC_OK; }
+  MNC_REQUIRE(boxes && masks && scores && out_mask && out_box && out_score, "mnc_mask_voting_image: null pointer");
+  for (int i = 0; i < n; ++i) {
+    const float* b = boxes + (size_t)i * 4;
+    MNC_REQUIRE(rintf(b[0]) <= rintf(b[2]) && rintf(b[1]) <= rintf(b[3]),
+                "mnc_mask_voting_image: box %d (%g, %g, %g, %g) is empty once rounded (cv2.resize would raise)", i, b[0], b[1],
+                b[2], b[3]);
+  }
+  const int keep_cap = max_per_image < n ? max_per_image : n;
+  VoteWs ws;
+  const size_t need = vote_ws_layout(nullptr, n, C, S, keep_cap, &ws);
+  LegacyWs* w = nullptr;
+  std::unique_lock<std::mutex> lock;
+  rc = legacy_ws(device_id, need, &w, &lock);
+  if (rc) return rc;
+  vote_ws_layout((char*)w->buf, n, C, S, keep_cap, &ws);
+  hipStream_t s = w->stream;
+  MNC_HIP_TRY(hipMemcpyAsync(ws.boxes, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
+  MNC_HIP_TRY(hipMemcpyAsync(ws.scores, scores, (size_t)n * C * 4, hipMemcpyHostToDevice, s));
+  MNC_HIP_TRY(hipMemcpyAsync(ws.masks, masks, (size_t)n * S * S * 4, hipMemcpyHostToDevice, s));
+  std::vector<int> h_order;
+  if (n > kMaxOrderDevice) {
+    host_order(scores, n, C, &h_order);
+    MNC_HIP_TRY(hipMemcpyAsync(ws.order, h_order.data(), (size_t)B * n * 4, hipMemcpyHostToDevice, s));
+  }
+  rc = vote_async(s, ws, ws.boxes, ws.masks, ws.scores, n > kMaxOrderDevice, n, C, S, max_per_image, nms_thresh, iou_thresh,
+                  image_height, image_width, ws.records, B * keep_cap, ws.counts, MNC_VOTE_IMAGE, binarize_thresh);
+  if (rc) return rc;
+  rc = vote_fetch(s, ws.records, ws.counts, B * keep_cap, C, S, max_per_image, out_mask, out_box, out_score, class_count,
+                  result_num);
+  if (rc) return rc;
+  clear_error();
+  return MNC_OK;
+}
+
 // The same with inputs AND outputs on the device, asynchronous on the context's stream -- what the whole-image path uses.
 int mnc_vote_instances(mnc_ctx* ctx, const float* d_boxes, const float* d_masks, const float* d_scores, int n, int num_classes,
                        int mask_size, int max_per_image, float nms_thresh, float iou_thresh, int image_height, int image_width,
                        float* d_records, int record_cap, int* d_counts) {
+  return mnc_vote_instances_ex(ctx, MNC_VOTE_MV, d_boxes, d_masks, d_scores, n, num_classes, mask_size, max_per_image, nms_thresh,
+                               iou_thresh, 0.4, image_height, image_width, d_records, record_cap, d_counts);
+}
+
+int mnc_vote_instances_ex(mnc_ctx* ctx, int mode, const float* d_boxes, const float* d_masks, const float* d_scores, int n,
+                          int num_classes, int mask_size, int max_per_image, float nms_thresh, float iou_thresh,
+                          double binarize_thresh, int image_height, int image_width, float* d_records, int record_cap,
+                          int* d_counts) {
   MNC_REQUIRE(ctx && d_records && d_counts && record_cap >= 0, "mnc_vote_instances: null pointer");
+  MNC_REQUIRE(mode == MNC_VOTE_MV || mode == MNC_VOTE_IMAGE, "mnc_vote_instances_ex: mode %d is not MNC_VOTE_MV / MNC_VOTE_IMAGE",
+              mode);
   int rc = vote_check_args("mnc_vote_instances", n, num_classes, mask_size, max_per_image, image_height, image_width);
   if (rc) return rc;
   const int B = num_classes - 1, S = mask_size, C = num_classes;
@@ -751,7 +849,7 @@ int mnc_vote_instances(mnc_ctx* ctx, const float* d_boxes, const float* d_masks,
     record_cap = Rmax;
   }
   rc = vote_async(ctx->stream, ws, d_boxes, d_masks, d_scores, false, n, C, S, max_per_image, nms_thresh, iou_thresh,
-                  image_height, image_width, d_records, record_cap, d_counts);
+                  image_height, image_width, d_records, record_cap, d_counts, mode, binarize_thresh);
   if (rc) return rc;
   return ls.finish("mask_voting");
 }

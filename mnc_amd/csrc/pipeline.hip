@@ -119,6 +119,9 @@ struct mnc_net {
   hipGraphExec_t gexec = nullptr;
   int graph_h = -1, graph_w = -1, seen_h = -1, seen_w = -1;
   unsigned long graph_gen = 0;   // arena generation (mnc_ctx::arena_gen of both contexts) the graph was captured under
+  // voting rule of the last stage (mnc_net_set_voting)
+  int vote_mode = MNC_VOTE_MV;
+  double vote_binarize = 0.4;
 };
 
 namespace {
@@ -642,8 +645,9 @@ int run_heads_and_vote(mnc_net* n, int r1) {
     NET_TRY(detect_tail_launch(ctx, (const float*)n->rois.p, r1, (const float*)n->rois_ext.p, r1, n->im_scale, n->H, n->W,
                                (float*)n->boxes.p, proposal_count_ptr(ctx), n->prop_count()));
   const int rows = (K - 1) * c.max_per_image;
-  NET_TRY(mnc_vote_instances(ctx, (const float*)n->boxes.p, (const float*)n->masks.p, (const float*)n->scores.p, 2 * r1, K, S,
-                             c.max_per_image, c.vote_nms_thresh, c.vote_iou_thresh, n->H, n->W, n->records(), rows, n->counts()));
+  NET_TRY(mnc_vote_instances_ex(ctx, n->vote_mode, (const float*)n->boxes.p, (const float*)n->masks.p, (const float*)n->scores.p,
+                                2 * r1, K, S, c.max_per_image, c.vote_nms_thresh, c.vote_iou_thresh, n->vote_binarize, n->H, n->W,
+                                n->records(), rows, n->counts()));
   n->last_r1 = r1; n->last_r2 = r1;
   return MNC_OK;
 }
@@ -919,6 +923,24 @@ int mnc_forward_image_async(mnc_net* net, const unsigned char* bgr_host, int H, 
   if (rc) return rc;
   if (d_records) *d_records = net->records();
   if (d_counts) *d_counts = net->counts();
+  clear_error();
+  return MNC_OK;
+}
+
+int mnc_net_set_voting(mnc_net* net, int mode, double binarize_thresh) {
+  MNC_REQUIRE(net, "mnc_net_set_voting: null pointer");
+  MNC_REQUIRE(mode == MNC_VOTE_MV || mode == MNC_VOTE_IMAGE, "mnc_net_set_voting: mode %d is not MNC_VOTE_MV / MNC_VOTE_IMAGE", mode);
+  if (mode != net->vote_mode || binarize_thresh != net->vote_binarize) {
+    if (net->gexec) {
+      // the graph holds the old rule's launches: drop it, as a buffer re-allocation does
+      MNC_HIP_TRY(hipSetDevice(net->ctx->device));
+      if (net->in_flight) MNC_HIP_TRY(hipStreamSynchronize(net->ctx->stream));
+      (void)hipGraphExecDestroy(net->gexec);
+      net->gexec = nullptr; net->graph_h = net->graph_w = -1;
+    }
+    net->vote_mode = mode;
+    net->vote_binarize = binarize_thresh;
+  }
   clear_error();
   return MNC_OK;
 }

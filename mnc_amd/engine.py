@@ -1729,12 +1729,19 @@ class Net(object):
         return (DeviceArray(self, d_boxes, (n, 4), self._tail_bufs, gen), DeviceArray(self, d_masks, (n, 1, S, S), self._tail_bufs, gen),
                 DeviceArray(self, d_scores, (n, K), self._tail_bufs, gen))
 
-    def vote_instances(self, boxes, masks, scores, num_classes, max_per_image, im_width, im_height, nms_thresh, iou_thresh):
+    VOTE_MODES = {"mv": 0, "image": 1}          # MNC_VOTE_MV / MNC_VOTE_IMAGE (include/mnc_hip.h)
+
+    def vote_instances(self, boxes, masks, scores, num_classes, max_per_image, im_width, im_height, nms_thresh, iou_thresh,
+                       mode="mv", binarize_thresh=0.4):
         """gpu_mask_voting (lib/transform/mask_transform.py:213-286) on this net's own device-resident results (the DeviceArrays
         of detect_tail), asynchronously on the net's stream: -> a view of the net's InstanceBlock (mnc_amd/instances.py) whose
         records stay on the GPU until .fetch() / .lists() copies them down (one copy, one synchronisation) or the multi-GPU gather
-        sends them.  The buffer is reused by the next image: a view that was never copied refuses to read another image's rows."""
+        sends them.  The buffer is reused by the next image: a view that was never copied refuses to read another image's rows.
+        mode="image": cpu_mask_voting's rule instead (:107-210, mnc_vote_instances_ex), same records; binarize_thresh is
+        cfg.BINARIZE_THRESH there (the "mv" rule's 0.4 is fixed)."""
         from .instances import InstanceBlock
+        if mode not in self.VOTE_MODES:
+            raise ValueError("vote_instances: mode must be one of %s (got %r)" % (sorted(self.VOTE_MODES), mode))
         n, S = boxes.shape[0], masks.shape[-1]
         blk = getattr(self, "_inst", None)
         if blk is None or not blk.fits(num_classes, S, max_per_image, n):
@@ -1742,9 +1749,14 @@ class Net(object):
                 blk.release()
             blk = self._inst = InstanceBlock(self, num_classes, S, max_per_image, n)
         blk.invalidate()
-        _lib.call("mnc_vote_instances", self._ctx.h, boxes.ptr, masks.ptr, scores.ptr, n, int(num_classes), S, int(max_per_image),
-                  float(nms_thresh), float(iou_thresh), int(im_height), int(im_width), blk.records_ptr, blk.rows_cap,
-                  blk.counts_ptr)
+        if mode == "mv":
+            _lib.call("mnc_vote_instances", self._ctx.h, boxes.ptr, masks.ptr, scores.ptr, n, int(num_classes), S,
+                      int(max_per_image), float(nms_thresh), float(iou_thresh), int(im_height), int(im_width), blk.records_ptr,
+                      blk.rows_cap, blk.counts_ptr)
+        else:
+            _lib.call("mnc_vote_instances_ex", self._ctx.h, self.VOTE_MODES[mode], boxes.ptr, masks.ptr, scores.ptr, n,
+                      int(num_classes), S, int(max_per_image), float(nms_thresh), float(iou_thresh), float(binarize_thresh),
+                      int(im_height), int(im_width), blk.records_ptr, blk.rows_cap, blk.counts_ptr)
         return blk.view()
 
     # ------------------------------------------------------------------------------------------------ one image, one launch

@@ -13,7 +13,7 @@ import caffe
 from mnc_config import cfg, get_output_dir
 from nms.nms_wrapper import apply_nms, apply_nms_mask_single
 from transform.bbox_transform import bbox_transform_inv, clip_boxes, filter_small_boxes
-from transform.mask_transform import gpu_mask_voting
+from transform.mask_transform import cpu_mask_voting, gpu_mask_voting
 from utils.blob import (can_prep_on_device, cfm_scale_factors, im_list_to_blob, prep_im_for_blob, prep_im_for_blob_cfm,
                         prep_im_for_blob_cfm_device, prep_im_for_blob_device, pred_rois_for_blob, resize_to)
 from utils.image_io import imread
@@ -141,12 +141,13 @@ class TesterWrapper(object):
                     mask_before_nms = cls_masks.astype(np.float32, copy=False)
                     all_boxes[j][i], all_masks[j][i] = apply_nms_mask_single(box_before_nms, mask_before_nms, cfg.TEST.NMS)
             else:
-                if not cfg.TEST.USE_GPU_MASK_MERGE:
-                    # the reference's cpu_mask_voting (mask_transform.py:142-211) is its CPU-only alternative; this
-                    # package has no CPU compute path
-                    raise NotImplementedError("cfg.TEST.USE_GPU_MASK_MERGE=False (cpu_mask_voting) is not provided")
-                result_mask, result_box = gpu_mask_voting(masks, boxes, seg_scores, self.num_classes,
-                                                          self.max_per_image, im.shape[1], im.shape[0])
+                if cfg.TEST.USE_GPU_MASK_MERGE:
+                    result_mask, result_box = gpu_mask_voting(masks, boxes, seg_scores, self.num_classes,
+                                                              self.max_per_image, im.shape[1], im.shape[0])
+                else:
+                    # the reference's image-space voting (mask_transform.py:142-211), on the GPU here (csrc/mv_image.hip)
+                    result_box, result_mask = cpu_mask_voting(masks, boxes, seg_scores, self.num_classes,
+                                                              self.max_per_image, im.shape[1], im.shape[0])
                 for j in range(1, self.num_classes):      # no heap: voting never returns more than max_per_image
                     all_boxes[j][i] = result_box[j - 1]
                     all_masks[j][i] = result_mask[j - 1]

@@ -1,8 +1,8 @@
 """`transform.mask_transform.gpu_mask_voting` (reference: lib/transform/mask_transform.py:213-286).
 
 Host orchestration only: 20 per-class NMS calls (HIP), a global score threshold, one IoU row per surviving box, then a
-single call into the fused HIP mask-voting kernels (nms.mv.mv).  The cv2-based cpu_mask_voting of the reference uses a
-different interpolation and is not part of the hot path."""
+single call into the fused HIP mask-voting kernels (nms.mv.mv).  The reference's cv2-based cpu_mask_voting (image-space voting,
+cfg.TEST.USE_GPU_MASK_MERGE = False) runs on the GPU as well: cpu_mask_voting below (csrc/mv_image.hip)."""
 import numpy as np
 
 from mnc_config import cfg
@@ -143,3 +143,59 @@ def gpu_mask_voting(masks, boxes, scores, num_classes, max_per_image, im_width, 
         list_mask.append(result_mask[lo:hi, :, :, :])
         lo = hi
     return list_mask, list_box
+
+
+def _image_voting_lists(rec, class_counts, S):
+    """records [R, 6+S*S] -> (result_box, result_mask) as cpu_mask_voting returns them: per class boxes [k,5] float64 and masks
+    [k,1,S,S] float64 (its float64 arrays, filled from float32 values)."""
+    boxes = rec[:, :5].astype(np.float64)
+    masks = rec[:, 6:].astype(np.float64).reshape(-1, 1, S, S)
+    result_box, result_mask, lo = [], [], 0
+    for k in class_counts:
+        hi = lo + int(k)
+        result_box.append(boxes[lo:hi])
+        result_mask.append(masks[lo:hi])
+        lo = hi
+    return result_box, result_mask
+
+
+def cpu_mask_voting(masks, boxes, scores, num_classes, max_per_image, im_width, im_height):
+    """The reference's image-space mask voting (mask_transform.py:142-210, cfg.TEST.USE_GPU_MASK_MERGE = False) on the GPU:
+    masks [n,1,S,S], boxes [n,4] float32, scores [n,num_classes] -> (result_box, result_mask), one entry per foreground class,
+    boxes [k,5] = (x1, y1, x2, y2, score) and masks [k,1,S,S], both float64 (note the order: gpu_mask_voting returns masks first).
+    Per-class NMS, threshold and candidate sets as gpu_mask_voting; a class's kept boxes re-sorted by argsort()[::-1] pinned as
+    stable-ascending-reversed (equal scores in reverse keep order); each mask resized to its rounded box with cv2's bilinear
+    rule, binarised at cfg.BINARIZE_THRESH and summed with its weight on a float64 image canvas (mnc_mask_voting_image /
+    mnc_vote_instances_ex).  n == 0 gives empty classes."""
+    import ctypes
+    from mnc_amd import _lib
+    from mnc_amd.devarray import DeviceArray
+    if not cfg.USE_GPU_NMS:
+        raise NotImplementedError("cpu_mask_voting with cfg.USE_GPU_NMS=False (cpu_nms.pyx's rule) is not provided")
+    B = num_classes - 1
+    S = masks.shape[-1]
+    n = boxes.shape[0]
+    if n == 0:
+        return [np.zeros((0, 5)) for _ in range(B)], [np.zeros((0, 1, S, S)) for _ in range(B)]
+    if all(isinstance(a, DeviceArray) for a in (masks, boxes, scores)):
+        blk = boxes._net.vote_instances(boxes, masks, scores, num_classes, max_per_image, im_width, im_height,
+                                        cfg.TEST.MASK_MERGE_NMS_THRESH, cfg.TEST.MASK_MERGE_IOU_THRESH, mode="image",
+                                        binarize_thresh=cfg.BINARIZE_THRESH)
+        counts, rec = blk.fetch()
+        return _image_voting_lists(rec, counts[1:num_classes], S)
+    masks = np.ascontiguousarray(np.asarray(masks), dtype=np.float32)
+    boxes = np.ascontiguousarray(np.asarray(boxes), dtype=np.float32)
+    scores = np.ascontiguousarray(np.asarray(scores), dtype=np.float32)
+    cap = B * min(max_per_image, n)
+    out_mask = np.zeros((cap, S * S), dtype=np.float32)
+    out_box = np.zeros((cap, 4), dtype=np.int32)
+    out_score = np.zeros(cap, dtype=np.float32)
+    counts = np.zeros(B, dtype=np.int32)
+    R = ctypes.c_int(0)
+    _lib.call("mnc_mask_voting_image", _lib.ptr(boxes), _lib.ptr(masks), _lib.ptr(scores), n, num_classes, S,
+              int(max_per_image), float(cfg.TEST.MASK_MERGE_NMS_THRESH), float(cfg.TEST.MASK_MERGE_IOU_THRESH),
+              float(cfg.BINARIZE_THRESH), int(im_height), int(im_width), _lib.ptr(out_mask), _lib.ptr(out_box),
+              _lib.ptr(out_score), _lib.ptr(counts), ctypes.addressof(R), int(cfg.GPU_ID))
+    R = R.value
+    rec = np.hstack((out_box[:R].astype(np.float32), out_score[:R, None], np.zeros((R, 1), np.float32), out_mask[:R]))
+    return _image_voting_lists(rec, counts, S)

@@ -82,12 +82,19 @@ def config_from_weights(weights, math="fp32", use_graph=True, winograd=None, **o
 
 
 class NativeNet(object):
-    def __init__(self, weights, device_id=0, math="fp32", use_graph=True, winograd=None, **overrides):
+    VOTING = {"mv": 0, "image": 1}          # MNC_VOTE_MV / MNC_VOTE_IMAGE (include/mnc_hip.h)
+
+    def __init__(self, weights, device_id=0, math="fp32", use_graph=True, winograd=None, voting="mv", binarize_thresh=0.4,
+                 **overrides):
         """weights: {layer: [W, b]} in Caffe layout (what mnc_amd.synth / caffemodel.load_weights return), or the path of a
         flat MNCW0001 file (caffemodel.save_flat) together with cfg=<NetConfig>, or ANOTHER NativeNet: this net then runs on that
         net's device weights and configuration (mnc_net_create_shared: own context, stream and buffers; nothing uploaded), which
-        must stay open while this one is in use."""
+        must stay open while this one is in use.
+        voting: the last stage's rule -- "mv" (gpu_mask_voting) or "image" (cpu_mask_voting, cfg.TEST.USE_GPU_MASK_MERGE = False,
+        binarising at binarize_thresh = cfg.BINARIZE_THRESH); a net built from another takes its own."""
         from .engine import _Ctx
+        if voting not in self.VOTING:
+            raise ValueError("NativeNet: voting must be one of %s (got %r)" % (sorted(self.VOTING), voting))
         if isinstance(weights, NativeNet):
             parent = weights
             self._ctx = _Ctx(parent._ctx.device_id)
@@ -100,6 +107,7 @@ class NativeNet(object):
             self.S = parent.S
             self.rec_dim = parent.rec_dim
             self.rows_cap = parent.rows_cap
+            self.set_voting(voting, binarize_thresh)
             return
         cfg = overrides.pop("cfg", None)
         self._ctx = _Ctx(device_id)
@@ -122,6 +130,14 @@ class NativeNet(object):
         self.S = int(cfg.mask_size)
         self.rec_dim = 6 + self.S * self.S
         self.rows_cap = (int(cfg.num_classes) - 1) * int(cfg.max_per_image)
+        self.set_voting(voting, binarize_thresh)
+
+    def set_voting(self, voting, binarize_thresh=0.4):
+        """Switch the last stage's voting rule ("mv" / "image"); the net's captured graph is dropped (mnc_net_set_voting)."""
+        if voting not in self.VOTING:
+            raise ValueError("NativeNet: voting must be one of %s (got %r)" % (sorted(self.VOTING), voting))
+        _lib.call("mnc_net_set_voting", self.h, self.VOTING[voting], float(binarize_thresh))
+        self.voting = voting
 
     def forward_image(self, im, record_cap=None):
         """uint8 BGR [H,W,3] -> (counts int32[num_classes], records float32[R, 6+S*S]): prep + forward + tail + voting, one call."""
@@ -240,11 +256,14 @@ class ImageStream(object):
         for counts, records in stream.map(images): ...
     """
 
-    def __init__(self, weights, in_flight=8, **kwargs):
+    def __init__(self, weights, in_flight=8, voting="mv", **kwargs):
         if in_flight < 1:
             raise ValueError("in_flight must be >= 1")
-        first = NativeNet(weights, **kwargs)
-        self.nets = [first] + [NativeNet(first) for _ in range(int(in_flight) - 1)]
+        vote = {"voting": voting}
+        if "binarize_thresh" in kwargs:
+            vote["binarize_thresh"] = kwargs.pop("binarize_thresh")
+        first = NativeNet(weights, **dict(kwargs, **vote))
+        self.nets = [first] + [NativeNet(first, **vote) for _ in range(int(in_flight) - 1)]
         self._pending = []                      # indices of the nets holding an unfetched image, oldest first
         self._next = 0
 
