@@ -149,6 +149,28 @@ MNC_API int mnc_mask_voting_image(const float* boxes, const float* masks, const 
                                   int* class_count, int* result_num, int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n1  The pixel counting of the SDS mAP^r evaluation (lib/utils/voc_eval.py:195-283 voc_eval_sds with
+ *     lib/transform/mask_transform.py:16-46 mask_overlap), host pointers, one call for a whole dataset (csrc/sds_eval.hip).
+ * ------------------------------------------------------------------------------------------------------------- */
+/* For every prediction p: boxes [P][4] float64 (x1, y1, x2, y2), rounded half to even; masks [P][mask_size^2] bytes, taken as
+ * float32, resized to the rounded box with cv2.resize INTER_LINEAR and binarised with >= float32(binarize_thresh).  Its GTs are
+ * [gt_begin[p], gt_end[p]) of the GT arrays: gt_bounds [G][4] int (x1, y1, x2, y2), gt_offsets [G] byte offsets into gt_bits
+ * (gt_bytes bytes) of the GT's bit rows, each ceil(w / 8) bytes with bit x at bit x % 8 of byte x / 8
+ * (np.packbits(mask, axis=1, bitorder='little')), gt_areas [G] its set bits.  With inter = pixels set in both inside the
+ * intersection of the two rectangles and union = area_g + area_p - inter, ov = (double)inter / (double)union (0 when the
+ * rectangles do not meet or union < 1); best_gt[p] is the first GT of the range with a strictly greater ov than all before it,
+ * starting from -1000 (-1 for an empty range), best_inter[p] / best_union[p] its inter and union (0 / 0 for -1).  Already
+ * matched GTs are not excluded: matching at a threshold is the caller's (utils/voc_eval.py:voc_eval_sds_device).
+ * P == 0 returns before any device work.  MNC_ERR_INVALID for bad sizes, ranges or GT rows outside gt_bytes, and for any rounded
+ * box with x2 < x1 or y2 < y1 (cv2.resize raises on it), checked before anything is launched; limits: mask_size <= 32,
+ * |coordinates| < 2^24, at most 2^26 pixels per rounded box or GT bound. */
+MNC_API int mnc_sds_best_overlap(const double* boxes, const unsigned char* masks, int P, int mask_size, const int* gt_begin,
+                                 const int* gt_end, int G, const int* gt_bounds, const long long* gt_offsets,
+                                 const unsigned char* gt_bits, size_t gt_bytes, const long long* gt_areas,
+                                 double binarize_thresh, int* best_gt, long long* best_inter, long long* best_union,
+                                 int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * b3  utils.cython_bbox.bbox_overlaps (lib/utils/bbox.pyx:15-55): float64 IoU with +1 widths, [N][K] row-major.
  *     A host function in the reference (Cython) and here (C); it is not a GPU kernel and has no GPU counterpart.
  * ------------------------------------------------------------------------------------------------------------- */

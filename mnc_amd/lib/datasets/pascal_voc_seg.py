@@ -11,7 +11,7 @@ import pickle
 import numpy as np
 
 from mnc_config import cfg
-from utils.voc_eval import voc_eval_sds
+from utils.voc_eval import voc_eval_sds, voc_eval_sds_device
 
 CLASSES = ('__background__',  # always index 0
            'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable', 'dog',
@@ -55,9 +55,13 @@ class PascalVOCSeg(object):
         from utils.vis_seg import vis_seg
         vis_seg(self.image_index, self.classes, output_dir, self._data_path, self._image_ext)
 
-    def evaluate_segmentation(self, all_boxes, all_masks, output_dir):
+    def evaluate_segmentation(self, all_boxes, all_masks, output_dir, on_device=None):
+        """Writes the per-class result pickles and returns {0.5: [AP per class], 0.7: [...]}.  on_device (None: cfg.TEST.
+        USE_GPU_SDS_EVAL) counts the overlaps of all classes on the GPU in one call (voc_eval_sds_device); the APs are the same."""
         self._write_voc_seg_results_file(all_boxes, all_masks, output_dir)
-        return self._py_evaluate_segmentation(output_dir)
+        if on_device is None:
+            on_device = cfg.TEST.USE_GPU_SDS_EVAL
+        return self._device_evaluate_segmentation(output_dir) if on_device else self._py_evaluate_segmentation(output_dir)
 
     def _write_voc_seg_results_file(self, all_boxes, all_masks, output_dir):
         """<class>_det.pkl = all_boxes[cls] ([n,5] per image), <class>_seg.pkl = binarised [n,21,21] masks per image."""
@@ -102,4 +106,23 @@ class PascalVOCSeg(object):
                 print('AP for {} = {:.2f}'.format(cls, ap * 100))
             print('Mean AP@{} = {:.2f}'.format(thr, np.mean(aps) * 100))
             result[thr] = aps
+        return result
+
+    def _device_evaluate_segmentation(self, output_dir):
+        """_py_evaluate_segmentation's results and report with the pixel counting of every class and threshold in one device
+        call."""
+        gt_dir = self._data_path
+        imageset_file = os.path.join(gt_dir, self._image_set + '.txt')
+        cache_dir = os.path.join(self._devkit_path, 'annotations_cache')
+        if not os.path.isdir(output_dir):
+            os.mkdir(output_dir)
+        print('VOC07 metric? Yes')
+        result = voc_eval_sds_device(os.path.join(output_dir, '{}_det.pkl'), os.path.join(output_dir, '{}_seg.pkl'), gt_dir,
+                                     imageset_file, self._classes, cache_dir, ov_threshs=(0.5, 0.7))
+        names = [c for c in self._classes if c != '__background__']
+        for thr in (0.5, 0.7):
+            print('~~~~~~ Evaluation use min overlap = {} ~~~~~~'.format(thr))
+            for cls, ap in zip(names, result[thr]):
+                print('AP for {} = {:.2f}'.format(cls, ap * 100))
+            print('Mean AP@{} = {:.2f}'.format(thr, np.mean(result[thr]) * 100))
         return result

@@ -71,7 +71,10 @@ cfg.TEST = AttrDict(
     CFM_INPUT_MASK_SIZE=14, MAX_ROIS_GPU=[2000], GROUP_SCALE=1, USE_TOP_K_MCG=0,
     USE_MASK_MERGE=True, USE_GPU_MASK_MERGE=True,
     # not in the reference: im_detect / _segmentation_forward leave boxes, masks and scores on the GPU for gpu_mask_voting
-    DEVICE_RESULTS=True, DEVICE_PREP=True)
+    DEVICE_RESULTS=True, DEVICE_PREP=True,
+    # not in the reference: imdb.evaluate_segmentation counts the SDS overlaps of all classes on the GPU in one call
+    # (utils/voc_eval.py:voc_eval_sds_device; same APs as the CPU loop)
+    USE_GPU_SDS_EVAL=False)
 
 
 def get_output_dir(imdb, net):

@@ -219,3 +219,167 @@ def voc_eval_sds(det_file, seg_file, devkit_path, image_list, cls_name, cache_di
     rec = tp / float(num_pos)
     prec = tp / np.maximum(fp + tp, np.finfo(np.float64).eps)
     return voc_ap(rec, prec, True)
+
+
+# ---- the same evaluation with the pixel counting on the GPU (csrc/sds_eval.hip, mnc_sds_best_overlap) ----------------------
+def sds_best_overlap(boxes, masks, gt_begin, gt_end, gt_bounds, gt_offsets, gt_bits, gt_areas, binarize_thresh, device_id=0):
+    """mnc_sds_best_overlap: per prediction the arg-max GT of voc_eval_sds's overlap loop (-1: no GT of its class in its image)
+    and that GT's pixel intersection / union.  boxes [P,4] float64, masks [P, S*S] uint8; GT i of the packed arrays is prediction
+    p's for gt_begin[p] <= i < gt_end[p].  -> best_gt int32 [P], best_inter int64 [P], best_union int64 [P]."""
+    from mnc_amd import _lib
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 4)
+    P = boxes.shape[0]
+    masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(P, -1)
+    S = int(round(np.sqrt(masks.shape[1]))) if P else cfg.MASK_SIZE
+    if S * S != masks.shape[1]:
+        raise ValueError('masks of %d values are not square' % masks.shape[1])
+    gt_begin = np.ascontiguousarray(gt_begin, dtype=np.int32)
+    gt_end = np.ascontiguousarray(gt_end, dtype=np.int32)
+    if gt_begin.shape != (P,) or gt_end.shape != (P,):
+        raise ValueError('gt_begin / gt_end must have one entry per prediction')
+    gt_bounds = np.ascontiguousarray(gt_bounds, dtype=np.int32).reshape(-1, 4)
+    G = gt_bounds.shape[0]
+    gt_offsets = np.ascontiguousarray(gt_offsets, dtype=np.int64)
+    gt_areas = np.ascontiguousarray(gt_areas, dtype=np.int64)
+    gt_bits = np.ascontiguousarray(gt_bits, dtype=np.uint8)
+    if gt_offsets.shape != (G,) or gt_areas.shape != (G,):
+        raise ValueError('gt_offsets / gt_areas must have one entry per GT')
+    best_gt = np.empty(P, np.int32)
+    best_inter = np.empty(P, np.int64)
+    best_union = np.empty(P, np.int64)
+    _lib.call('mnc_sds_best_overlap', _lib.ptr(boxes), _lib.ptr(masks), P, S, _lib.ptr(gt_begin), _lib.ptr(gt_end), G,
+              _lib.ptr(gt_bounds), _lib.ptr(gt_offsets), _lib.ptr(gt_bits), gt_bits.size, _lib.ptr(gt_areas),
+              float(binarize_thresh), _lib.ptr(best_gt), _lib.ptr(best_inter), _lib.ptr(best_union), int(device_id))
+    return best_gt, best_inter, best_union
+
+
+def pack_sds_gt(gt_dicts):
+    """Cached GT instances (check_voc_sds_cache's dicts, in order) -> the entry's GT arrays: bounds int32 [G,4] (the rounded
+    mask_bound), byte offsets int64 [G], the bit rows of every mask (np.packbits(axis=1, bitorder='little')), areas int64 [G],
+    and the instances' already_detect flags (bool [G])."""
+    G = len(gt_dicts)
+    bounds = np.zeros((G, 4), np.int32)
+    offsets = np.zeros(G, np.int64)
+    areas = np.zeros(G, np.int64)
+    pre = np.zeros(G, bool)
+    rows, nbytes = [], 0
+    for i, gt in enumerate(gt_dicts):
+        b = np.round(gt['mask_bound']).astype(int)
+        m = np.asarray(gt['mask'], dtype=bool)
+        if m.shape != (b[3] - b[1] + 1, b[2] - b[0] + 1):
+            raise ValueError('GT mask of shape %s does not fill its bound %s' % (m.shape, b))
+        bounds[i] = b
+        offsets[i] = nbytes
+        areas[i] = m.sum()
+        pre[i] = bool(gt.get('already_detect', False))
+        r = np.packbits(m, axis=1, bitorder='little')
+        rows.append(r.ravel())
+        nbytes += r.size
+    bits = np.concatenate(rows) if rows else np.zeros(0, np.uint8)
+    return bounds, offsets, bits, areas, pre
+
+
+def sds_class_predictions(det_file, seg_file, num_images):
+    """voc_eval_sds's ranking of one class's predictions without its per-prediction loop: -> boxes float64 [P,4], masks uint8
+    [P, MASK_SIZE^2] and image indices [P] in the order of np.argsort(-score) over the same float64 score column."""
+    with open(det_file, 'rb') as f:
+        boxes_pkl = pickle.load(f)
+    with open(seg_file, 'rb') as f:
+        masks_pkl = pickle.load(f)
+    S = cfg.MASK_SIZE
+    boxes, masks, image = [np.zeros((0, 5))], [np.zeros((0, S * S), np.uint8)], []
+    for image_ind in range(num_images):
+        n = len(boxes_pkl[image_ind])
+        if n == 0:
+            continue
+        boxes.append(np.asarray(boxes_pkl[image_ind], dtype=np.float64).reshape(n, 5))
+        m = np.asarray(masks_pkl[image_ind])[:n].reshape(n, S * S)
+        m8 = m.astype(np.uint8)
+        if m.dtype != bool and not np.array_equal(m8, m):
+            raise ValueError('masks of image %d are not 0/1 (the _seg.pkl masks are binarised)' % image_ind)
+        masks.append(m8)
+        image.append(np.full(n, image_ind, np.int64))
+    new_boxes = np.concatenate(boxes)
+    keep_inds = np.argsort(-new_boxes[:, -1])
+    image = np.concatenate(image) if image else np.zeros(0, np.int64)
+    return new_boxes[keep_inds, :4], np.concatenate(masks)[keep_inds], image[keep_inds]
+
+
+def sds_match(best_gt, ov, ov_thresh, pre_matched=None):
+    """voc_eval_sds's greedy matching at one threshold, vectorised: a prediction (in ranked order) is a true positive iff its
+    best overlap is >= ov_thresh and it is the first such prediction of its best GT (which was not matched before).  Every
+    other prediction is a false positive.  -> tp, fp float64 [P]."""
+    hit = np.nonzero((best_gt >= 0) & (ov >= ov_thresh))[0]
+    g = best_gt[hit]
+    _, first = np.unique(g, return_index=True)
+    tp_idx = hit[first]
+    if pre_matched is not None:
+        tp_idx = tp_idx[~pre_matched[g[first]]]
+    tp = np.zeros(len(best_gt))
+    tp[tp_idx] = 1
+    return tp, 1 - tp
+
+
+def sds_device_inputs(det_path, seg_path, image_names, class_names, cache_dir):
+    """Everything mnc_sds_best_overlap needs for all classes at once: the predictions of every class (each ranked as by
+    voc_eval_sds) one after the other, and the GT instances of every (class, image) pair that has predictions packed with
+    pack_sds_gt.  det_path / seg_path are formatted with the class name.  -> dict."""
+    classes = [c for c in class_names if c != '__background__']
+    boxes, masks, begin, end, gts, slices, num_pos = [], [], [], [], [], [], []
+    lo = 0
+    for cls in classes:
+        b, m, img = sds_class_predictions(det_path.format(cls), seg_path.format(cls), len(image_names))
+        with open(os.path.join(cache_dir, cls + '_mask_gt.pkl'), 'rb') as f:
+            gt_pkl = pickle.load(f)
+        num_pos.append(sum(len(val) for val in gt_pkl.values()))
+        rb = np.zeros(len(image_names), np.int32)
+        re = np.zeros(len(image_names), np.int32)
+        ranges = {}                          # one GT range per image name (a repeated name shares its instances)
+        for ii in np.unique(img):
+            name = image_names[ii]
+            if name not in gt_pkl:
+                continue
+            if name not in ranges:
+                ranges[name] = (len(gts), len(gts) + len(gt_pkl[name]))
+                gts.extend(gt_pkl[name])
+            rb[ii], re[ii] = ranges[name]
+        boxes.append(b)
+        masks.append(m)
+        begin.append(rb[img])
+        end.append(re[img])
+        slices.append((lo, lo + len(b)))
+        lo += len(b)
+    bounds, offsets, bits, areas, pre = pack_sds_gt(gts)
+    return {'classes': classes, 'boxes': np.concatenate(boxes), 'masks': np.concatenate(masks),
+            'gt_begin': np.concatenate(begin), 'gt_end': np.concatenate(end), 'gt_bounds': bounds, 'gt_offsets': offsets,
+            'gt_bits': bits, 'gt_areas': areas, 'gt_pre': pre, 'gt_dicts': gts, 'slices': slices, 'num_pos': num_pos}
+
+
+def voc_eval_sds_device(det_path, seg_path, devkit_path, image_list, class_names, cache_dir, ov_threshs=(0.5, 0.7),
+                        device_id=None):
+    """voc_eval_sds for every class and every threshold of ov_threshs with ONE device call (mnc_sds_best_overlap) for the
+    pixel counting; the APs are those of voc_eval_sds, bit for bit.  det_path / seg_path: the per-class result files with
+    '{}' for the class name (e.g. output_dir + '/{}_det.pkl').  -> {thresh: [AP of each class but __background__]}."""
+    with open(image_list, 'r') as f:
+        image_names = [x.strip() for x in f.readlines()]
+    check_voc_sds_cache(cache_dir, devkit_path, image_names, class_names)
+    d = sds_device_inputs(det_path, seg_path, image_names, class_names, cache_dir)
+    best_gt, inter, union = sds_best_overlap(d['boxes'], d['masks'], d['gt_begin'], d['gt_end'], d['gt_bounds'],
+                                             d['gt_offsets'], d['gt_bits'], d['gt_areas'], cfg.BINARIZE_THRESH,
+                                             cfg.GPU_ID if device_id is None else device_id)
+    # mask_overlap's float(inter) / float(union), 0 for union < 1 (and for -1, whose union is 0)
+    ov = np.zeros(len(best_gt))
+    ok = union >= 1
+    ov[ok] = inter[ok] / union[ok]
+    result = {}
+    for thr in ov_threshs:
+        aps = []
+        for (lo, hi), num_pos in zip(d['slices'], d['num_pos']):
+            tp, fp = sds_match(best_gt[lo:hi], ov[lo:hi], thr, d['gt_pre'])
+            fp = np.cumsum(fp)
+            tp = np.cumsum(tp)
+            rec = tp / float(num_pos)
+            prec = tp / np.maximum(fp + tp, np.finfo(np.float64).eps)
+            aps.append(voc_ap(rec, prec, True))
+        result[thr] = aps
+    return result
