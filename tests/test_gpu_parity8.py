@@ -57,14 +57,15 @@ def vgg():
     return synth.synthetic_weights(path, seed=0)
 
 
-def _oracle_image(w, seed):
-    """Everything of the oracle that does not depend on the device: input, trunk, RPN, its own rois and full result."""
-    if seed not in _cache:
-        im = np.random.default_rng(seed).integers(0, 256, (600, 1000, 3), dtype=np.uint8)
-        data, im_info, scale = ohost.prepare_mnc_args(im)
-        ref = {}
-        c5 = onet.trunk(w, data, ref)
-        prob, bbox = onet.rpn(w, c5, ref)
+def oracle_for_image(w, im, full=True):
+    """Everything of the oracle that does not depend on the device, for one uint8 BGR image of any size: input, trunk, RPN and
+    (full) its own rois and full result -- the free-running half; the teacher-forced checks need the first three only."""
+    data, im_info, scale = ohost.prepare_mnc_args(im)
+    ref = {}
+    c5 = onet.trunk(w, data, ref)
+    prob, bbox = onet.rpn(w, c5, ref)
+    o = dict(im=im, data=data, im_info=im_info, scale=scale, c5=c5, conv5_3=ref["conv5_3"], prob=prob, bbox=bbox)
+    if full:
         rois = ohost.proposal_forward(prob, bbox, im_info)
         h1 = onet.head(w, c5, rois, False)
         rois_ext = ohost.stage_bridge_forward_test(rois, h1["bbox_pred"], h1["seg_cls_prob"], im_info)
@@ -72,8 +73,14 @@ def _oracle_image(w, seed):
         boxes, masks, scores = ohost.im_detect_tail(rois, h1["mask_proposal"], h1["seg_cls_prob"], rois_ext, h2["mask_proposal"],
                                                     h2["seg_cls_prob"], scale, im.shape)
         lm, lb = ohost.gpu_mask_voting(masks, boxes, scores, 21, 100, im.shape[1], im.shape[0])
-        _cache[seed] = dict(im=im, data=data, im_info=im_info, scale=scale, c5=c5, conv5_3=ref["conv5_3"], prob=prob, bbox=bbox,
-                            rois=rois, rois_ext=rois_ext, lm=lm, lb=lb)
+        o.update(rois=rois, rois_ext=rois_ext, lm=lm, lb=lb)
+    return o
+
+
+def _oracle_image(w, seed):
+    """oracle_for_image of BASELINE image `seed` (600x1000), computed once and shared by the math modes."""
+    if seed not in _cache:
+        _cache[seed] = oracle_for_image(w, np.random.default_rng(seed).integers(0, 256, (600, 1000, 3), dtype=np.uint8))
     return _cache[seed]
 
 
