@@ -171,6 +171,25 @@ MNC_API int mnc_sds_best_overlap(const double* boxes, const unsigned char* masks
                                  int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n4  The visualisation tail: instance-id and class-id label maps of the voted instances (lib/utils/vis_seg.py:101-130
+ *     _convert_pred_to_image), their VOC colours (:134-147) and the blend over the photograph (csrc/render.hip).
+ * ------------------------------------------------------------------------------------------------------------- */
+/* _convert_pred_to_image in ONE call, host pointers.  boxes [n][4] float64 (the rows of pred_dict['boxes'] without the score),
+ * masks [n][mask_size^2] float32, classes [n].  Per instance i, in list order: the box is rounded half to even and each coordinate
+ * clipped to [0, W-1] / [0, H-1]; the mask is resized to the box with cv2.resize INTER_LINEAR and binarised with
+ * >= float32(binarize_thresh); set pixels get i + 1 in inst_img and classes[i] in cls_img; then cls_img gets the box outline, value
+ * 150, as the four numpy slices [y1:y2+1, x1-1:x1+1], [y1:y2+1, x2-1:x2+1], [y1-1:y1+1, x1:x2+1], [y2-1:y2+1, x1:x2+1] -- a slice
+ * that would start at -1 is EMPTY, so a side at coordinate 0 is not drawn at all.  Later instances overwrite earlier ones; the
+ * kernel evaluates that order-free per pixel (csrc/render.hip).  inst_img / cls_img [H][W] int32, either may be NULL; n == 0 gives
+ * zero images.  Bit-identical to the reference function.
+ * MNC_ERR_INVALID, checked before anything is launched: mask_size > 32, a rounded |coordinate| >= 2^24, H or W outside
+ * [2, 32768] (below 2 the -1 slices would wrap instead of being empty), and any rounded, clipped box with x2 < x1 or y2 < y1
+ * (cv2.resize raises on it). */
+MNC_API int mnc_render_instances(const double* boxes, const float* masks, const int* classes, int n, int mask_size,
+                                 double binarize_thresh, int image_height, int image_width, int* inst_img, int* cls_img,
+                                 int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * b3  utils.cython_bbox.bbox_overlaps (lib/utils/bbox.pyx:15-55): float64 IoU with +1 widths, [N][K] row-major.
  *     A host function in the reference (Cython) and here (C); it is not a GPU kernel and has no GPU counterpart.
  * ------------------------------------------------------------------------------------------------------------- */
@@ -631,6 +650,25 @@ MNC_API int mnc_vote_instances_ex(mnc_ctx* ctx, int mode, const float* d_boxes, 
                                   int n, int num_classes, int mask_size, int max_per_image, float nms_thresh, float iou_thresh,
                                   double binarize_thresh, int image_height, int image_width, float* d_records, int record_cap,
                                   int* d_counts);
+/* The visualisation tail of the records of mnc_vote_instances (tools/demo.py:get_vis_dict + _convert_pred_to_image + the colour
+ * map + Image.blend), everything on the device, asynchronous on ctx's stream, no host read-back.  The rows [0, min(d_counts[0],
+ * record_cap)) of d_records [record_cap][6 + S*S] with (double)score >= vis_thresh are painted in record order (class-major, keep
+ * order: the order get_vis_dict / _prepare_dict build) by the rule of mnc_render_instances, the class being the record's class id.
+ * Unlike there, a rounded, clipped box with x2 < x1 or y2 < y1 is not an error: it covers no pixel and draws no outline, but still
+ * consumes its instance id (the convention of mnc_vote_instances_ex).  Every output is optional (NULL):
+ *   d_inst, d_cls            [H][W] int32 label maps
+ *   d_inst_rgb, d_cls_rgb    [H][W][3] uint8, _get_voc_color_map()[label] (computed from the label's bits, no table)
+ *   d_overlay_rgb            [H][W][3] uint8, PIL.Image.blend(photograph as RGB, cls_rgb, alpha): (uint8)((int)a + alpha *
+ *                            ((int)b - (int)a)) in float32 with truncation, 0 <= alpha <= 1; d_bgr_hwc is the uint8 [H][W][3] BGR
+ *                            photograph (NULL: a black one)
+ *   d_kept                   int32, the number of rows painted
+ * The colour map has 256 entries: the colour of an instance label is that of label & 255, which differs from the reference (an
+ * IndexError there) only when more than 255 instances are kept -- out of reach with max_per_image <= 255 and no score ties at
+ * the voting threshold (the default is 100).  Limits: mask_size <= 32, num_classes <= 256, H and W in [2, 32768]. */
+MNC_API int mnc_render_records(mnc_ctx* ctx, const float* d_records, const int* d_counts, int record_cap, int num_classes,
+                               int mask_size, double vis_thresh, double binarize_thresh, int H, int W,
+                               const unsigned char* d_bgr_hwc, float alpha, int* d_inst, int* d_cls, unsigned char* d_inst_rgb,
+                               unsigned char* d_cls_rgb, unsigned char* d_overlay_rgb, int* d_kept);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */
@@ -727,6 +765,14 @@ MNC_API int mnc_forward_image(mnc_net* net, const unsigned char* bgr_host, int H
  *   mnc_net_fetch            waits for that image and hands out its records exactly as mnc_forward_image does. */
 MNC_API int mnc_forward_image_async(mnc_net* net, const unsigned char* bgr_host, int H, int W, float** d_records, int** d_counts);
 MNC_API int mnc_net_fetch(mnc_net* net, float* records_host, int record_cap, int* counts_host);
+/* mnc_render_records of the LAST image of the net -- its own record block, its own staged photograph -- into host memory: waits
+ * for the image, renders on the net's stream behind it (never inside the captured graph, which stays as it is, as does a following
+ * mnc_net_fetch), waits again and copies out what was asked for.  inst_host / cls_host [H][W] int32, inst_rgb_host / cls_rgb_host /
+ * overlay_rgb_host [H][W][3] uint8, kept_host one int; each may be NULL.  H, W are those of the image given to mnc_forward_image.
+ * MNC_ERR_STATE when no image has been forwarded on this net. */
+MNC_API int mnc_net_render(mnc_net* net, double vis_thresh, double binarize_thresh, float alpha, int* inst_host, int* cls_host,
+                           unsigned char* inst_rgb_host, unsigned char* cls_rgb_host, unsigned char* overlay_rgb_host,
+                           int* kept_host);
 /* Device address and Caffe-order shape of an intermediate blob of the LAST image, for parity tests: "conv5_3" (c8),
  * "rpn_cls_prob_reshape", "rpn_bbox_pred", "rois", "rois_ext", "mask_proposal" [2R][S][S] (both stages stacked),
  * "seg_cls_prob" [2R][num_classes], "boxes" [2R][4], "head_scores" [2R][6*num_classes] = [cls_score | seg_cls_score | bbox_pred]

@@ -164,6 +164,7 @@ int mnc_ctx_destroy(mnc_ctx* ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->proposal) mnc::proposal_state_free(ctx->proposal);
   if (ctx->vote_ws) (void)hipFree(ctx->vote_ws);
+  if (ctx->render_ws) (void)hipFree(ctx->render_ws);
   if (ctx->tickets) (void)hipFree(ctx->tickets);
   if (ctx->comm) mnc::comm_free(ctx);
   (void)hipStreamDestroy(ctx->stream);

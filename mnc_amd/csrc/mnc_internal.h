@@ -57,6 +57,8 @@ struct mnc_ctx {
   void* proposal = nullptr;   // mnc_proposal_state (proposal.hip), created on first use
   void* vote_ws = nullptr;    // gpu_mask_voting scratch (mv.hip), grown on demand
   size_t vote_ws_bytes = 0;
+  void* render_ws = nullptr;  // instance descriptors of mnc_render_records (render.hip), grown on demand; in no captured graph
+  size_t render_ws_bytes = 0;
   void* comm = nullptr;       // RCCL communicator state (comm.hip), set by mnc_comm_init
   // Arrival tickets of the K-range reductions that finish INSIDE the launch (gemm.hip, conv_wino4.hip): kTickets counters, zero
   // between launches -- allocated and zeroed with the context, every launch's last arriver of a tile puts its counter back to

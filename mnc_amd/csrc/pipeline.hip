@@ -119,6 +119,9 @@ struct mnc_net {
   hipGraphExec_t gexec = nullptr;
   int graph_h = -1, graph_w = -1, seen_h = -1, seen_w = -1;
   unsigned long graph_gen = 0;   // arena generation (mnc_ctx::arena_gen of both contexts) the graph was captured under
+  // mnc_net_render's outputs, device and pinned host: [inst | cls | inst_rgb | cls_rgb | overlay | kept].  Allocated on first use,
+  // outside dev_ensure: no captured graph holds these addresses
+  void* render_dev = nullptr; void* render_pin = nullptr; size_t render_cap = 0;
   // voting rule of the last stage (mnc_net_set_voting)
   int vote_mode = MNC_VOTE_MV;
   double vote_binarize = 0.4;
@@ -979,6 +982,60 @@ int mnc_net_fetch(mnc_net* net, float* records_host, int record_cap, int* counts
   return MNC_OK;
 }
 
+int mnc_net_render(mnc_net* net, double vis_thresh, double binarize_thresh, float alpha, int* inst_host, int* cls_host,
+                   unsigned char* inst_rgb_host, unsigned char* cls_rgb_host, unsigned char* overlay_rgb_host, int* kept_host) {
+  MNC_REQUIRE(net, "mnc_net_render: null pointer");
+  if (net->H <= 0) {
+    set_error("mnc_net_render: no image has been forwarded on this net");
+    return MNC_ERR_STATE;
+  }
+  const mnc_net_config& c = net->cfg;
+  mnc_ctx* ctx = net->ctx;
+  MNC_HIP_TRY(hipSetDevice(ctx->device));
+  MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  net->in_flight = false;            // the staged image has been consumed (mnc_net_fetch needs no image in flight)
+  if (*(const int*)((const char*)net->pin_out + 256) < c.post_nms_topn) {
+    // fewer proposals than post_nms_topn: the record block is final only after the re-run mnc_net_fetch makes (idempotent)
+    NET_TRY(run_heads_and_vote(net, *(const int*)((const char*)net->pin_out + 256)));
+    NET_TRY(enqueue_outputs(net));
+  }
+  const size_t px = (size_t)net->H * net->W;
+  const size_t o_cls = px * 4, o_irgb = o_cls + px * 4, o_crgb = o_irgb + px * 3, o_ovl = o_crgb + px * 3,
+               o_kept = (o_ovl + px * 3 + 255) & ~(size_t)255, total = o_kept + 256;
+  if (total > net->render_cap) {
+    if (net->render_dev) MNC_HIP_TRY(hipFree(net->render_dev));
+    if (net->render_pin) MNC_HIP_TRY(hipHostFree(net->render_pin));
+    net->render_dev = net->render_pin = nullptr;
+    net->render_cap = 0;
+    if (hipMalloc(&net->render_dev, total) != hipSuccess || hipHostMalloc(&net->render_pin, total, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      if (net->render_dev) (void)hipFree(net->render_dev);
+      net->render_dev = net->render_pin = nullptr;
+      set_error("mnc_net_render: allocating %zu bytes failed", total);
+      return MNC_ERR_NOMEM;
+    }
+    net->render_cap = total;
+  }
+  char* d = (char*)net->render_dev;
+  char* h = (char*)net->render_pin;
+  const int rows = (c.num_classes - 1) * c.max_per_image;
+  NET_TRY(mnc_render_records(ctx, net->records(), net->counts(), rows, c.num_classes, c.mask_size, vis_thresh, binarize_thresh,
+                             net->H, net->W, (const unsigned char*)net->img.p, alpha, inst_host ? (int*)d : nullptr,
+                             cls_host ? (int*)(d + o_cls) : nullptr, inst_rgb_host ? (unsigned char*)(d + o_irgb) : nullptr,
+                             cls_rgb_host ? (unsigned char*)(d + o_crgb) : nullptr,
+                             overlay_rgb_host ? (unsigned char*)(d + o_ovl) : nullptr, (int*)(d + o_kept)));
+  struct Out { void* host; size_t off, bytes; };
+  const Out outs[] = {{inst_host, 0, px * 4}, {cls_host, o_cls, px * 4}, {inst_rgb_host, o_irgb, px * 3},
+                      {cls_rgb_host, o_crgb, px * 3}, {overlay_rgb_host, o_ovl, px * 3}, {kept_host, o_kept, sizeof(int)}};
+  for (const Out& o : outs)
+    if (o.host) NET_TRY(mnc_d2h_async(ctx, h + o.off, d + o.off, o.bytes));
+  MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (const Out& o : outs)
+    if (o.host) memcpy(o.host, h + o.off, o.bytes);
+  clear_error();
+  return MNC_OK;
+}
+
 int mnc_forward_image(mnc_net* net, const unsigned char* bgr_host, int H, int W, float* records_host, int record_cap,
                       int* counts_host) {
   MNC_REQUIRE(net && records_host && counts_host && record_cap >= 0, "mnc_forward_image: null pointer");
@@ -1047,6 +1104,8 @@ int mnc_net_destroy(mnc_net* net) {
   }
   if (net->pin_img) (void)hipHostFree(net->pin_img);
   if (net->pin_out) (void)hipHostFree(net->pin_out);
+  if (net->render_dev) (void)hipFree(net->render_dev);
+  if (net->render_pin) (void)hipHostFree(net->render_pin);
   for (int i = 0; i < 2; ++i) {
     if (net->ev_fork[i]) (void)hipEventDestroy(net->ev_fork[i]);
     if (net->ev_join[i]) (void)hipEventDestroy(net->ev_join[i]);

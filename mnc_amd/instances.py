@@ -91,6 +91,9 @@ class InstanceBlock(object):
         if getattr(self, "_pin", None):
             _lib.call("mnc_host_free", self._net._ctx.h, self._pin)
             self._pin = None
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.release()
+            self._renderer = None
         self._buf.release()
 
 
@@ -130,6 +133,18 @@ class InstanceView(object):
     def lists(self):
         counts, rec = self.fetch()
         return split_records(rec, counts[1:self.num_classes], self.S)
+
+    def render(self, H, W, vis_thresh=0.5, image=None, alpha=0.8, binarize_thresh=None):
+        """Label maps, VOC colours and the blend over `image` (uint8 BGR [H, W, 3], or None) of this image's instances scoring
+        >= vis_thresh, straight from the device records (mnc_render_records; no lists() / get_vis_dict): -> a RenderResult
+        (mnc_amd/render.py) with .inst, .cls, .inst_rgb, .cls_rgb, .overlay as lazily copied arrays and .kept.  Enqueued on the
+        net's stream behind the voting; the result's buffers are reused by the next render() of this block."""
+        from .render import DeviceRenderer
+        blk = self._blk
+        if getattr(blk, "_renderer", None) is None:
+            blk._renderer = DeviceRenderer(blk._net._ctx.h)
+        return blk._renderer.render(self.records_ptr, self.counts_ptr, self.rows_cap, self.num_classes, self.S, H, W, vis_thresh,
+                                    binarize_thresh, image, alpha)
 
 
 def split_records(rec, class_counts, S):

@@ -74,7 +74,10 @@ cfg.TEST = AttrDict(
     DEVICE_RESULTS=True, DEVICE_PREP=True,
     # not in the reference: imdb.evaluate_segmentation counts the SDS overlaps of all classes on the GPU in one call
     # (utils/voc_eval.py:voc_eval_sds_device; same APs as the CPU loop)
-    USE_GPU_SDS_EVAL=False)
+    USE_GPU_SDS_EVAL=False,
+    # not in the reference: utils/vis_seg.py:vis_seg and tools/demo.py render label maps, colours and the blend on the GPU
+    # (csrc/render.hip; the same pixels as the numpy / PIL form)
+    USE_GPU_VIS=False)
 
 
 def get_output_dir(imdb, net):

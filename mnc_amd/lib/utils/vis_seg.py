@@ -1,7 +1,9 @@
 """Rendering of instance-segmentation results (reference: lib/utils/vis_seg.py:14-147; the tail of tools/demo.py:150-191).
-SURVEY section 8f row n4 (visualisation tail).  Host-only; cv2 is replaced by numpy / PIL:
+SURVEY section 8f row n4 (visualisation tail).  The default is the host form, cv2 replaced by numpy / PIL:
 `_convert_pred_to_image` and `_get_voc_color_map` are pinned against the reference's functions
-(tests/golden/make_golden_eval.py); file encoding (JPEG / PNG bytes) is PIL's, not OpenCV's."""
+(tests/golden/make_golden_eval.py).  With cfg.TEST.USE_GPU_VIS the label maps, their colours and the blend come from the GPU
+(csrc/render.hip: `_convert_pred_to_image_device`, mnc_amd/render.py), bit for bit the same.  File encoding (JPEG / PNG bytes)
+is PIL's in both forms, not OpenCV's."""
 import os
 import pickle
 
@@ -27,6 +29,14 @@ def vis_seg(img_names, cls_names, output_dir, gt_dir, image_ext='.jpg'):
         print(image_name)
         img_data = imread(os.path.join(gt_dir, 'img', image_name + image_ext))            # BGR
         img_height, img_width = img_data.shape[:2]
+        if cfg.TEST.USE_GPU_VIS:
+            # label maps, colours and the 0.8 blend in one launch (mnc_render_records); only the encoding is left to PIL
+            from mnc_amd.render import render_pred_dict
+            res = render_pred_dict(img_width, img_height, res_list[img_ind], image=np.ascontiguousarray(img_data), alpha=0.8)
+            Image.fromarray(res.inst_rgb).save(os.path.join(inst_dir, image_name + '.jpg'))
+            Image.fromarray(res.cls_rgb).save(os.path.join(cls_dir, image_name + '.jpg'))
+            Image.fromarray(res.overlay).convert('RGBA').save(os.path.join(res_dir, image_name + '.png'), 'PNG')
+            continue
         inst_img, cls_img = _convert_pred_to_image(img_width, img_height, res_list[img_ind])
         inst_rgb, cls_rgb = color_map[inst_img], color_map[cls_img]                       # cv2.imwrite of the BGR-flipped map
         Image.fromarray(inst_rgb).save(os.path.join(inst_dir, image_name + '.jpg'))
@@ -85,6 +95,28 @@ def _convert_pred_to_image(img_width, img_height, pred_dict):
         cls_img[box[1]:box[3] + 1, box[2] - 1:box[2] + 1] = 150
         cls_img[box[1] - 1:box[1] + 1, box[0]:box[2] + 1] = 150
         cls_img[box[3] - 1:box[3] + 1, box[0]:box[2] + 1] = 150
+    return inst_img.astype(int), cls_img.astype(int)
+
+
+def _convert_pred_to_image_device(img_width, img_height, pred_dict, device_id=None):
+    """_convert_pred_to_image on the GPU (mnc_render_instances, csrc/render.hip): same arguments, same two `int` arrays, bit for
+    bit.  An instance whose rounded, clipped box is empty raises (cv2.resize raises on it in the reference)."""
+    from mnc_amd import _lib
+    if device_id is None:
+        device_id = int(cfg.get('GPU_ID', 0))
+    n = len(pred_dict['boxes'])
+    S = int(np.asarray(pred_dict['masks'][0]).shape[-1]) if n else int(cfg.MASK_SIZE)
+    # np.round acts in the boxes' own precision; float32 -> float64 is exact, so rounding the widened value is the same
+    boxes = np.zeros((n, 4), np.float64)
+    masks = np.zeros((n, S * S), np.float32)
+    for i in range(n):
+        boxes[i] = np.asarray(pred_dict['boxes'][i], np.float64)[:4]
+        masks[i] = np.asarray(pred_dict['masks'][i], np.float32).reshape(-1)
+    classes = np.ascontiguousarray(np.asarray(pred_dict['cls_name'], np.int32).reshape(n))
+    inst_img = np.zeros((img_height, img_width), np.int32)
+    cls_img = np.zeros((img_height, img_width), np.int32)
+    _lib.call('mnc_render_instances', _lib.ptr(boxes), _lib.ptr(masks), _lib.ptr(classes), n, S, float(cfg.BINARIZE_THRESH),
+              int(img_height), int(img_width), _lib.ptr(inst_img), _lib.ptr(cls_img), int(device_id))
     return inst_img.astype(int), cls_img.astype(int)
 
 

@@ -148,6 +148,7 @@ class NativeNet(object):
         rec = np.zeros((cap, self.rec_dim), np.float32)
         counts = np.zeros(int(self.cfg.num_classes), np.int32)
         _lib.call("mnc_forward_image", self.h, _lib.ptr(im), im.shape[0], im.shape[1], _lib.ptr(rec), cap, _lib.ptr(counts))
+        self._hw = (int(im.shape[0]), int(im.shape[1]))
         return counts, rec[:min(int(counts[0]), cap)]
 
     def launch(self, im):
@@ -156,6 +157,7 @@ class NativeNet(object):
         if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
             raise TypeError("launch takes a uint8 HxWx3 image (got %s %r)" % (im.dtype, im.shape))
         _lib.call("mnc_forward_image_async", self.h, _lib.ptr(im), im.shape[0], im.shape[1], None, None)
+        self._hw = (int(im.shape[0]), int(im.shape[1]))
 
     def fetch(self, record_cap=None):
         """Second half: wait for the launched image, -> (counts, records) as forward_image."""
@@ -164,6 +166,33 @@ class NativeNet(object):
         counts = np.zeros(int(self.cfg.num_classes), np.int32)
         _lib.call("mnc_net_fetch", self.h, _lib.ptr(rec), cap, _lib.ptr(counts))
         return counts, rec[:min(int(counts[0]), cap)]
+
+    def render(self, vis_thresh=0.5, alpha=0.8, overlay=True, inst=True, cls=True, rgb=False, binarize_thresh=0.4):
+        """The visualisation tail of the LAST image on the GPU (mnc_net_render: the net's own records and staged photograph, on
+        its stream behind the image, outside the captured graph): -> dict with 'kept' (instances scoring >= vis_thresh) and, as
+        asked for, 'inst' / 'cls' (int32 [H, W] label maps of utils/vis_seg.py:_convert_pred_to_image), 'overlay' (uint8 [H, W, 3]
+        RGB: the class colours blended `alpha` over the photograph, PIL.Image.blend's rule), 'inst_rgb' / 'cls_rgb' (rgb=True).
+        A following fetch() / forward_image() is not disturbed."""
+        if not getattr(self, "_hw", None):
+            _lib.call("mnc_net_render", self.h, float(vis_thresh), float(binarize_thresh), float(alpha), None, None, None, None, None,
+                      None)                              # raises MNC_ERR_STATE: no image has been forwarded on this net
+        H, W = self._hw
+        out = {}
+        if inst:
+            out["inst"] = np.zeros((H, W), np.int32)
+        if cls:
+            out["cls"] = np.zeros((H, W), np.int32)
+        if rgb:
+            out["inst_rgb"] = np.zeros((H, W, 3), np.uint8)
+            out["cls_rgb"] = np.zeros((H, W, 3), np.uint8)
+        if overlay:
+            out["overlay"] = np.zeros((H, W, 3), np.uint8)
+        kept = ctypes.c_int(0)
+        _lib.call("mnc_net_render", self.h, float(vis_thresh), float(binarize_thresh), float(alpha), _lib.ptr(out.get("inst")),
+                  _lib.ptr(out.get("cls")), _lib.ptr(out.get("inst_rgb")), _lib.ptr(out.get("cls_rgb")), _lib.ptr(out.get("overlay")),
+                  ctypes.addressof(kept))
+        out["kept"] = int(kept.value)
+        return out
 
     def detect(self, im):
         """-> (list_result_mask, list_result_box) as the reference's gpu_mask_voting returns them."""
@@ -256,9 +285,12 @@ class ImageStream(object):
         for counts, records in stream.map(images): ...
     """
 
-    def __init__(self, weights, in_flight=8, voting="mv", **kwargs):
+    def __init__(self, weights, in_flight=8, voting="mv", render=False, render_args=None, **kwargs):
+        """render=True: every result is (counts, records, rendering) with rendering = NativeNet.render(**render_args) of that
+        image, made when the image is drained (on its own net's stream, so the other images in flight keep running)."""
         if in_flight < 1:
             raise ValueError("in_flight must be >= 1")
+        self._render = dict(render_args or {}) if render else None
         vote = {"voting": voting}
         if "binarize_thresh" in kwargs:
             vote["binarize_thresh"] = kwargs.pop("binarize_thresh")
@@ -267,11 +299,17 @@ class ImageStream(object):
         self._pending = []                      # indices of the nets holding an unfetched image, oldest first
         self._next = 0
 
+    def _take(self, net, record_cap):
+        res = net.fetch(record_cap)
+        if self._render is None:
+            return res
+        return res + (net.render(**self._render),)
+
     def submit(self, im, record_cap=None):
         """Launch `im`; -> (counts, records) of the OLDEST image in flight when every net is busy, else None."""
         out = None
         if len(self._pending) == len(self.nets):
-            out = self.nets[self._pending.pop(0)].fetch(record_cap)
+            out = self._take(self.nets[self._pending.pop(0)], record_cap)
         which = self._next
         self._next = (self._next + 1) % len(self.nets)
         self.nets[which].launch(im)
@@ -282,7 +320,7 @@ class ImageStream(object):
         """-> the results of the images still in flight, oldest first."""
         out = []
         while self._pending:
-            out.append(self.nets[self._pending.pop(0)].fetch(record_cap))
+            out.append(self._take(self.nets[self._pending.pop(0)], record_cap))
         return out
 
     def map(self, images, record_cap=None):

@@ -3,7 +3,7 @@
 build the net, warm up twice on a grey image, then per image: im_detect (timed "forward time"), gpu_mask_voting,
 optional visualisation.
 
-    python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis]
+    python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -36,6 +36,8 @@ def parse_args(argv=None):
     p.add_argument("--out-dir", dest="out_dir", default=None, help="where the *_mnc.png visualisations go [next to each image]")
     p.add_argument("--vis-thresh", dest="vis_thresh", default=0.5, type=float,
                    help="score threshold of the drawn instances [0.5, the reference's constant, demo.py:103]")
+    p.add_argument("--device-vis", dest="device_vis", action="store_true",
+                   help="render the class image and its blend over the photo on the GPU (cfg.TEST.USE_GPU_VIS)")
     return p.parse_args(argv)
 
 
@@ -89,17 +91,33 @@ def _read_image_bgr(path):
     return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])
 
 
-def _visualise(im_bgr, pred, out_path):
-    """The tail of the reference demo (tools/demo.py:150-191): class-id image of the voted instances
-    (lib/utils/vis_seg.py:_convert_pred_to_image) in VOC colours, blended 0.8 over the photo, one "<class> <score>" label per
-    instance at its box corner, saved as PNG (matplotlib; PIL-only without the labels when matplotlib is missing)."""
+def _class_overlay(im_bgr, pred, view=None, vis_thresh=0.5):
+    """-> PIL RGB image: the class-id image of the instances in VOC colours blended 0.8 over the photo.  With
+    cfg.TEST.USE_GPU_VIS it comes from the GPU in one launch (csrc/render.hip) -- from the device records of `view` (the
+    InstanceView of the voting; no lists() / get_vis_dict on this path) or else from `pred` -- with the same pixels."""
     from PIL import Image
-    from utils.vis_seg import _convert_pred_to_image, _get_voc_color_map
     h, w = im_bgr.shape[:2]
+    if cfg.TEST.USE_GPU_VIS:
+        if view is not None:
+            # the record's class id is get_vis_dict's cls_ind + 1 (over the foreground list) and vis_seg._prepare_dict's cls_ind
+            # (over all classes): the same number
+            res = view.render(h, w, vis_thresh=vis_thresh, image=np.ascontiguousarray(im_bgr), alpha=0.8)
+        else:
+            from mnc_amd.render import render_pred_dict
+            res = render_pred_dict(w, h, pred, image=np.ascontiguousarray(im_bgr), alpha=0.8)
+        return Image.fromarray(res.overlay)
+    from utils.vis_seg import _convert_pred_to_image, _get_voc_color_map
     _, cls_img = _convert_pred_to_image(w, h, pred)
     cls_rgb = _get_voc_color_map().astype(np.uint8)[cls_img]
     background = Image.fromarray(np.ascontiguousarray(im_bgr[:, :, ::-1])).convert("RGBA")
-    blended = Image.blend(background, Image.fromarray(cls_rgb).convert("RGBA"), 0.8).convert("RGB")
+    return Image.blend(background, Image.fromarray(cls_rgb).convert("RGBA"), 0.8).convert("RGB")
+
+
+def _visualise(im_bgr, pred, out_path, view=None, vis_thresh=0.5):
+    """The tail of the reference demo (tools/demo.py:150-191): class-id image of the voted instances
+    (lib/utils/vis_seg.py:_convert_pred_to_image) in VOC colours, blended 0.8 over the photo, one "<class> <score>" label per
+    instance at its box corner, saved as PNG (matplotlib; PIL-only without the labels when matplotlib is missing)."""
+    blended = _class_overlay(im_bgr, pred, view, vis_thresh)
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -134,6 +152,8 @@ def build_net(args):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.device_vis:
+        cfg.TEST.USE_GPU_VIS = True
     net = build_net(args)
     warm = 128 * np.ones((300, 500, 3), dtype=np.float32)
     for _ in range(2):
@@ -162,7 +182,12 @@ def main(argv=None):
             if args.out_dir:
                 os.makedirs(args.out_dir, exist_ok=True)
                 out = os.path.join(args.out_dir, os.path.basename(out))
-            _visualise(im, pred, out)
+            # with the results on the device, the overlay is rendered from the voting's own record block; `pred` (from the records
+            # fetched for the count above) only places the text labels
+            from mnc_amd.devarray import DeviceArray
+            blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
+            view = blk.view() if cfg.TEST.USE_GPU_VIS and blk is not None and im.dtype == np.uint8 else None
+            _visualise(im, pred, out, view, args.vis_thresh)
             print("wrote", out)
     net.close()
 

@@ -12,6 +12,12 @@ included (image preparation, forward, result hand-over) -- what bench.py's HBM-r
 Seeded synthetic weights, pixels and proposals.  Prints wall time per image and the per-kernel breakdown (HIP events).
 
     python tools/task_bench.py --task seg|cfm|resnet [--iters 5] [--math fp32|bf16x3|f16] [--host-prep]
+
+  --task seg --vis   instead: the visualisation tail behind that body (tools/demo.py: class image, colours, 0.8
+               blend over the photo) per image, in host form (get_vis_dict + utils/vis_seg.py + PIL) against device form
+               (InstanceView.render, csrc/render.hip, with the copy of one int32 label map and the RGB overlay to the host);
+               medians over --iters images, one JSON line.  Synthetic weights give meaningless scores, so the threshold is the
+               score of the --vis-keep'th best instance unless --vis-thresh is given.
 """
 import argparse
 import json
@@ -35,7 +41,12 @@ def main():
     ap.add_argument("--math", default=os.environ.get("MNC_MATH", "fp32"))
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--vis", action="store_true", help="--task seg: time the visualisation tail, host form against device form")
+    ap.add_argument("--vis-thresh", type=float, default=None)
+    ap.add_argument("--vis-keep", type=int, default=40)
     args = ap.parse_args()
+    if args.vis and args.task != "seg":
+        ap.error("--vis goes with --task seg")
     resnet = args.task == "resnet"
     if resnet:
         args.task = "seg"
@@ -90,6 +101,8 @@ def main():
             masks, bxs, scores = t._segmentation_forward(im)
             return gpu_mask_voting(masks, bxs, scores, 21, 100, im.shape[1], im.shape[0])
 
+        if args.vis:
+            return vis_tail(args, t, body, imread(Imdb().image_path_at(0)))
         calls = []
         real = t.net.forward
 
@@ -129,6 +142,53 @@ def main():
                                        "tflops": round(v[2] / v[1] / 1e9, 1) if v[1] > 0 and v[2] > 0 else None}
                                       for k, v in rows[:14]]}))
         t.net.close()
+
+
+def vis_tail(args, t, body, im):
+    import demo
+    from PIL import Image
+    from mnc_config import cfg
+    from utils.vis_seg import _convert_pred_to_image, _get_voc_color_map
+    H, W = im.shape[:2]
+    result_mask, result_box = body()                                 # warm-up; the records every timed image renders
+    scores = np.sort(np.concatenate([b[:, 4] for b in result_box]))[::-1]
+    thr = args.vis_thresh if args.vis_thresh is not None else float(scores[min(args.vis_keep, len(scores)) - 1])
+    view = t.net._inst.view()
+    color_map = _get_voc_color_map().astype(np.uint8)
+
+    def host():
+        pred = demo.get_vis_dict(result_box, result_mask, "im0", demo.CLASSES, thr)
+        _, cls_img = _convert_pred_to_image(W, H, pred)
+        cls_rgb = color_map[cls_img]
+        background = Image.fromarray(np.ascontiguousarray(im[:, :, ::-1])).convert("RGBA")
+        return len(pred["boxes"]), cls_img, np.asarray(Image.blend(background, Image.fromarray(cls_rgb).convert("RGBA"), 0.8).convert("RGB"))
+
+    def device(upload):
+        res = view.render(H, W, vis_thresh=thr, image=im if upload else dev_im[0], alpha=0.8)
+        if upload:
+            dev_im[0] = res.renderer.image_ptr
+        return res.kept, res.cls, res.overlay
+
+    dev_im = [None]
+    want, got = host(), device(True)
+    same = want[0] == got[0] and np.array_equal(want[1], got[1]) and np.array_equal(want[2], got[2])
+    ms = {}
+    for name, fn in (("host", host), ("device_with_upload", lambda: device(True)), ("device", lambda: device(False))):
+        times = []
+        for _ in range(max(args.iters, 1)):
+            t.net.sync()
+            t0 = time.perf_counter()
+            fn()
+            times.append((time.perf_counter() - t0) * 1e3)
+        ms[name] = (round(sorted(times)[len(times) // 2], 3), round(min(times), 3))
+    print(json.dumps({"workload": "visualisation tail of mnc 5-stage vgg16, %dx%d image: class label map + colours + 0.8 overlay" % (H, W),
+                      "kept": int(want[0]), "vis_thresh": thr, "images": max(args.iters, 1), "device_equals_host": bool(same),
+                      "host_ms_median": ms["host"][0], "host_ms_min": ms["host"][1],
+                      "device_ms_median": ms["device"][0], "device_ms_min": ms["device"][1],
+                      "device_with_photo_upload_ms_median": ms["device_with_upload"][0],
+                      "device_outputs_copied": "cls int32 [H,W] + overlay uint8 [H,W,3]",
+                      "note": "device: photograph already on the GPU (as NativeNet's staged image is); with_photo_upload adds its H2D copy"}))
+    t.net.close()
 
 
 if __name__ == "__main__":
