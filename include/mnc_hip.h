@@ -190,6 +190,24 @@ MNC_API int mnc_render_instances(const double* boxes, const float* masks, const 
                                  int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
+ *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers, one call per image.  superpixels [H][W] ids; proposal i is the union P_i of the superpixels
+ * label_ids[label_ptr[i] .. label_ptr[i + 1]) (np.in1d: duplicates and ids that occur nowhere in the map change nothing).
+ * boxes[i] = (min col, min row, max col, max row) of P_i as float64; masks[i] [mask_size][mask_size] bytes 0 / 1 =
+ * cv2.resize(P_i cropped to its box, (mask_size, mask_size), INTER_NEAREST): mask[dy][dx] = P_i[y1 + sy(dy)][x1 + sx(dx)],
+ * sx(dx) = min(floor(dx * ifx), w - 1) with ifx = 1.0 / ((double)mask_size / w) in float64, w = x2 - x1 + 1; sy alike with h
+ * (OpenCV's resizeNN: the inverse scale formed in two steps, then cvFloor -- stated from OpenCV's published source).
+ * n == 0 returns before any device work.  MNC_ERR_INVALID, checked before anything is launched: n < 0, mask_size outside
+ * [1, 32], H or W outside [1, 32768], label_ptr[0] != 0 or label_ptr decreasing, any id of superpixels or label_ids outside
+ * [0, 65535].  A proposal with empty P_i (an empty list, or none of its ids in the map; the reference dies in np.min) is
+ * detected by the kernel from its own data: MNC_ERR_INVALID after the call's device work, mnc_last_error names the smallest
+ * such index, and boxes / masks are then unspecified. */
+MNC_API int mnc_mcg_maskdb(const int* superpixels, int H, int W, const int* label_ptr, const int* label_ids, int n,
+                           int mask_size, double* boxes, unsigned char* masks, int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * b3  utils.cython_bbox.bbox_overlaps (lib/utils/bbox.pyx:15-55): float64 IoU with +1 widths, [N][K] row-major.
  *     A host function in the reference (Cython) and here (C); it is not a GPU kernel and has no GPU counterpart.
  * ------------------------------------------------------------------------------------------------------------- */

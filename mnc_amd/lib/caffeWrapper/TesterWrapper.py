@@ -232,10 +232,17 @@ class TesterWrapper(object):
 
     def _load_mcg_maskdb(self, im_i):
         """{'boxes': [n,4], 'masks': [n,S,S]} of image im_i: the .mat files tools/prepare_mcg_maskdb.py writes
-        (TesterWrapper.py:339-341).  scipy is needed for this task only."""
+        (TesterWrapper.py:339-341).  scipy is needed for this task only.  Not in the reference: with cfg.TEST.MCG_RAW_DIR set, an
+        image without that file gets the same dict built on the GPU from MCG_RAW_DIR/<name>.mat, the published MCG candidates
+        (db/mcg_maskdb.py:mcg_maskdb_device); nothing is written."""
         import scipy.io
-        path = os.path.join(cfg.TEST.get('MCG_MASKDB_DIR', 'data/cache/voc_2012_val_mcg_maskdb/'),
-                            self.imdb._image_index[im_i] + '.mat')
+        name = self.imdb._image_index[im_i]
+        path = os.path.join(cfg.TEST.get('MCG_MASKDB_DIR', 'data/cache/voc_2012_val_mcg_maskdb/'), name + '.mat')
+        raw_dir = cfg.TEST.get('MCG_RAW_DIR', '')
+        if raw_dir and not os.path.exists(path):
+            from db import mcg_maskdb
+            return mcg_maskdb.mcg_maskdb_device(*mcg_maskdb.read_mcg_raw(os.path.join(raw_dir, name + '.mat')),
+                                                mask_size=cfg.MASK_SIZE)
         return scipy.io.loadmat(path)
 
     def cfm_network_forward(self, im_i):

@@ -77,7 +77,10 @@ cfg.TEST = AttrDict(
     USE_GPU_SDS_EVAL=False,
     # not in the reference: utils/vis_seg.py:vis_seg and tools/demo.py render label maps, colours and the blend on the GPU
     # (csrc/render.hip; the same pixels as the numpy / PIL form)
-    USE_GPU_VIS=False)
+    USE_GPU_VIS=False,
+    # not in the reference: where an image has no .mat under MCG_MASKDB_DIR, `--task cfm` builds its maskdb entry on the GPU from
+    # MCG_RAW_DIR/<name>.mat, the published MCG candidates (db/mcg_maskdb.py, csrc/mcg_maskdb.hip); '' = off, the file must exist
+    MCG_RAW_DIR='')
 
 
 def get_output_dir(imdb, net):
