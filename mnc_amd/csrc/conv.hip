@@ -662,7 +662,7 @@ int mnc_conv3x3(mnc_ctx* ctx, const float* d_in, const float* d_wpk, const float
   if (ksplit > 1) {
     int rc = ensure_scratch(ctx, (size_t)ksplit * Cout * H * W * 4);
     if (rc) return rc;
-    part = (float*)ctx->scratch;
+    part = (float*)ctx->scratch.p;
   }
   const int tx = cdiv(W, kTileCols), ty = cdiv(H, rows);
   const double flops = 2.0 * H * W * 9.0 * Cin * Cout;

@@ -527,7 +527,7 @@ static int conv3x3_sw(mnc_ctx* ctx, const char* name, const void* d_in, const vo
     int rc = ensure_scratch(ctx, (size_t)H * W * Cout * (MODE == 0 ? 4 : 2));
     if (rc) return rc;
     d_pooled = d_out_pk;
-    d_out_pk = ctx->scratch;
+    d_out_pk = ctx->scratch.p;
     pool = 0;
   }
   const double opix = pool ? (double)((H + 1) / 2) * ((W + 1) / 2) : (double)H * W;
@@ -647,8 +647,8 @@ static int sw_pack_input(mnc_ctx* ctx, int mode, const float* d_c8, size_t n, co
   if (rc) return rc;
   const long npix = (long)(n / 8);
   auto kern = mode == 0 ? pack_act_kernel<0> : mode == 1 ? pack_act_kernel<1> : pack_act_kernel<2>;
-  hipLaunchKernelGGL(kern, dim3(sw_grid_for(npix)), dim3(256), 0, ctx->stream, (const float4*)d_c8, ctx->scratch, npix);
-  *packed = ctx->scratch;
+  hipLaunchKernelGGL(kern, dim3(sw_grid_for(npix)), dim3(256), 0, ctx->stream, (const float4*)d_c8, ctx->scratch.p, npix);
+  *packed = ctx->scratch.p;
   return MNC_OK;
 }
 

@@ -1100,7 +1100,7 @@ static int wino_impl(mnc_ctx* ctx, const float* d_in, const float* d_wpk, const 
   if (ksplit > 1 || ksplit_b > 1) {
     int rc = ensure_scratch(ctx, (size_t)((ksplit > ksplit_b ? ksplit : ksplit_b) + (pool && ksplit > 1 ? 1 : 0)) * Cout * H * W * 4);
     if (rc) return rc;
-    part = (float*)ctx->scratch;
+    part = (float*)ctx->scratch.p;
     if (pool && ksplit > 1) full = part + (size_t)ksplit * Cout * H * W;
   }
   const int kpool = (pool && ksplit == 1) ? 1 : 0;               // pooling inside the kernel's epilogue

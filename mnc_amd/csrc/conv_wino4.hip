@@ -787,7 +787,7 @@ static int wino4_impl(mnc_ctx* ctx, const float* d_in, const float* d_wpk, const
   if (smax > 1) {
     int rc = ensure_scratch(ctx, inkernel ? (size_t)cut_tiles * smax * 65536 : (size_t)smax * Cout * H * W * 4);
     if (rc) return rc;
-    part = (float*)ctx->scratch;
+    part = (float*)ctx->scratch.p;
   }
   const double flops = 2.0 * H * W * 9.0 * Cin * Cout;           // ALGORITHMIC work of the convolution (direct form)
   const double out_px = pool ? (double)((H + 1) / 2) * ((W + 1) / 2) : (double)H * W;

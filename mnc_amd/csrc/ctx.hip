@@ -28,26 +28,46 @@ void set_error(const char* fmt, ...) {
 }
 void clear_error() { g_err[0] = 0; }
 
-int ensure_scratch(mnc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->scratch_bytes) return MNC_OK;
-  MNC_NO_CAPTURE(ctx, "scratch arena growth");
-  MNC_HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->scratch) {
-    MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    MNC_HIP_TRY(hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    ++ctx->arena_gen;
+int arena_ensure(DevArena* a, size_t bytes, size_t slack, const char* who, hipStream_t stream, mnc_ctx* ctx, bool graph_visible) {
+  if (bytes <= a->cap) return MNC_OK;
+  if (ctx) {
+    MNC_NO_CAPTURE(ctx, who);
+    MNC_HIP_TRY(hipSetDevice(ctx->device));
   }
-  size_t want = bytes + (bytes >> 2);
-  hipError_t e = hipMalloc(&ctx->scratch, want);
+  if (a->p) {
+    MNC_HIP_TRY(hipStreamSynchronize(stream));
+    MNC_HIP_TRY(hipFree(a->p));
+  }
+  a->p = nullptr;
+  a->cap = 0;
+  if (ctx && graph_visible) ++ctx->arena_gen;     // a captured graph that holds the old address must not be replayed (pipeline.hip)
+  const size_t want = bytes + slack;
+  const hipError_t e = hipMalloc(&a->p, want);
   if (e != hipSuccess) {
-    set_error("hipMalloc(%zu) for scratch failed: %s", want, hipGetErrorString(e));
+    (void)hipGetLastError();                      // (the error is sticky: the next MNC_HIP_TRY would report it again)
+    a->p = nullptr;
+    set_error("%s: hipMalloc(%zu) failed: %s", who, want, hipGetErrorString(e));
     return MNC_ERR_NOMEM;
   }
-  ctx->scratch_bytes = want;
-  ++ctx->arena_gen;
+  a->cap = want;
   return MNC_OK;
+}
+
+void arena_free(DevArena* a) {
+  if (a->p) (void)hipFree(a->p);
+  *a = DevArena();
+}
+
+int ensure_scratch(mnc_ctx* ctx, size_t bytes) {
+  return arena_ensure(&ctx->scratch, bytes, bytes >> 2, "scratch arena", ctx->stream, ctx, true);
+}
+
+int CallBuf::alloc(const char* who, size_t bytes) {
+  if (hipMalloc(&p, bytes) == hipSuccess) return MNC_OK;
+  (void)hipGetLastError();
+  p = nullptr;
+  set_error("%s: hipMalloc(%zu) failed", who, bytes);
+  return MNC_ERR_NOMEM;
 }
 
 static hipEvent_t take_event(mnc_ctx* ctx) {
@@ -161,10 +181,10 @@ int mnc_ctx_destroy(mnc_ctx* ctx) {
     (void)hipEventDestroy(r.stop);
   }
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
+  arena_free(&ctx->scratch);
   if (ctx->proposal) mnc::proposal_state_free(ctx->proposal);
-  if (ctx->vote_ws) (void)hipFree(ctx->vote_ws);
-  if (ctx->render_ws) (void)hipFree(ctx->render_ws);
+  arena_free(&ctx->vote_ws);
+  arena_free(&ctx->render_ws);
   if (ctx->tickets) (void)hipFree(ctx->tickets);
   if (ctx->comm) mnc::comm_free(ctx);
   (void)hipStreamDestroy(ctx->stream);

@@ -994,7 +994,7 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
   if (splits > 1) {
     int rc = ensure_scratch(ctx, slab ? (size_t)tn * tm * splits * 163840 : (size_t)splits * M * N * 4);
     if (rc) return rc;
-    part = (float*)ctx->scratch;
+    part = (float*)ctx->scratch.p;
   }
   const double flops = 2.0 * M * (double)N * K, bytes = 4.0 * ((double)N * K + (double)M * K + (double)M * N);
   {
@@ -1151,7 +1151,7 @@ int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float*
   if (splits > 1) {
     int rc = ensure_scratch(ctx, (size_t)2 * tn * tm * splits * 163840);
     if (rc) return rc;
-    part = (float*)ctx->scratch;
+    part = (float*)ctx->scratch.p;
   }
   constexpr int lds = 65536 + (320 + kBN) * 32 * 4;
   {

@@ -776,10 +776,10 @@ static int fc_lowp(mnc_ctx* ctx, const char* what, const float* d_a, const uint4
   const size_t part_bytes = splits > 1 ? (((size_t)splits * M * N * 4 + 255) & ~(size_t)255) : 0;
   int rc = ensure_scratch(ctx, part_bytes + (d_pre ? 0 : (size_t)M * K * (F16 ? 2 : 4)));
   if (rc) return rc;
-  float* part = splits > 1 ? (float*)ctx->scratch : nullptr;
+  float* part = splits > 1 ? (float*)ctx->scratch.p : nullptr;
   const uint4* d_ax = d_pre;
   if (!d_pre) {
-    uint4* conv = (uint4*)((char*)ctx->scratch + part_bytes);
+    uint4* conv = (uint4*)((char*)ctx->scratch.p + part_bytes);
     LaunchScope ls(ctx, F16 ? "fc_f16_convert" : "fc_bf16x3_split", 0.0, (F16 ? 6.0 : 8.0) * M * (double)K);
     if (F16) f16_pack_launch(ctx, d_a, conv, M, K, M, 1, F16 == 2);
     else x3_pack_launch(ctx, d_a, conv, M, K, M, 1);
@@ -920,11 +920,11 @@ static int fc_lowp_pair(mnc_ctx* ctx, const char* what, const float* d_a0, const
   const size_t conv_bytes = ((size_t)M * K * (F16 ? 2 : 4) + 255) & ~(size_t)255;
   int rc = ensure_scratch(ctx, part_bytes + (d_pre0 ? 0 : conv_bytes) + (d_pre1 ? 0 : conv_bytes));
   if (rc) return rc;
-  float* part = splits > 1 ? (float*)ctx->scratch : nullptr;
+  float* part = splits > 1 ? (float*)ctx->scratch.p : nullptr;
   const uint4* ax[2] = {d_pre0, d_pre1};
   int ms[2] = {mstride, mstride};
   {
-    char* conv = (char*)ctx->scratch + part_bytes;
+    char* conv = (char*)ctx->scratch.p + part_bytes;
     const float* a32[2] = {d_a0, d_a1};
     for (int i = 0; i < 2; ++i) {
       if (ax[i]) continue;

@@ -98,14 +98,6 @@ __global__ __launch_bounds__(kMcgThreads) void mcg_mask_kernel(const int* __rest
   }
 }
 
-namespace {
-struct McgDevBuf {                        // this call's device scratch, freed on every way out
-  void* p = nullptr;
-  ~McgDevBuf() { if (p) (void)hipFree(p); }
-};
-size_t mcg_up256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
 }  // namespace mnc
 
 using namespace mnc;
@@ -133,39 +125,39 @@ int mnc_mcg_maskdb(const int* superpixels, int H, int W, const int* label_ptr, c
 
   const int S = mask_size;
   const size_t nP = (size_t)n, table_bytes = ((size_t)max_id + 1) * 16;
-  // [label map | label_ptr | label_ids | table, error word | boxes | masks]
-  const size_t o_ptr = mcg_up256(px * 4), o_ids = o_ptr + mcg_up256((nP + 1) * 4), o_table = o_ids + mcg_up256(L * 4),
-               o_err = o_table + table_bytes, o_boxes = o_table + mcg_up256(table_bytes + 4), o_masks = o_boxes + mcg_up256(nP * 32),
-               total = o_masks + mcg_up256(nP * S * S);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int rc = legacy_ws(device_id, 0, &w, &lock);      // the device's stream (and device check); the buffer is this call's own
+  int *d_sp, *d_ptr, *d_ids, *d_table; double* d_boxes; unsigned char* d_masks;
+  auto layout = [&](WsLayout l) {
+    d_sp = l.take<int>(px);
+    d_ptr = l.take<int>(nP + 1);
+    d_ids = l.take<int>(L);
+    d_table = l.take<int>(table_bytes / 4 + 1);     // the error word follows the table
+    d_boxes = l.take<double>(nP * 4);
+    d_masks = l.take<unsigned char>(nP * S * S);
+    return l.bytes();
+  };
+  HostScope hs;
+  int rc = hs.open(device_id, 0);                   // the device's stream (and device check); the buffer is this call's own
   if (rc) return rc;
-  McgDevBuf buf;
-  if (hipMalloc(&buf.p, total) != hipSuccess) {
-    (void)hipGetLastError();
-    buf.p = nullptr;
-    set_error("mnc_mcg_maskdb: hipMalloc(%zu) failed", total);
-    return MNC_ERR_NOMEM;
-  }
-  char* d = (char*)buf.p;
-  hipStream_t s = w->stream;
-  MNC_HIP_TRY(hipMemcpyAsync(d, superpixels, px * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(d + o_ptr, label_ptr, (nP + 1) * 4, hipMemcpyHostToDevice, s));
-  if (L) MNC_HIP_TRY(hipMemcpyAsync(d + o_ids, label_ids, L * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemsetAsync(d + o_table, 0x7f, table_bytes + 4, s));
+  CallBuf buf;
+  rc = buf.alloc("mnc_mcg_maskdb", layout(WsLayout()));
+  if (rc) return rc;
+  layout(WsLayout(buf.p));
+  int* d_err = d_table + table_bytes / 4;
+  MNC_HIP_TRY(hs.up(d_sp, superpixels, px * 4));
+  MNC_HIP_TRY(hs.up(d_ptr, label_ptr, (nP + 1) * 4));
+  MNC_HIP_TRY(hs.up(d_ids, label_ids, L * 4));
+  MNC_HIP_TRY(hipMemsetAsync(d_table, 0x7f, table_bytes + 4, hs.stream));
   const int grid = std::min(cdiv((long)px, kMcgThreads), 2048);
-  hipLaunchKernelGGL(mcg_extent_kernel, dim3(grid), dim3(kMcgThreads), 0, s, (const int*)d, H, W, (int*)(d + o_table));
+  hipLaunchKernelGGL(mcg_extent_kernel, dim3(grid), dim3(kMcgThreads), 0, hs.stream, d_sp, H, W, d_table);
   MNC_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(mcg_mask_kernel, dim3(n), dim3(kMcgThreads), 0, s, (const int*)d, W, (const int*)(d + o_ptr),
-                     (const int*)(d + o_ids), (const int4*)(d + o_table), max_id, S, (double*)(d + o_boxes),
-                     (unsigned char*)(d + o_masks), (int*)(d + o_err));
+  hipLaunchKernelGGL(mcg_mask_kernel, dim3(n), dim3(kMcgThreads), 0, hs.stream, d_sp, W, d_ptr, d_ids, (const int4*)d_table, max_id, S,
+                     d_boxes, d_masks, d_err);
   MNC_HIP_TRY(hipGetLastError());
   int first_empty = kMcgEmpty;
-  MNC_HIP_TRY(hipMemcpyAsync(boxes, d + o_boxes, nP * 32, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipMemcpyAsync(masks, d + o_masks, nP * S * S, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipMemcpyAsync(&first_empty, d + o_err, 4, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipStreamSynchronize(s));
+  MNC_HIP_TRY(hs.down(boxes, d_boxes, nP * 32));
+  MNC_HIP_TRY(hs.down(masks, d_masks, nP * S * S));
+  MNC_HIP_TRY(hs.down(&first_empty, d_err, 4));
+  MNC_HIP_TRY(hs.sync());
   MNC_REQUIRE(first_empty == kMcgEmpty,
               "mnc_mcg_maskdb: proposal %d covers no pixel (its list is empty or none of its ids occurs in the label map)", first_empty);
   clear_error();

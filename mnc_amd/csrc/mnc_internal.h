@@ -11,8 +11,15 @@
 #include <vector>
 
 #include "../../include/mnc_hip.h"
+#include "ws_layout.h"
 
 namespace mnc {
+
+// A device buffer that only grows (arena_ensure, ctx.hip).
+struct DevArena {
+  void* p = nullptr;
+  size_t cap = 0;
+};
 
 void set_error(const char* fmt, ...);
 void clear_error();
@@ -51,14 +58,10 @@ struct mnc_ctx {
   int profiling = 0;   // 0 off, 1 every launch, 2 only launches with >= 1 GFLOP of algorithmic work (the MFMA kernels)
   std::vector<mnc::ProfRecord> prof;
   std::vector<hipEvent_t> event_pool;
-  // split-K scratch for mnc_fc and friends; grown on demand, never shrunk
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
+  mnc::DevArena scratch;      // split-K scratch for mnc_fc and friends; grown on demand, never shrunk
   void* proposal = nullptr;   // mnc_proposal_state (proposal.hip), created on first use
-  void* vote_ws = nullptr;    // gpu_mask_voting scratch (mv.hip), grown on demand
-  size_t vote_ws_bytes = 0;
-  void* render_ws = nullptr;  // instance descriptors of mnc_render_records (render.hip), grown on demand; in no captured graph
-  size_t render_ws_bytes = 0;
+  mnc::DevArena vote_ws;      // gpu_mask_voting scratch (mv.hip), grown on demand
+  mnc::DevArena render_ws;    // instance descriptors of mnc_render_records (render.hip), grown on demand; in no captured graph
   void* comm = nullptr;       // RCCL communicator state (comm.hip), set by mnc_comm_init
   // Arrival tickets of the K-range reductions that finish INSIDE the launch (gemm.hip, conv_wino4.hip): kTickets counters, zero
   // between launches -- allocated and zeroed with the context, every launch's last arriver of a tile puts its counter back to
@@ -72,7 +75,7 @@ struct mnc_ctx {
   int deferred_splits = 0;
   // Bumped whenever one of the context-owned arenas above (scratch, proposal state, voting scratch) is re-allocated: a captured
   // HIP graph holds their raw addresses, so a graph owner (pipeline.hip) records the value at capture and drops its graph when
-  // the value has moved on.
+  // the value has moved on.  Written by arena_ensure (ctx.hip) and by nothing else.
   unsigned long arena_gen = 0;
   // conventions of the three Caffe layers whose source is unavailable (all zero = oracle/SPEC.md); read by roi.hip's launchers
   mnc_layer_conventions conv = {0, 0, 0, 0, 0, 0, 0.4f, 0};
@@ -128,6 +131,13 @@ inline int fc_lowp_ranges(const mnc_ctx* ctx, int splits, int K, int tiles, bool
 
 namespace mnc {
 
+// Makes `a` hold at least `bytes`, growing it to bytes + slack: waits for `stream` (work in flight may use the old buffer), frees,
+// allocates.  With a context: refuses while a launch sequence is captured, selects the context's device and, when graph_visible,
+// moves ctx->arena_gen -- once per re-allocation, also when the allocation then fails.  Without one (the host-array entry points'
+// workspace) the caller has selected the device.  `who` names the arena in the error message.
+int arena_ensure(DevArena* a, size_t bytes, size_t slack, const char* who, hipStream_t stream, mnc_ctx* ctx = nullptr,
+                 bool graph_visible = false);
+void arena_free(DevArena* a);
 int ensure_scratch(mnc_ctx* ctx, size_t bytes);
 void prof_begin(mnc_ctx* ctx, const char* name, double flops, double bytes);
 void prof_end(mnc_ctx* ctx);
@@ -258,17 +268,32 @@ __device__ __forceinline__ bool slab_last_arriver(unsigned* ticket, int arrivals
   return last;
 }
 
-// Per-device stream + growable device buffer behind the host-pointer entry points (_nms/_mv): the reference
-// cudaMalloc/cudaFree's its scratch on every call (nms_kernel.cu:99-143, mv_kernel.cu:250-347).
-struct LegacyWs {
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  void* buf = nullptr;
-  size_t cap = 0;
+// A device buffer of one call, freed on every way out: for entry points whose need grows with a whole dataset (~0.5 KB per
+// prediction in mnc_sds_best_overlap), too much to keep in an arena.
+struct CallBuf {
+  void* p = nullptr;
+  ~CallBuf() { if (p) (void)hipFree(p); }
+  int alloc(const char* who, size_t bytes);   // ctx.hip
 };
-// Returns the device's workspace with its mutex HELD in *lock (taken before the buffer may be re-allocated: ctypes releases
-// the GIL, so two host threads may be inside _nms / _mv / mnc_mask_voting on one device) and at least `bytes` of buffer.
-int legacy_ws(int device_id, size_t bytes, LegacyWs** out, std::unique_lock<std::mutex>* lock);  // nms.hip
+
+// Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances): the
+// device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
+// mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
+// ctypes releases the GIL, so two host threads may be inside such entry points on one device.
+struct HostScope {
+  std::unique_lock<std::mutex> lock;
+  hipStream_t stream = nullptr;
+  void* buf = nullptr;                        // at least the `bytes` of open(); null when it asked for none
+  int open(int device_id, size_t bytes);      // nms.hip: device check, lock, stream, workspace
+  // asynchronous copies on `stream`; nothing is enqueued for zero bytes
+  hipError_t up(void* d_dst, const void* src, size_t bytes) const {
+    return bytes ? hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+  }
+  hipError_t down(void* dst, const void* d_src, size_t bytes) const {
+    return bytes ? hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+  }
+  hipError_t sync() const { return hipStreamSynchronize(stream); }
+};
 
 // launchers shared between translation units (all asynchronous on `stream`, pointers are device pointers)
 int nms_mask_launch(hipStream_t stream, const float* d_boxes, const int* d_order, int n, int dim, float thr,
@@ -283,7 +308,6 @@ int nms_scan_launch_indirect(hipStream_t stream, const unsigned long long* d_mas
                              float* d_rois = nullptr, int rois_cap = 0);   // d_rois: the ProposalLayer's RoI rows written by the same launch
 void proposal_state_free(void* state);  // proposal.hip
 void comm_free(mnc_ctx* ctx);           // comm.hip
-// out = act(sum of the ksplit partial c8 tensors + bias)  (conv.hip)
 void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,
                       int act);   // gemm.hip: out = act(sum of the K splits' partial sums + bias), shared by the three FC kernels
 bool fc_reduce_launch_sm(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,
@@ -291,6 +315,7 @@ bool fc_reduce_launch_sm(hipStream_t stream, const float* part, const float* bia
 bool fc_reduce_pair_launch_sm(hipStream_t stream, const float* part0, const float* part1, const float* bias0, const float* bias1,
                               float* out0, float* out1, int M, int N, int ldc, int splits, int act, void* sm0, void* sm1, int sm_fmt,
                               long sm_rows, bool* sm_done);   // two products' reductions in one launch (gemm.hip)
+// conv.hip: out = act(sum of the ksplit partial c8 tensors + bias)
 void conv_splitk_reduce_launch(hipStream_t stream, const float* d_part, const float* d_bias, float* d_out, int H, int W,
                                int Cout, int ksplit, int relu);
 // proposal.hip: finishes the sibling classifiers of a head stage in one launch -- the K ranges of [cls_score | seg_cls_score |

@@ -499,8 +499,6 @@ int mv_launch(hipStream_t stream, const float* d_boxes, int box_dim, const float
                         d_out_mask, d_out_box);
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Device scratch of one gpu_mask_voting problem (n boxes, C classes incl. background, S x S masks, keep_cap kept per class).
 struct VoteWs {
   float *boxes, *masks, *scores;        // staging for host inputs (unused when the inputs are already on the device)
@@ -511,32 +509,30 @@ struct VoteWs {
   float* records;                       // [Rmax][6 + S*S]
 };
 
-static size_t vote_ws_layout(char* base, int n, int C, int S, int keep_cap, VoteWs* w) {
-  const int B = C - 1, cb = cdiv(n, 64), Rmax = B * keep_cap;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base + off; off += align256(bytes); return p; };
-  w->boxes = (float*)take((size_t)n * 16);
-  w->masks = (float*)take((size_t)n * S * S * 4);
-  w->scores = (float*)take((size_t)n * C * 4);
-  w->order = (int*)take((size_t)B * n * 4);
-  w->bits = (unsigned long long*)take((size_t)B * n * cb * 8);
-  w->keep = (int*)take((size_t)B * n * 4);
-  w->num = (int*)take((size_t)B * 4);
-  w->pool_box = (int*)take((size_t)Rmax * 4);
-  w->pool_cls = (int*)take((size_t)Rmax * 4);
-  w->pool_score = (float*)take((size_t)Rmax * 4);
-  w->rows = (int*)take((size_t)Rmax * 8);
-  w->rscore = (float*)take((size_t)Rmax * 4);
-  w->counts = (int*)take((size_t)C * 4);
-  w->cinds = (int*)take((size_t)Rmax * n * 4);
-  w->cw = (float*)take((size_t)Rmax * n * 4);
-  w->cbegin = (int*)take((size_t)Rmax * 4);
-  w->cend = (int*)take((size_t)Rmax * 4);
-  w->bounds = (int*)take((size_t)Rmax * 16);
-  w->omask = (float*)take((size_t)Rmax * S * S * 4);
-  w->obox = (int*)take((size_t)Rmax * 16);
-  w->records = (float*)take((size_t)Rmax * (6 + S * S) * 4);
-  return off;
+static size_t vote_ws_layout(WsLayout l, int n, int C, int S, int keep_cap, VoteWs* w) {
+  const size_t B = C - 1, cb = cdiv(n, 64), Rmax = B * keep_cap, N = n;
+  w->boxes = l.take<float>(N * 4);
+  w->masks = l.take<float>(N * S * S);
+  w->scores = l.take<float>(N * C);
+  w->order = l.take<int>(B * N);
+  w->bits = l.take<unsigned long long>(B * N * cb);
+  w->keep = l.take<int>(B * N);
+  w->num = l.take<int>(B);
+  w->pool_box = l.take<int>(Rmax);
+  w->pool_cls = l.take<int>(Rmax);
+  w->pool_score = l.take<float>(Rmax);
+  w->rows = l.take<int>(Rmax * 2);
+  w->rscore = l.take<float>(Rmax);
+  w->counts = l.take<int>(C);
+  w->cinds = l.take<int>(Rmax * N);
+  w->cw = l.take<float>(Rmax * N);
+  w->cbegin = l.take<int>(Rmax);
+  w->cend = l.take<int>(Rmax);
+  w->bounds = l.take<int>(Rmax * 4);
+  w->omask = l.take<float>(Rmax * S * S);
+  w->obox = l.take<int>(Rmax * 4);
+  w->records = l.take<float>(Rmax * (6 + S * S));
+  return l.bytes();
 }
 
 // gpu_mask_voting (lib/transform/mask_transform.py:213-286 + lib/nms/mv_kernel.cu) as ONE asynchronous launch sequence on
@@ -641,24 +637,54 @@ using namespace mnc;
 
 // per-context voting scratch (mnc_ctx::vote_ws), grown on demand
 static int ctx_vote_ws(mnc_ctx* ctx, int n, int C, int S, int keep_cap, VoteWs* w) {
-  const size_t need = vote_ws_layout(nullptr, n, C, S, keep_cap, w);
-  if (need > ctx->vote_ws_bytes) {
-    MNC_NO_CAPTURE(ctx, "voting scratch growth");
-    MNC_HIP_TRY(hipSetDevice(ctx->device));
-    MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->vote_ws) MNC_HIP_TRY(hipFree(ctx->vote_ws));
-    ctx->vote_ws = nullptr;
-    ctx->vote_ws_bytes = 0;
-    ++ctx->arena_gen;                  // a captured graph that holds the old address must not be replayed (pipeline.hip)
-    hipError_t e = hipMalloc(&ctx->vote_ws, need + (need >> 2));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("voting scratch: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-      return MNC_ERR_NOMEM;
-    }
-    ctx->vote_ws_bytes = need + (need >> 2);
+  const size_t need = vote_ws_layout(WsLayout(), n, C, S, keep_cap, w);
+  const int rc = arena_ensure(&ctx->vote_ws, need, need >> 2, "voting scratch", ctx->stream, ctx, true);
+  if (rc) return rc;
+  vote_ws_layout(WsLayout(ctx->vote_ws.p), n, C, S, keep_cap, w);
+  return MNC_OK;
+}
+
+// mnc_mask_voting (mode MNC_VOTE_MV: `order` may be given) and mnc_mask_voting_image (MNC_VOTE_IMAGE) behind their own argument
+// checks: inputs up, the asynchronous device sequence, records down.
+static int vote_host(int mode, const float* boxes, const float* masks, const float* scores, const int* order, int n,
+                     int C, int S, int max_per_image, float nms_thresh, float iou_thresh, double binarize_thresh, int H, int W,
+                     float* out_mask, int* out_box, float* out_score, int* class_count, int* result_num, int device_id) {
+  const int B = C - 1, keep_cap = max_per_image < n ? max_per_image : n;
+  VoteWs ws;
+  HostScope hs;
+  int rc = hs.open(device_id, vote_ws_layout(WsLayout(), n, C, S, keep_cap, &ws));
+  if (rc) return rc;
+  vote_ws_layout(WsLayout(hs.buf), n, C, S, keep_cap, &ws);
+  MNC_HIP_TRY(hs.up(ws.boxes, boxes, (size_t)n * 16));
+  MNC_HIP_TRY(hs.up(ws.scores, scores, (size_t)n * C * 4));
+  MNC_HIP_TRY(hs.up(ws.masks, masks, (size_t)n * S * S * 4));
+  std::vector<int> h_order;
+  if (!order && n > kMaxOrderDevice) {
+    host_order(scores, n, C, &h_order);
+    order = h_order.data();
   }
-  vote_ws_layout((char*)ctx->vote_ws, n, C, S, keep_cap, w);
+  if (order) MNC_HIP_TRY(hs.up(ws.order, order, (size_t)B * n * 4));
+  rc = vote_async(hs.stream, ws, ws.boxes, ws.masks, ws.scores, order != nullptr, n, C, S, max_per_image, nms_thresh, iou_thresh, H,
+                  W, ws.records, B * keep_cap, ws.counts, mode, binarize_thresh);
+  if (rc) return rc;
+  rc = vote_fetch(hs.stream, ws.records, ws.counts, B * keep_cap, C, S, max_per_image, out_mask, out_box, out_score, class_count,
+                  result_num);
+  if (rc) return rc;
+  clear_error();
+  return MNC_OK;
+}
+
+// The checks and the empty result the two host entry points share (n == 0: that result is all there is).
+static int vote_host_begin(const char* who, const float* boxes, const float* masks, const float* scores, int n, int C, int S,
+                           int max_per_image, int H, int W, float* out_mask, int* out_box, float* out_score, int* class_count,
+                           int* result_num) {
+  MNC_REQUIRE(result_num && class_count, "%s: null output pointer", who);
+  const int rc = vote_check_args(who, n, C, S, max_per_image, H, W);
+  if (rc) return rc;
+  *result_num = 0;
+  for (int c = 0; c < C - 1; ++c) class_count[c] = 0;
+  MNC_REQUIRE(n == 0 || (boxes && masks && scores && out_mask && out_box && out_score), "%s: null pointer", who);
+  clear_error();
   return MNC_OK;
 }
 
@@ -682,87 +708,54 @@ int mnc_mv(const float* all_boxes, const float* all_masks, int all_boxes_num, co
     MNC_REQUIRE(candidate_inds[i] >= 0 && candidate_inds[i] < all_boxes_num, "mnc_mv: candidate_inds[%d]=%d out of range",
                 i, candidate_inds[i]);
   const int S = mask_size, R = result_num;
-  const size_t b_boxes = align256((size_t)all_boxes_num * box_dim * 4), b_masks = align256((size_t)all_boxes_num * S * S * 4);
-  const size_t b_inds = align256((size_t)candidate_num * 4), b_wts = b_inds, b_starts = align256((size_t)R * 8);
-  const size_t b_bounds = align256((size_t)R * 16), b_omask = align256((size_t)R * S * S * 4), b_obox = align256((size_t)R * 16);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int rc = legacy_ws(device_id, b_boxes + b_masks + b_inds + b_wts + b_starts + b_bounds + b_omask + b_obox, &w, &lock);
+  const size_t nb = all_boxes_num, nc = candidate_num;
+  float *d_boxes, *d_masks, *d_wts, *d_omask; int *d_inds, *d_starts, *d_bounds, *d_obox;
+  auto layout = [&](WsLayout l) {
+    d_boxes = l.take<float>(nb * box_dim);
+    d_masks = l.take<float>(nb * S * S);
+    d_inds = l.take<int>(nc);
+    d_wts = l.take<float>(nc);
+    d_starts = l.take<int>(2 * (size_t)R);    // begins, then ends
+    d_bounds = l.take<int>(4 * (size_t)R);
+    d_omask = l.take<float>((size_t)R * S * S);
+    d_obox = l.take<int>(4 * (size_t)R);
+    return l.bytes();
+  };
+  HostScope hs;
+  int rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
-  char* p = (char*)w->buf;
-  float* d_boxes = (float*)p; p += b_boxes;
-  float* d_masks = (float*)p; p += b_masks;
-  int* d_inds = (int*)p; p += b_inds;
-  float* d_wts = (float*)p; p += b_wts;
-  int* d_starts = (int*)p; p += b_starts;
-  int* d_bounds = (int*)p; p += b_bounds;
-  float* d_omask = (float*)p; p += b_omask;
-  int* d_obox = (int*)p;
-  hipStream_t s = w->stream;
-  if (all_boxes_num) {
-    MNC_HIP_TRY(hipMemcpyAsync(d_boxes, all_boxes, (size_t)all_boxes_num * box_dim * 4, hipMemcpyHostToDevice, s));
-    MNC_HIP_TRY(hipMemcpyAsync(d_masks, all_masks, (size_t)all_boxes_num * S * S * 4, hipMemcpyHostToDevice, s));
-  }
-  if (candidate_num) {
-    MNC_HIP_TRY(hipMemcpyAsync(d_inds, candidate_inds, (size_t)candidate_num * 4, hipMemcpyHostToDevice, s));
-    MNC_HIP_TRY(hipMemcpyAsync(d_wts, candidate_weights, (size_t)candidate_num * 4, hipMemcpyHostToDevice, s));
-  }
+  layout(WsLayout(hs.buf));
+  MNC_HIP_TRY(hs.up(d_boxes, all_boxes, nb * box_dim * 4));
+  MNC_HIP_TRY(hs.up(d_masks, all_masks, nb * S * S * 4));
+  MNC_HIP_TRY(hs.up(d_inds, candidate_inds, nc * 4));
+  MNC_HIP_TRY(hs.up(d_wts, candidate_weights, nc * 4));
   std::vector<int> h_begins(R);              // candidate_start holds END offsets (gpu_mv.pyx / mv_kernel.cu:100)
   for (int r = 0; r < R; ++r) h_begins[r] = r ? candidate_start[r - 1] : 0;
-  MNC_HIP_TRY(hipMemcpyAsync(d_starts, h_begins.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(d_starts + R, candidate_start, (size_t)R * 4, hipMemcpyHostToDevice, s));
-  mv_launch(s, d_boxes, box_dim, d_masks, S, d_inds, d_starts, d_starts + R, d_wts, image_height, image_width, R, d_bounds,
+  MNC_HIP_TRY(hs.up(d_starts, h_begins.data(), (size_t)R * 4));
+  MNC_HIP_TRY(hs.up(d_starts + R, candidate_start, (size_t)R * 4));
+  mv_launch(hs.stream, d_boxes, box_dim, d_masks, S, d_inds, d_starts, d_starts + R, d_wts, image_height, image_width, R, d_bounds,
             d_omask, d_obox);
   MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hipMemcpyAsync(out_mask, d_omask, (size_t)R * S * S * 4, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipMemcpyAsync(out_box, d_obox, (size_t)R * 16, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipStreamSynchronize(s));
+  MNC_HIP_TRY(hs.down(out_mask, d_omask, (size_t)R * S * S * 4));
+  MNC_HIP_TRY(hs.down(out_box, d_obox, (size_t)R * 16));
+  MNC_HIP_TRY(hs.sync());
   clear_error();
   return MNC_OK;
 }
 
-// gpu_mask_voting in one call on HOST arrays (see include/mnc_hip.h): inputs up, the asynchronous device sequence, records down.
+// gpu_mask_voting in one call on HOST arrays (see include/mnc_hip.h)
 int mnc_mask_voting(const float* boxes, const float* masks, const float* scores, const int* order, int n, int num_classes,
                     int mask_size, int max_per_image, float nms_thresh, float iou_thresh, int image_height,
                     int image_width, float* out_mask, int* out_box, float* out_score, int* class_count, int* result_num,
                     int device_id) {
-  MNC_REQUIRE(result_num && class_count, "mnc_mask_voting: null output pointer");
-  int rc = vote_check_args("mnc_mask_voting", n, num_classes, mask_size, max_per_image, image_height, image_width);
-  if (rc) return rc;
-  const int B = num_classes - 1, S = mask_size, C = num_classes;
-  *result_num = 0;
-  for (int c = 0; c < B; ++c) class_count[c] = 0;
-  if (n == 0) { clear_error(); return MNC_OK; }
-  MNC_REQUIRE(boxes && masks && scores && out_mask && out_box && out_score, "mnc_mask_voting: null pointer");
+  const int rc = vote_host_begin("mnc_mask_voting", boxes, masks, scores, n, num_classes, mask_size, max_per_image, image_height,
+                                 image_width, out_mask, out_box, out_score, class_count, result_num);
+  if (rc || n == 0) return rc;
   if (order)
-    for (long i = 0; i < (long)B * n; ++i)
+    for (long i = 0; i < (long)(num_classes - 1) * n; ++i)
       MNC_REQUIRE(order[i] >= 0 && order[i] < n, "mnc_mask_voting: order[%ld]=%d out of range", i, order[i]);
-  const int keep_cap = max_per_image < n ? max_per_image : n;
-  VoteWs ws;
-  const size_t need = vote_ws_layout(nullptr, n, C, S, keep_cap, &ws);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  rc = legacy_ws(device_id, need, &w, &lock);
-  if (rc) return rc;
-  vote_ws_layout((char*)w->buf, n, C, S, keep_cap, &ws);
-  hipStream_t s = w->stream;
-  MNC_HIP_TRY(hipMemcpyAsync(ws.boxes, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(ws.scores, scores, (size_t)n * C * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(ws.masks, masks, (size_t)n * S * S * 4, hipMemcpyHostToDevice, s));
-  std::vector<int> h_order;
-  if (!order && n > kMaxOrderDevice) {
-    host_order(scores, n, C, &h_order);
-    order = h_order.data();
-  }
-  if (order) MNC_HIP_TRY(hipMemcpyAsync(ws.order, order, (size_t)B * n * 4, hipMemcpyHostToDevice, s));
-  rc = vote_async(s, ws, ws.boxes, ws.masks, ws.scores, order != nullptr, n, C, S, max_per_image, nms_thresh, iou_thresh,
-                  image_height, image_width, ws.records, B * keep_cap, ws.counts);
-  if (rc) return rc;
-  rc = vote_fetch(s, ws.records, ws.counts, B * keep_cap, C, S, max_per_image, out_mask, out_box, out_score, class_count,
-                  result_num);
-  if (rc) return rc;
-  clear_error();
-  return MNC_OK;
+  return vote_host(MNC_VOTE_MV, boxes, masks, scores, order, n, num_classes, mask_size, max_per_image, nms_thresh, iou_thresh, 0.4,
+                   image_height, image_width, out_mask, out_box, out_score, class_count, result_num, device_id);
 }
 
 // cpu_mask_voting in one call on HOST arrays (see include/mnc_hip.h): mnc_mask_voting's sequence with the image-space rule.
@@ -770,45 +763,17 @@ int mnc_mask_voting_image(const float* boxes, const float* masks, const float* s
                           int max_per_image, float nms_thresh, float iou_thresh, double binarize_thresh, int image_height,
                           int image_width, float* out_mask, int* out_box, float* out_score, int* class_count, int* result_num,
                           int device_id) {
-  MNC_REQUIRE(result_num && class_count, "mnc_mask_voting_image: null output pointer");
-  int rc = vote_check_args("mnc_mask_voting_image", n, num_classes, mask_size, max_per_image, image_height, image_width);
-  if (rc) return rc;
-  const int B = num_classes - 1, S = mask_size, C = num_classes;
-  *result_num = 0;
-  for (int c = 0; c < B; ++c) class_count[c] = 0;
-  if (n == 0) { clear_error(); return MNC_OK; }
-  MNC_REQUIRE(boxes && masks && scores && out_mask && out_box && out_score, "mnc_mask_voting_image: null pointer");
+  const int rc = vote_host_begin("mnc_mask_voting_image", boxes, masks, scores, n, num_classes, mask_size, max_per_image,
+                                 image_height, image_width, out_mask, out_box, out_score, class_count, result_num);
+  if (rc || n == 0) return rc;
   for (int i = 0; i < n; ++i) {
     const float* b = boxes + (size_t)i * 4;
     MNC_REQUIRE(rintf(b[0]) <= rintf(b[2]) && rintf(b[1]) <= rintf(b[3]),
                 "mnc_mask_voting_image: box %d (%g, %g, %g, %g) is empty once rounded (cv2.resize would raise)", i, b[0], b[1],
                 b[2], b[3]);
   }
-  const int keep_cap = max_per_image < n ? max_per_image : n;
-  VoteWs ws;
-  const size_t need = vote_ws_layout(nullptr, n, C, S, keep_cap, &ws);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  rc = legacy_ws(device_id, need, &w, &lock);
-  if (rc) return rc;
-  vote_ws_layout((char*)w->buf, n, C, S, keep_cap, &ws);
-  hipStream_t s = w->stream;
-  MNC_HIP_TRY(hipMemcpyAsync(ws.boxes, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(ws.scores, scores, (size_t)n * C * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(ws.masks, masks, (size_t)n * S * S * 4, hipMemcpyHostToDevice, s));
-  std::vector<int> h_order;
-  if (n > kMaxOrderDevice) {
-    host_order(scores, n, C, &h_order);
-    MNC_HIP_TRY(hipMemcpyAsync(ws.order, h_order.data(), (size_t)B * n * 4, hipMemcpyHostToDevice, s));
-  }
-  rc = vote_async(s, ws, ws.boxes, ws.masks, ws.scores, n > kMaxOrderDevice, n, C, S, max_per_image, nms_thresh, iou_thresh,
-                  image_height, image_width, ws.records, B * keep_cap, ws.counts, MNC_VOTE_IMAGE, binarize_thresh);
-  if (rc) return rc;
-  rc = vote_fetch(s, ws.records, ws.counts, B * keep_cap, C, S, max_per_image, out_mask, out_box, out_score, class_count,
-                  result_num);
-  if (rc) return rc;
-  clear_error();
-  return MNC_OK;
+  return vote_host(MNC_VOTE_IMAGE, boxes, masks, scores, nullptr, n, num_classes, mask_size, max_per_image, nms_thresh, iou_thresh,
+                   binarize_thresh, image_height, image_width, out_mask, out_box, out_score, class_count, result_num, device_id);
 }
 
 // The same with inputs AND outputs on the device, asynchronous on the context's stream -- what the whole-image path uses.

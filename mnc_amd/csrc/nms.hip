@@ -256,37 +256,21 @@ int nms_scan_launch_indirect(hipStream_t stream, const u64* d_mask, const int* d
 }
 
 // ---- per-device workspace for the host-pointer entry points (b1/b2 allocate-per-call in the reference) ----------
-static LegacyWs g_ws[16];
+static struct { std::mutex mu; hipStream_t stream = nullptr; DevArena buf; } g_ws[16];
 
-int legacy_ws(int device_id, size_t bytes, LegacyWs** out, std::unique_lock<std::mutex>* lock) {
+int HostScope::open(int device_id, size_t bytes) {
   int ndev = 0;
   MNC_HIP_TRY(hipGetDeviceCount(&ndev));
   MNC_REQUIRE(device_id >= 0 && device_id < ndev && device_id < 16, "device %d out of range (have %d)", device_id, ndev);
   MNC_HIP_TRY(hipSetDevice(device_id));
-  LegacyWs* w = &g_ws[device_id];
-  *lock = std::unique_lock<std::mutex>(w->mu);        // before anything is created, grown or freed
-  if (!w->stream) MNC_HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-  if (bytes > w->cap) {
-    if (w->buf) {
-      MNC_HIP_TRY(hipStreamSynchronize(w->stream));
-      MNC_HIP_TRY(hipFree(w->buf));
-    }
-    w->buf = nullptr;
-    w->cap = 0;
-    size_t want = bytes + (bytes >> 1) + 4096;
-    hipError_t e = hipMalloc(&w->buf, want);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-      return MNC_ERR_NOMEM;
-    }
-    w->cap = want;
-  }
-  *out = w;
-  return MNC_OK;
+  auto& w = g_ws[device_id];
+  lock = std::unique_lock<std::mutex>(w.mu);          // before anything is created, grown or freed
+  if (!w.stream) MNC_HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+  stream = w.stream;
+  const int rc = arena_ensure(&w.buf, bytes, (bytes >> 1) + 4096, "host-entry workspace", stream);
+  buf = w.buf.p;
+  return rc;
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // boxes_host [n][dim]; order_host: nullptr (boxes already sorted, batch == 1) or [batch][n] indices into boxes.
 // keep_out [batch][n] positions in each item's order; num_out [batch].  mask_out (batch == 1 only): row-major [n][cb].
@@ -301,37 +285,35 @@ static int nms_host_impl(int* keep_out, int* num_out, u64* mask_out, const float
       MNC_REQUIRE(order_host[i] >= 0 && order_host[i] < n, "mnc_nms_batched: order[%ld]=%d out of range", i, order_host[i]);
   const int cb = cdiv(n, 64);
   if (max_keep < 0 || max_keep > n) max_keep = n;
-  const size_t box_b = align256((size_t)n * dim * 4), ord_b = order_host ? align256((size_t)batch * n * 4) : 0;
-  const size_t mask_b = align256((size_t)batch * n * cb * 8), keep_b = align256((size_t)batch * n * 4);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int rc = legacy_ws(device_id, box_b + ord_b + mask_b + keep_b + align256((size_t)batch * 4), &w, &lock);
+  float* d_boxes; int *d_order, *d_keep, *d_num; u64* d_mask;
+  auto layout = [&](WsLayout l) {
+    d_boxes = l.take<float>((size_t)n * dim);
+    d_order = order_host ? l.take<int>((size_t)batch * n) : nullptr;
+    d_mask = l.take<u64>((size_t)batch * n * cb);
+    d_keep = l.take<int>((size_t)batch * n);
+    d_num = l.take<int>(batch);
+    return l.bytes();
+  };
+  HostScope hs;
+  int rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
-  char* base = (char*)w->buf;
-  float* d_boxes = (float*)base;
-  int* d_order = order_host ? (int*)(base + box_b) : nullptr;
-  u64* d_mask = (u64*)(base + box_b + ord_b);
-  int* d_keep = (int*)(base + box_b + ord_b + mask_b);
-  int* d_num = (int*)(base + box_b + ord_b + mask_b + keep_b);
-  MNC_HIP_TRY(hipMemcpyAsync(d_boxes, boxes_host, (size_t)n * dim * 4, hipMemcpyHostToDevice, w->stream));
-  if (order_host) MNC_HIP_TRY(hipMemcpyAsync(d_order, order_host, (size_t)batch * n * 4, hipMemcpyHostToDevice, w->stream));
+  layout(WsLayout(hs.buf));
+  MNC_HIP_TRY(hs.up(d_boxes, boxes_host, (size_t)n * dim * 4));
+  if (order_host) MNC_HIP_TRY(hs.up(d_order, order_host, (size_t)batch * n * 4));
   const bool device_scan = cb <= kMaxScanBlocks && !mask_out;
-  if (!device_scan) MNC_HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)batch * n * cb * 8, w->stream));
-  nms_mask_launch(w->stream, d_boxes, d_order, n, dim, thr, d_mask, batch);
+  if (!device_scan) MNC_HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)batch * n * cb * 8, hs.stream));
+  nms_mask_launch(hs.stream, d_boxes, d_order, n, dim, thr, d_mask, batch);
   MNC_HIP_TRY(hipGetLastError());
   if (device_scan) {
-    nms_scan_launch(w->stream, d_mask, n, max_keep, d_keep, d_num, batch);
+    nms_scan_launch(hs.stream, d_mask, n, max_keep, d_keep, d_num, batch);
     MNC_HIP_TRY(hipGetLastError());
-    MNC_HIP_TRY(hipMemcpyAsync(num_out, d_num, (size_t)batch * 4, hipMemcpyDeviceToHost, w->stream));
-    if (batch > 1) {  // one copy of the whole (small) keep table instead of a second dependent round trip
-      MNC_HIP_TRY(hipMemcpyAsync(keep_out, d_keep, (size_t)batch * n * 4, hipMemcpyDeviceToHost, w->stream));
-      MNC_HIP_TRY(hipStreamSynchronize(w->stream));
-    } else {
-      MNC_HIP_TRY(hipStreamSynchronize(w->stream));
-      if (num_out[0] > 0) {
-        MNC_HIP_TRY(hipMemcpyAsync(keep_out, d_keep, (size_t)num_out[0] * 4, hipMemcpyDeviceToHost, w->stream));
-        MNC_HIP_TRY(hipStreamSynchronize(w->stream));
-      }
+    MNC_HIP_TRY(hs.down(num_out, d_num, (size_t)batch * 4));
+    // batch > 1: one copy of the whole (small) keep table instead of a second dependent round trip
+    if (batch > 1) MNC_HIP_TRY(hs.down(keep_out, d_keep, (size_t)batch * n * 4));
+    MNC_HIP_TRY(hs.sync());
+    if (batch == 1 && num_out[0] > 0) {
+      MNC_HIP_TRY(hs.down(keep_out, d_keep, (size_t)num_out[0] * 4));
+      MNC_HIP_TRY(hs.sync());
     }
     clear_error();
     return MNC_OK;
@@ -340,8 +322,8 @@ static int nms_host_impl(int* keep_out, int* num_out, u64* mask_out, const float
   // (nms_kernel.cu:118-140).  The device layout is column-block major; rows are re-assembled here.
   std::vector<u64> hm((size_t)n * cb);
   for (int b = 0; b < batch; ++b) {
-    MNC_HIP_TRY(hipMemcpyAsync(hm.data(), d_mask + (size_t)b * n * cb, (size_t)n * cb * 8, hipMemcpyDeviceToHost, w->stream));
-    MNC_HIP_TRY(hipStreamSynchronize(w->stream));
+    MNC_HIP_TRY(hs.down(hm.data(), d_mask + (size_t)b * n * cb, (size_t)n * cb * 8));
+    MNC_HIP_TRY(hs.sync());
     if (mask_out) {
       for (int r = 0; r < n; ++r)
         for (int c = 0; c < cb; ++c) mask_out[(size_t)r * cb + c] = hm[(size_t)c * n + r];

@@ -385,15 +385,27 @@ struct ProposalWs {
   int cap_n = 0, cap_k = 0;
 };
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+// N anchors decoded, the first topn of them ranked and suppressed, nruns sorted runs of kRun keys
+static size_t proposal_ws_layout(WsLayout l, size_t N, size_t topn, size_t nruns, ProposalWs* w) {
+  w->boxes = l.take<float>(N * 4);
+  w->keys = l.take<u64>(N);
+  w->scores = l.take<float>(N);
+  w->order = l.take<int>(topn);
+  w->sorted_scores = l.take<float>(topn);
+  w->n_cand = l.take<int>(1);
+  w->mask = l.take<u64>(topn * cdiv(topn, 64));
+  w->keep = l.take<int>(topn);
+  w->num = l.take<int>(1);
+  w->runs = l.take<u64>(nruns * kRun);
+  return l.bytes();
+}
 
 }  // namespace mnc
 
 using namespace mnc;
 
 struct mnc_proposal_state {
-  void* buf = nullptr;
-  size_t bytes = 0;
+  DevArena buf;
   ProposalWs ws;
   int last_n = 0, last_topn = 0;
 };
@@ -405,7 +417,7 @@ int* proposal_count_ptr(mnc_ctx* ctx) {
 }
 void proposal_state_free(void* state) {
   mnc_proposal_state* st = (mnc_proposal_state*)state;
-  if (st->buf) (void)hipFree(st->buf);
+  arena_free(&st->buf);
   delete st;
 }
 }  // namespace mnc
@@ -441,35 +453,14 @@ int mnc_proposal(mnc_ctx* ctx, const float* d_cls_prob, const float* d_bbox_pred
   int topn = pre_nms_topn > 0 ? pre_nms_topn : N;
   if (topn > N) topn = N;
   MNC_REQUIRE(topn <= kSortCap, "mnc_proposal: pre_nms_topN=%d exceeds the LDS sort capacity %d", topn, kSortCap);
-  const int cb = cdiv(topn, 64);
   mnc_proposal_state* st = state_of(ctx);
   const int nruns = cdiv(N, kRun);
   const bool wide_topk = nruns <= kMaxRuns && !tune(ctx, T_TOPK_SINGLE_WG, 0);
-  const size_t need = a256((size_t)N * 16) + a256((size_t)N * 8) + a256((size_t)N * 4) + a256((size_t)topn * 4) * 2 + 256 +
-                      a256((size_t)topn * cb * 8) + a256((size_t)topn * 4) + 256 + a256((size_t)nruns * kRun * 8);
-  if (need > st->bytes) {
-    MNC_NO_CAPTURE(ctx, "proposal state growth");
-    MNC_HIP_TRY(hipSetDevice(ctx->device));
-    MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (st->buf) MNC_HIP_TRY(hipFree(st->buf));
-    st->buf = nullptr; st->bytes = 0;
-    ++ctx->arena_gen;                  // a captured graph that holds the old address must not be replayed (pipeline.hip)
-    hipError_t e = hipMalloc(&st->buf, need + (need >> 2));
-    if (e != hipSuccess) { set_error("mnc_proposal: hipMalloc(%zu) failed", need); return MNC_ERR_NOMEM; }
-    st->bytes = need + (need >> 2);
-  }
-  char* p = (char*)st->buf;
-  ProposalWs& w = st->ws;
-  w.boxes = (float*)p; p += a256((size_t)N * 16);
-  w.keys = (u64*)p; p += a256((size_t)N * 8);
-  w.scores = (float*)p; p += a256((size_t)N * 4);
-  w.order = (int*)p; p += a256((size_t)topn * 4);
-  w.sorted_scores = (float*)p; p += a256((size_t)topn * 4);
-  w.n_cand = (int*)p; p += 256;
-  w.mask = (u64*)p; p += a256((size_t)topn * cb * 8);
-  w.keep = (int*)p; p += a256((size_t)topn * 4);
-  w.num = (int*)p; p += 256;
-  w.runs = (u64*)p;
+  ProposalWs sized, &w = st->ws;
+  const size_t need = proposal_ws_layout(WsLayout(), N, topn, nruns, &sized);
+  const int rc = arena_ensure(&st->buf, need, need >> 2, "proposal state", ctx->stream, ctx, true);
+  if (rc) return rc;
+  proposal_ws_layout(WsLayout(st->buf.p), N, topn, nruns, &w);
   st->last_n = N; st->last_topn = topn;
 
   Anchors anc;
@@ -529,7 +520,7 @@ int mnc_proposal(mnc_ctx* ctx, const float* d_cls_prob, const float* d_bbox_pred
 int mnc_proposal_count(mnc_ctx* ctx, int* num_rois_host) {
   MNC_REQUIRE(ctx && num_rois_host, "mnc_proposal_count: null pointer");
   mnc_proposal_state* st = (mnc_proposal_state*)ctx->proposal;
-  MNC_REQUIRE(st && st->buf, "mnc_proposal_count: mnc_proposal has not run on this context");
+  MNC_REQUIRE(st && st->buf.p, "mnc_proposal_count: mnc_proposal has not run on this context");
   MNC_NO_CAPTURE(ctx, "mnc_proposal_count");
   MNC_HIP_TRY(hipMemcpyAsync(num_rois_host, st->ws.num, 4, hipMemcpyDeviceToHost, ctx->stream));
   MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -540,7 +531,7 @@ int mnc_proposal_count(mnc_ctx* ctx, int* num_rois_host) {
 int mnc_proposal_count_ptr(mnc_ctx* ctx, void** d_count) {
   MNC_REQUIRE(ctx && d_count, "mnc_proposal_count_ptr: null pointer");
   mnc_proposal_state* st = (mnc_proposal_state*)ctx->proposal;
-  MNC_REQUIRE(st && st->buf, "mnc_proposal_count_ptr: mnc_proposal has not run on this context");
+  MNC_REQUIRE(st && st->buf.p, "mnc_proposal_count_ptr: mnc_proposal has not run on this context");
   *d_count = st->ws.num;
   clear_error();
   return MNC_OK;
@@ -549,7 +540,7 @@ int mnc_proposal_count_ptr(mnc_ctx* ctx, void** d_count) {
 int mnc_proposal_candidates(mnc_ctx* ctx, float* boxes_host, float* scores_host, int capacity, int* n_host) {
   MNC_REQUIRE(ctx && n_host, "mnc_proposal_candidates: null pointer");
   mnc_proposal_state* st = (mnc_proposal_state*)ctx->proposal;
-  MNC_REQUIRE(st && st->buf, "mnc_proposal_candidates: mnc_proposal has not run on this context");
+  MNC_REQUIRE(st && st->buf.p, "mnc_proposal_candidates: mnc_proposal has not run on this context");
   MNC_NO_CAPTURE(ctx, "mnc_proposal_candidates");
   int n = 0;
   MNC_HIP_TRY(hipMemcpyAsync(&n, st->ws.n_cand, 4, hipMemcpyDeviceToHost, ctx->stream));

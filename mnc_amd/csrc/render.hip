@@ -208,8 +208,6 @@ __global__ __launch_bounds__(kRenderThreads) void render_paint_kernel(
 
 namespace {
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 void paint_launch(hipStream_t s, const RenderDesc* d_descs, const int* d_n, int n_fixed, const float* d_masks, long mask_stride,
                   int S, double binarize_thresh, int H, int W, const unsigned char* d_bgr, float alpha, int* d_inst, int* d_cls,
                   unsigned char* d_inst_rgb, unsigned char* d_cls_rgb, unsigned char* d_overlay_rgb) {
@@ -222,24 +220,14 @@ void paint_launch(hipStream_t s, const RenderDesc* d_descs, const int* d_n, int 
 // per-context descriptor scratch (mnc_ctx::render_ws): [kept count: 256 B | record_cap descriptors].  No captured graph holds its
 // address (rendering is never part of one), so growing it does not touch mnc_ctx::arena_gen.
 int ctx_render_ws(mnc_ctx* ctx, int record_cap, int** d_kept, RenderDesc** d_descs) {
-  const size_t need = 256 + up256((size_t)(record_cap > 0 ? record_cap : 1) * sizeof(RenderDesc));
-  if (need > ctx->render_ws_bytes) {
-    MNC_NO_CAPTURE(ctx, "render scratch growth");
-    MNC_HIP_TRY(hipSetDevice(ctx->device));
-    MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->render_ws) MNC_HIP_TRY(hipFree(ctx->render_ws));
-    ctx->render_ws = nullptr;
-    ctx->render_ws_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->render_ws, need);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("render scratch: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-      return MNC_ERR_NOMEM;
-    }
-    ctx->render_ws_bytes = need;
-  }
-  *d_kept = (int*)ctx->render_ws;
-  *d_descs = (RenderDesc*)((char*)ctx->render_ws + 256);
+  auto layout = [&](WsLayout l) {
+    *d_kept = l.take<int>(1);
+    *d_descs = l.take<RenderDesc>(record_cap > 0 ? record_cap : 1);
+    return l.bytes();
+  };
+  const int rc = arena_ensure(&ctx->render_ws, layout(WsLayout()), 0, "render scratch", ctx->stream, ctx);
+  if (rc) return rc;
+  layout(WsLayout(ctx->render_ws.p));
   return MNC_OK;
 }
 
@@ -281,24 +269,26 @@ int mnc_render_instances(const double* boxes, const float* masks, const int* cla
   }
   if (!inst_img && !cls_img) { clear_error(); return MNC_OK; }
   const size_t px = (size_t)H * W;
-  const size_t o_masks = up256((size_t)n * sizeof(RenderDesc)), o_inst = o_masks + up256((size_t)n * S * S * 4),
-               o_cls = o_inst + up256(px * 4), total = o_cls + up256(px * 4);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int rc = legacy_ws(device_id, total, &w, &lock);
+  RenderDesc* d_descs; float* d_masks; int *d_inst, *d_cls;
+  auto layout = [&](WsLayout l) {
+    d_descs = l.take<RenderDesc>(n);
+    d_masks = l.take<float>((size_t)n * S * S);
+    d_inst = l.take<int>(px);
+    d_cls = l.take<int>(px);
+    return l.bytes();
+  };
+  HostScope hs;
+  int rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
-  char* d = (char*)w->buf;
-  hipStream_t s = w->stream;
-  if (n) {
-    MNC_HIP_TRY(hipMemcpyAsync(d, descs.data(), (size_t)n * sizeof(RenderDesc), hipMemcpyHostToDevice, s));
-    MNC_HIP_TRY(hipMemcpyAsync(d + o_masks, masks, (size_t)n * S * S * 4, hipMemcpyHostToDevice, s));
-  }
-  paint_launch(s, (const RenderDesc*)d, nullptr, n, (const float*)(d + o_masks), (long)S * S, S, binarize_thresh, H, W, nullptr,
-               0.0f, inst_img ? (int*)(d + o_inst) : nullptr, cls_img ? (int*)(d + o_cls) : nullptr, nullptr, nullptr, nullptr);
+  layout(WsLayout(hs.buf));
+  MNC_HIP_TRY(hs.up(d_descs, descs.data(), (size_t)n * sizeof(RenderDesc)));
+  MNC_HIP_TRY(hs.up(d_masks, masks, (size_t)n * S * S * 4));
+  paint_launch(hs.stream, d_descs, nullptr, n, d_masks, (long)S * S, S, binarize_thresh, H, W, nullptr, 0.0f,
+               inst_img ? d_inst : nullptr, cls_img ? d_cls : nullptr, nullptr, nullptr, nullptr);
   MNC_HIP_TRY(hipGetLastError());
-  if (inst_img) MNC_HIP_TRY(hipMemcpyAsync(inst_img, d + o_inst, px * 4, hipMemcpyDeviceToHost, s));
-  if (cls_img) MNC_HIP_TRY(hipMemcpyAsync(cls_img, d + o_cls, px * 4, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipStreamSynchronize(s));
+  if (inst_img) MNC_HIP_TRY(hs.down(inst_img, d_inst, px * 4));
+  if (cls_img) MNC_HIP_TRY(hs.down(cls_img, d_cls, px * 4));
+  MNC_HIP_TRY(hs.sync());
   clear_error();
   return MNC_OK;
 }

@@ -897,9 +897,9 @@ static int roi_warp_impl(mnc_ctx* ctx, const float* d_feat, const float* d_hwc_r
   if (!d_hwc) {
     rc = ensure_scratch(ctx, (size_t)C * H * W * 4);
     if (rc) return rc;
-    rc = c8_to_hwc_launch(ctx, d_feat, (float*)ctx->scratch, C, H, W);
+    rc = c8_to_hwc_launch(ctx, d_feat, (float*)ctx->scratch.p, C, H, W);
     if (rc) return rc;
-    d_hwc = (const float*)ctx->scratch;
+    d_hwc = (const float*)ctx->scratch.p;
   }
   LaunchScope ls(ctx, pool2 ? "roi_warp_pool2" : "roi_warp", 0.0,
                  4.0 * ((double)R * PH * PW * C * (1.0 + 4.0 * samples)) + ((sm_fmt == 1 || sm_fmt == 3) ? 2.0 : sm_fmt == 2 ? 4.0 : 0.0) * R * PH * PW * C);

@@ -98,15 +98,6 @@ __global__ __launch_bounds__(kSdsThreads) void sds_best_overlap_kernel(
   if (threadIdx.x == 0) { best_gt[p] = bg; best_inter[p] = bi; best_union[p] = bu; }
 }
 
-namespace {
-// hipMalloc'd for one call and freed on every way out: a whole-dataset call needs ~0.5 KB per prediction, too much to keep
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
 }  // namespace mnc
 
 using namespace mnc;
@@ -155,44 +146,44 @@ int mnc_sds_best_overlap(const double* boxes, const unsigned char* masks, int P,
   }
   const int S = mask_size;
   const size_t nP = (size_t)P, nG = (size_t)G;
-  const size_t o_masks = up256(nP * 32), o_begin = o_masks + up256(nP * S * S), o_end = o_begin + up256(nP * 4),
-               o_bounds = o_end + up256(nP * 4), o_offs = o_bounds + up256(nG * 16), o_areas = o_offs + up256(nG * 8),
-               o_bits = o_areas + up256(nG * 8), o_bg = o_bits + up256(gt_bytes), o_bi = o_bg + up256(nP * 4),
-               o_bu = o_bi + up256(nP * 8), total = o_bu + up256(nP * 8);
-  LegacyWs* w = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int rc = legacy_ws(device_id, 0, &w, &lock);      // the device's stream (and device check); the buffer is this call's own
+  double* d_boxes; unsigned char *d_masks, *d_bits; int *d_begin, *d_end, *d_bounds, *d_bg; long long *d_offs, *d_areas, *d_bi, *d_bu;
+  auto layout = [&](WsLayout l) {
+    d_boxes = l.take<double>(nP * 4);
+    d_masks = l.take<unsigned char>(nP * S * S);
+    d_begin = l.take<int>(nP);
+    d_end = l.take<int>(nP);
+    d_bounds = l.take<int>(nG * 4);
+    d_offs = l.take<long long>(nG);
+    d_areas = l.take<long long>(nG);
+    d_bits = l.take<unsigned char>(gt_bytes);
+    d_bg = l.take<int>(nP);
+    d_bi = l.take<long long>(nP);
+    d_bu = l.take<long long>(nP);
+    return l.bytes();
+  };
+  HostScope hs;
+  int rc = hs.open(device_id, 0);                   // the device's stream (and device check)
   if (rc) return rc;
-  DevBuf buf;
-  if (hipMalloc(&buf.p, total) != hipSuccess) {
-    (void)hipGetLastError();
-    buf.p = nullptr;
-    set_error("mnc_sds_best_overlap: hipMalloc(%zu) failed", total);
-    return MNC_ERR_NOMEM;
-  }
-  char* d = (char*)buf.p;
-  hipStream_t s = w->stream;
-  MNC_HIP_TRY(hipMemcpyAsync(d, boxes, nP * 32, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(d + o_masks, masks, nP * S * S, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(d + o_begin, gt_begin, nP * 4, hipMemcpyHostToDevice, s));
-  MNC_HIP_TRY(hipMemcpyAsync(d + o_end, gt_end, nP * 4, hipMemcpyHostToDevice, s));
-  if (G) {
-    MNC_HIP_TRY(hipMemcpyAsync(d + o_bounds, gt_bounds, nG * 16, hipMemcpyHostToDevice, s));
-    MNC_HIP_TRY(hipMemcpyAsync(d + o_offs, gt_offsets, nG * 8, hipMemcpyHostToDevice, s));
-    MNC_HIP_TRY(hipMemcpyAsync(d + o_areas, gt_areas, nG * 8, hipMemcpyHostToDevice, s));
-  }
-  if (gt_bytes) MNC_HIP_TRY(hipMemcpyAsync(d + o_bits, gt_bits, gt_bytes, hipMemcpyHostToDevice, s));
+  CallBuf buf;     // this call's own: a whole-dataset call needs ~0.5 KB per prediction, too much to keep in the workspace
+  rc = buf.alloc("mnc_sds_best_overlap", layout(WsLayout()));
+  if (rc) return rc;
+  layout(WsLayout(buf.p));
+  MNC_HIP_TRY(hs.up(d_boxes, boxes, nP * 32));
+  MNC_HIP_TRY(hs.up(d_masks, masks, nP * S * S));
+  MNC_HIP_TRY(hs.up(d_begin, gt_begin, nP * 4));
+  MNC_HIP_TRY(hs.up(d_end, gt_end, nP * 4));
+  MNC_HIP_TRY(hs.up(d_bounds, gt_bounds, nG * 16));
+  MNC_HIP_TRY(hs.up(d_offs, gt_offsets, nG * 8));
+  MNC_HIP_TRY(hs.up(d_areas, gt_areas, nG * 8));
+  MNC_HIP_TRY(hs.up(d_bits, gt_bits, gt_bytes));
   // a numpy float32 mask is compared with the Python float threshold in float32
-  hipLaunchKernelGGL(sds_best_overlap_kernel, dim3(P), dim3(kSdsThreads), 0, s, (const double*)d,
-                     (const unsigned char*)(d + o_masks), S, (const int*)(d + o_begin), (const int*)(d + o_end),
-                     (const int*)(d + o_bounds), (const long long*)(d + o_offs), (const unsigned char*)(d + o_bits),
-                     (const long long*)(d + o_areas), (float)binarize_thresh, (int*)(d + o_bg), (long long*)(d + o_bi),
-                     (long long*)(d + o_bu));
+  hipLaunchKernelGGL(sds_best_overlap_kernel, dim3(P), dim3(kSdsThreads), 0, hs.stream, d_boxes, d_masks, S, d_begin, d_end, d_bounds,
+                     d_offs, d_bits, d_areas, (float)binarize_thresh, d_bg, d_bi, d_bu);
   MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hipMemcpyAsync(best_gt, d + o_bg, nP * 4, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipMemcpyAsync(best_inter, d + o_bi, nP * 8, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipMemcpyAsync(best_union, d + o_bu, nP * 8, hipMemcpyDeviceToHost, s));
-  MNC_HIP_TRY(hipStreamSynchronize(s));
+  MNC_HIP_TRY(hs.down(best_gt, d_bg, nP * 4));
+  MNC_HIP_TRY(hs.down(best_inter, d_bi, nP * 8));
+  MNC_HIP_TRY(hs.down(best_union, d_bu, nP * 8));
+  MNC_HIP_TRY(hs.sync());
   clear_error();
   return MNC_OK;
 }

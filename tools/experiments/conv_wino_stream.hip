@@ -504,7 +504,7 @@ int wino_stream_launch(mnc_ctx* ctx, const float* d_in, const float* d_wpk, cons
   if (G > u2) G = u2;
   int rc = ensure_scratch(ctx, (size_t)G * 2 * kSTileFloats * 4 + (size_t)G * 64);
   if (rc) return rc;
-  float* part = (float*)ctx->scratch;
+  float* part = (float*)ctx->scratch.p;
 #ifdef MNC_TUNING
 #define MNC_STREAM_ABL(A) if (abl == A) rc = launch_stream<1, A>(ctx, d_in, d_wpk, d_bias, d_out, H, W, Cin, Cout, relu, pool, tiles_x, (int)u2, (int)G, part); else
   MNC_STREAM_ABL(1) MNC_STREAM_ABL(3) MNC_STREAM_ABL(4) MNC_STREAM_ABL(7) MNC_STREAM_ABL(8) MNC_STREAM_ABL(15) MNC_STREAM_ABL(16)
