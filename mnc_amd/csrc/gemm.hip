@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "fc_plan.h"
 #include "mnc_internal.h"
 #include "x3_split.h"
 
@@ -923,12 +924,9 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
   MNC_REQUIRE(M >= 0 && N > 0 && K > 0 && K % kBK == 0 && ldc >= N && act >= 0 && act <= 2,
               "mnc_fc: unsupported shape M=%d N=%d K=%d ldc=%d act=%d (need K%%32==0)", M, N, K, ldc, act);
   if (M == 0) return MNC_OK;
-  // Several 320-row blocks with a ragged tail (the CFM / ResNet configurations: 500-2000 RoIs per call): every block
-  // multiplies all of its row tiles, so the full blocks and the tail are two launches, each with the tile height and split
-  // count that suit it (M = 760: 2 x 320 + one 160-row block instead of 3 x 320).  Same stream: the second launch re-uses
-  // the split-K scratch after the first one's reduction.  MNC_FC_NOTAIL=1 keeps one launch.
-  if (M > 320 && M % 320 != 0 && M % 320 <= 160 && 2.0 * M * (double)N * K >= 2.0e9 && !tune(ctx, T_FC_NOTAIL, 0)) {
-    const int head = M / 320 * 320;
+  const FcPlan p = fc_plan(FcCall(M, N, K, ldc), ctx->tune, kTuningBuild);
+  if (p.head) {
+    const int head = p.head;
     // (two launches cannot hand ONE set of partial sums to the caller: the deferred reduction is for single-launch products only --
     // both halves finish their own reduction, the caller sees deferred_splits == 1)
     const bool defer = ctx->defer_reduce;
@@ -940,59 +938,11 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
     ctx->deferred_splits = 1;
     return rc;
   }
-  // small problems (< 2 GFLOP) use 64-row workgroups so that rows, column tiles and K splits together fill the chip; the
-  // large ones the smallest of {160, 320} rows that covers M in one block (weights streamed once).  Measured at M = 300
-  // (round 1): 320 rows x 32-deep stages, one workgroup per CU, and 160 rows x 16-deep stages, two per CU, are within 1 %
-  // of each other on every FC of the heads (MNC_FC_TILE=5|10 overrides).
-  const bool small = 2.0 * M * (double)N * K < 2.0e9;
-  int mt = small ? 2 : (M <= 160 ? 5 : 10);            // row tiles per workgroup (all of them are always multiplied)
-  // When the K splits of the 320-row variant would be shorter than 64 stages (fc7, fc6_maskest), 160-row blocks were a few per
-  // cent faster than the REGISTER-STAGED 320-row kernel (round 1: 107 vs 112 us, 160 vs 169 us).  Against the LDS-DMA kernel
-  // (K % 64 == 0) they lose: fc7 105.7 -> 100.7 us, fc6_maskest 159.6 -> 153.5 us on the 320-row DMA kernel (round 3,
-  // kernel_bench fc), and the weights are streamed once instead of once per row block -- so the rule only applies without it.
-  if (mt == 10 && (K % 64 != 0 || tune(ctx, T_FC_DMA, 1) == 0) && (K / 32) / cdiv(256, cdiv(N, kBN) * cdiv(M, 320)) < 64) mt = 5;
-  if (tune_set(ctx, T_FC_TILE)) {
-    const int v = tune(ctx, T_FC_TILE, 0);
-    if (!small && (v == 5 || v == 10)) mt = v;
-  }
-  const int sk = mt == 5 ? 16 : 32;                    // K values per stage
-  const int bm = 32 * mt;
-  const int tn = cdiv(N, kBN), tm = cdiv(M, bm), stages = K / sk;
-  // enough splits to give every CU its workgroups (two per CU except for the 320-row variant), but at least 64 K values
-  // (8 stages for the large variants) per split
-  int splits = cdiv(mt == 10 ? 256 : 512, tn * tm);
-  // small variant: deep K (the N = 126 heads, K = 8192) gets at least 8 stages per split -- 32 splits instead of 103 cut
-  // its reduction from 24 to 11 us and the total from 44 to 29 us; shallow K (mask_pred, K = 256) keeps 2
-  const int min_stages = small ? (stages >= 64 ? 8 : 2) : (mt == 5 ? 16 : 8);
-  if (splits > stages / min_stages) splits = stages / min_stages;
-  // a small GEMM over at most 8 stages (mask_pred: K = 256) is not cut at all: four ranges of two stages each cost 9.5 us + a
-  // 6.3 us reduction launch (kernel_bench fc, round 5) for 0.07 GFLOP; one range of eight stages writes the result itself
-  if (small && stages <= 8) splits = 1;
-  if (splits < 1) splits = 1;
-  if (!small && tm == 1) splits = fc_split_div(ctx, splits, K);
-  if (tm > 1 && !small)      // several row blocks: pick the split count by cost (see choose_splits); one block: as tuned above
-    splits = choose_splits(tn * tm, stages, min_stages, mt == 10 ? 256 : 512,
-                           (double)bm * kBN * sk * 2.0 / 460.0e3 * (mt == 10 ? 1.0 : 2.0), 4.0 * M * (double)N);
-  int kper = cdiv(stages, splits) * sk;
-  // LDS-DMA build of the 320-row kernel (fc_mfma_dma16_kernel; MNC_FC_DMA=0: the register-staged one).  Its loop walks one stage per
-  // iteration, so a K range may hold an odd number of stages (rounds 3-5 rounded the ranges up to even counts, a leftover of the first
-  // DMA build: fc6_maskest then ran 121 ranges of 26 stages on 242 CUs where 126 ranges of 25 fit 252 -- profiles/r06_fc_maskest.txt)
-  const bool dma = mt == 10 && K % 64 == 0 && !tune_set(ctx, T_FC_ABL) && tune(ctx, T_FC_DMA, 1) != 0;
-  if (dma && tune(ctx, T_FC_EVEN, 0)) kper = cdiv(kper, 64) * 64;
-  splits = cdiv(K, kper);
-  // (In-launch reduction of the K ranges by each tile's last arriver: built and measured in round 5 -- a loss here, the last arriver
-  // reads 8 x 160 KB on one CU while 224 idle, profiles/r05_inlaunch_reduce.txt -- and removed in round 6.)
-  // the eight-wave 16x16x4 kernel leaves its K ranges as SLABS (its accumulators in register layout, 160 KB per tile and range:
-  // fc_reduce_slab_kernel); every other kernel as [range][M][N] rows (fc_reduce_kernel)
-  bool slab = dma;
-#ifdef MNC_TUNING
-  if (dma && tune(ctx, T_FC_DMA_ABL, 0) < 16 &&
-      (tune(ctx, T_FC_MFMA16, 1) == 0 || tune(ctx, T_FC_DMA_WAVES, 8) == 4 || tune(ctx, T_FC_DMA_ABL, 0)))
-    slab = false;                                    // (the 32x32x2 builds of the tuning library)
-#endif
+  const int mt = p.mt, tn = p.tn, tm = p.tm, splits = p.splits, kper = p.kper;
+  const bool small = p.small, dma = p.kernel == kFcDma16, slab = p.slab;
   float* part = nullptr;
   if (splits > 1) {
-    int rc = ensure_scratch(ctx, slab ? (size_t)tn * tm * splits * 163840 : (size_t)splits * M * N * 4);
+    int rc = ensure_scratch(ctx, p.part_bytes);
     if (rc) return rc;
     part = (float*)ctx->scratch.p;
   }
@@ -1004,13 +954,7 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
 #define MNC_FC_DMA_LAUNCH(A, WM) MNC_FC_DMA_LAUNCH_H(A, WM, 0)
 #define MNC_FC_DMA_LAUNCH_H(A, WM, H)                                                                                               \
   do {                                                                                                                              \
-    static std::atomic<unsigned long long> attr_set{0};            /* one bit per device: function attributes are per device */   \
-    const unsigned long long bit = 1ull << (ctx->device & 63);                                                                      \
-    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {                                                                        \
-      MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_mfma_dma_kernel<10, A, WM, H>),                                 \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                            \
-      attr_set.fetch_or(bit, std::memory_order_relaxed);                                                                            \
-    }                                                                                                                               \
+    MNC_HIP_TRY((lds_limit_once<fc_mfma_dma_kernel<10, A, WM, H>>(ctx->device, lds)));                                              \
     hipLaunchKernelGGL((fc_mfma_dma_kernel<10, A, WM, H>), dim3(tn * splits * tm), dim3(256 * WM), lds, ctx->stream, d_a, d_w, d_bias, \
                        d_out, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, tn, splits, tm);                                  \
   } while (0)
@@ -1024,12 +968,11 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
       const int waves = tune(ctx, T_FC_DMA_WAVES, 8), dabl = tune(ctx, T_FC_DMA_ABL, 0);
       if (dabl >= 16) {                              // ablations of the product kernel
         launched = true;
-        const int drop = tm == 1 && M > 288 && M <= 304 ? 1 : 0;
         auto kern = dabl == 17 ? fc_mfma_dma16_kernel<10, 1> : dabl == 18 ? fc_mfma_dma16_kernel<10, 2> : dabl == 19 ? fc_mfma_dma16_kernel<10, 3>
                     : dabl == 20 ? fc_mfma_dma16_kernel<10, 0, 1> : dabl == 21 ? fc_mfma_dma16_kernel<10, 4, 1> : fc_mfma_dma16_kernel<10, 0>;
         MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL(kern, dim3(tn * splits * tm), dim3(512), lds, ctx->stream, d_a, d_w, d_bias, d_out, part, M, N, K, ldc, kper,
-                           act, splits == 1 ? 1 : 0, tn, splits, tm, drop, (const float*)nullptr, (const float*)nullptr,
+                           act, splits == 1 ? 1 : 0, tn, splits, tm, p.drop, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (float*)nullptr, 0);
       } else if (tune(ctx, T_FC_MFMA16, 1) == 0 || waves == 4 || dabl) {
         launched = true;
@@ -1042,24 +985,11 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
       }
 #endif
       if (!launched) {
-        static std::atomic<unsigned long long> attr16{0};            // one bit per device: function attributes are per device
-        const unsigned long long bit = 1ull << (ctx->device & 63);
-        if (!(attr16.load(std::memory_order_relaxed) & bit)) {
-          MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_mfma_dma16_kernel<10, 0, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-          MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_mfma_dma16_kernel<10, 0, 0>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-          attr16.fetch_or(bit, std::memory_order_relaxed);
-        }
-        // one row block whose last 16-row sub-tile holds no live row (300 RoIs = 18 sub-tiles + 12 rows): its MFMAs are skipped
-        const int drop = tm == 1 && M > 288 && M <= 304 ? 1 : 0;
-        // copies through buffer descriptors (32-bit lane offsets from the workgroup's first row: 320 rows of K floats must stay
-        // below the descriptor's range) -- same bytes to the same places, bit-identical results, 2-4 % faster than 64-bit lane
-        // addresses (kernel_bench fc, MNC_FC_DMA_ABL=20 against 16: fc6 511 -> 500 us, fc7 92.9 -> 89.2, fc6_maskest 142 -> 137)
-        const bool buf = 320.0 * (double)K * 4.0 < 1.8e9;
-        hipLaunchKernelGGL((buf ? fc_mfma_dma16_kernel<10, 0, 1> : fc_mfma_dma16_kernel<10, 0, 0>), dim3(tn * splits * tm), dim3(512), lds,
+        if (p.buf) MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 1>>(ctx->device, lds)));
+        else MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 0>>(ctx->device, lds)));
+        hipLaunchKernelGGL((p.buf ? fc_mfma_dma16_kernel<10, 0, 1> : fc_mfma_dma16_kernel<10, 0, 0>), dim3(tn * splits * tm), dim3(512), lds,
                            ctx->stream, d_a, d_w, d_bias, d_out, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, tn, splits,
-                           tm, drop, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0);
+                           tm, p.drop, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0);
       }
     }
     else if (mt == 2) MNC_FC_LAUNCH(2, 32, 0);
@@ -1122,34 +1052,20 @@ int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float*
   MNC_REQUIRE(M >= 0 && N > 0 && K > 0 && K % kBK == 0 && ldc >= N && act >= 0 && act <= 2,
               "mnc_fc_pair: unsupported shape M=%d N=%d K=%d ldc=%d act=%d (need K%%32==0)", M, N, K, ldc, act);
   if (M == 0) return MNC_OK;
-  // what mnc_fc would do with ONE of them: the 320-row LDS-DMA kernel in a single launch?  (small products run the 64-row kernel,
-  // M <= 160 the 160-row one, several row blocks with a ragged tail two launches: none of these is paired)
-  const bool big = 2.0 * M * (double)N * K >= 2.0e9;
-  const bool ragged = M > 320 && M % 320 != 0 && M % 320 <= 160 && !tune(ctx, T_FC_NOTAIL, 0);
-  const bool paired = big && M > 160 && !ragged;
-  const bool vec = N % 4 == 0 && ldc % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_out0) | reinterpret_cast<uintptr_t>(d_out1) |
-                                                   reinterpret_cast<uintptr_t>(d_bias0) | reinterpret_cast<uintptr_t>(d_bias1)) & 15) == 0;
-  bool fast = paired && vec && K % 64 == 0 && tune(ctx, T_FC_DMA, 1) != 0 && !tune_set(ctx, T_FC_ABL) && !tune_set(ctx, T_FC_TILE) &&
-              320.0 * (double)K * 4.0 < 1.8e9 && !ctx->defer_reduce;
-#ifdef MNC_TUNING
-  if (tune(ctx, T_FC_MFMA16, 1) == 0 || tune(ctx, T_FC_DMA_WAVES, 8) == 4 || tune(ctx, T_FC_DMA_ABL, 0)) fast = false;
-#endif
-  if (!fast) {
+  FcCall call(M, N, K, ldc);
+  call.defer_reduce = ctx->defer_reduce;
+  call.aligned16 = ((reinterpret_cast<uintptr_t>(d_out0) | reinterpret_cast<uintptr_t>(d_out1) | reinterpret_cast<uintptr_t>(d_bias0) |
+                     reinterpret_cast<uintptr_t>(d_bias1)) & 15) == 0;
+  const FcPlan p = fc_pair_plan(call, ctx->tune, kTuningBuild);
+  if (p.two_singles) {
     int rc = mnc_fc(ctx, d_a0, d_w0, d_bias0, d_out0, M, N, K, ldc, act);
     if (rc) return rc;
     return mnc_fc(ctx, d_a1, d_w1, d_bias1, d_out1, M, N, K, ldc, act);
   }
-  const int tn = cdiv(N, kBN), tm = cdiv(M, 320), stages = K / 32;
-  int splits = cdiv(256, 2 * tn * tm);
-  if (splits > stages / 8) splits = stages / 8;
-  if (splits < 1) splits = 1;
-  if (tm > 1) splits = choose_splits(2 * tn * tm, stages, 8, 256, 320.0 * kBN * 32 * 2.0 / 460.0e3, 8.0 * M * (double)N);
-  else splits = fc_split_div(ctx, splits, K);
-  int kper = cdiv(cdiv(stages, splits) * 32, 64) * 64;
-  splits = cdiv(K, kper);
+  const int tn = p.tn / 2, tm = p.tm, splits = p.splits, kper = p.kper;      // (tn: column tiles of ONE product)
   float* part = nullptr;
   if (splits > 1) {
-    int rc = ensure_scratch(ctx, (size_t)2 * tn * tm * splits * 163840);
+    int rc = ensure_scratch(ctx, p.part_bytes);
     if (rc) return rc;
     part = (float*)ctx->scratch.p;
   }
@@ -1157,16 +1073,9 @@ int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float*
   {
     const double flops = 4.0 * M * (double)N * K, bytes = 8.0 * ((double)N * K + (double)M * K + (double)M * N);
     LaunchScope ls(ctx, "fc_mfma", flops, bytes);
-    static std::atomic<unsigned long long> attr{0};
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(attr.load(std::memory_order_relaxed) & bit)) {
-      MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_mfma_dma16_kernel<10, 0, 1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr.fetch_or(bit, std::memory_order_relaxed);
-    }
-    const int drop = tm == 1 && M > 288 && M <= 304 ? 1 : 0;
+    MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 1>>(ctx->device, lds)));
     hipLaunchKernelGGL((fc_mfma_dma16_kernel<10, 0, 1>), dim3(2 * tn * splits * tm), dim3(512), lds, ctx->stream, d_a0, d_w0, d_bias0,
-                       d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, tm, drop, d_a1, d_w1,
+                       d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, tm, p.drop, d_a1, d_w1,
                        d_bias1, d_out1, tn);
     int rc = ls.finish("fc_mfma_dma16_kernel");
     if (rc) return rc;

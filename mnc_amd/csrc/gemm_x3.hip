@@ -18,6 +18,7 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "fc_plan.h"
 #include "mnc_internal.h"
 #include "x3_split.h"
 
@@ -694,22 +695,14 @@ template <int F16>
 static int fc_lowp(mnc_ctx* ctx, const char* what, const float* d_a, const uint4* d_pre, int mstride, const void* d_w_packed,
                    const float* d_bias, float* d_out, int M, int N, int K, int ldc, int act, void* d_osm = nullptr, int osm_fmt = 0,
                    long osm_rows = 0, long osm_row0 = 0) {
-  constexpr int kStage = F16 ? 64 : kXBK;
   if (M == 0) return MNC_OK;
-  // Several row blocks (M > 320: the 1000-RoI ResNet configuration, CFM): every block streams its whole weight panel, so a
-  // block costs about (rows + 128) -- measured: the 40-row tail of M = 1000 took 0.19 of the time of the 960 rows before it.
-  // 256-row blocks (fc_x3_kernel<8, 2>) in ONE launch when that is cheaper than 320-row blocks plus a tail launch:
-  // M = 1000: 4 x (256 + 128) = 1536 against 3 x 448 + 288 = 1632; M = 960 or 2000 stay on 320-row blocks.
-  bool rows256 = false;
-  if (M > 320 && 2.0 * M * (double)N * K >= 2.0e9) {
-    const int tail = M % 320;
-    const long cost320 = (long)(M / 320) * 448 + (tail == 0 ? 0 : tail <= 160 ? 288 : 448);
-    const long cost256 = (long)cdiv(M, 256) * 384;
-    rows256 = cost256 < cost320 && !tune(ctx, T_FC_NO256, 0);
-  }
-  // full 320-row blocks and a ragged tail of at most 160 rows are two launches, each with its own tile height (see mnc_fc)
-  if (!rows256 && M > 320 && M % 320 != 0 && M % 320 <= 160 && 2.0 * M * (double)N * K >= 2.0e9 && !tune(ctx, T_FC_NOTAIL, 0)) {
-    const int head = M / 320 * 320;
+  FcCall call(M, N, K, ldc);
+  call.f16 = F16;
+  call.osm[0] = d_osm != nullptr; call.osm_rows = osm_rows; call.osm_row0 = osm_row0;
+  call.pre[0] = d_pre != nullptr; call.mstride = mstride;
+  const FcPlan p = fc_lowp_plan(call, ctx->tune);
+  if (p.head) {
+    const int head = p.head;
     int rc = fc_lowp<F16>(ctx, what, d_a, d_pre, mstride, d_w_packed, d_bias, d_out, head, N, K, ldc, act, d_osm, osm_fmt, osm_rows,
                           osm_row0);
     if (rc) return rc;
@@ -717,64 +710,11 @@ static int fc_lowp(mnc_ctx* ctx, const char* what, const float* d_a, const uint4
                         d_w_packed, d_bias, d_out + (size_t)head * ldc, M - head, N, K, ldc, act, d_osm, osm_fmt, osm_rows,
                         osm_row0 + head);
   }
-  // row tiles per workgroup: 2 (64 rows) for the small GEMMs, else the smallest of {5, 10} that covers M in one block
-  const bool small = 2.0 * M * (double)N * K < 2.0e9;
-  int mt = small ? 2 : (M <= 160 ? 5 : 10);
-  // 320-row blocks stream the weights once but need many K splits to fill the chip; when a split would be shorter than 64 stages
-  // (bf16x3; 32 for fp16), 160-row blocks (twice the tiles, half the splits and half the partial-sum traffic) are faster
-  // (measured at M = 300, bf16x3: fc7 59 vs 69 us, fc6_maskest 132 vs 151 us, fc6 274 vs 262 us)
-  // Round 6, throughput plan: ONE row block runs on the 256-column LDS-DMA kernel from N = 256 on, in fc_lowp_ranges' K ranges, split
-  // bf16 included -- fc6_maskest (N = 256, K = 100352): one column tile x 49 ranges of 2048 K values on 49 CUs, each operand read
-  // once (111 MB), instead of 2 x 2 tiles x 64 ranges on the 160-row register-staged kernel.  The launch is longer (fp16 37 -> 67 us,
-  // split bf16 65 -> 159) and costs a fifth of the CU time: f16 985 -> 991 images/s, mixed 616 -> 620, bf16x3 488 -> 491 (two runs
-  // each, profiles/r06_fc_ranges.txt); the latency plan keeps the old choice.
-  const bool wide1 = tune(ctx, T_FCX3_WIDE, 1) != 0 && !tune_set(ctx, T_FCX3_TILE) && !plan_latency(ctx) && mt == 10 && M <= 320 && N % 256 == 0 && N >= 256 &&
-                     (K / kStage) / fc_lowp_ranges(ctx, 256, K, N / 256) >= (F16 ? 8 : 16);
-  if (!wide1 && mt == 10 && (K / kStage) / cdiv(256, cdiv(N, kXBN) * cdiv(M, 320)) < (F16 ? 32 : 64)) mt = 5;
-  if (rows256) mt = 8;
-  if (tune_set(ctx, T_FCX3_TILE)) {
-    const int v = tune(ctx, T_FCX3_TILE, 0);
-    if (v == 2 || v == 5 || v == 8 || v == 10) mt = v;
-  }
-  const int bm = 32 * mt;
-  const int stages = K / kStage, tm = cdiv(M, bm);
-  // 256- or 320-row blocks, N a multiple of 256: the 256-column LDS-DMA kernel (fc_lowp_dma_kernel) -- half the activation
-  // bytes per flop (the reduced-precision pipe is power limited, DESIGN.md section 9 item 4: bytes are energy) -- when its K splits keep at least 8 stages
-  // (fc7 at 300 RoIs would get 4: prologue and epilogue of a workgroup then outweigh the traffic saved).  FCX3_WIDE=0: off.
-  bool wide = false;
-  // (throughput plan, round 6: from N = 256 on -- one column tile per row block; ResNet-50 configuration, fc6_maskest at 1000 RoIs:
-  // f16 260.5 -> 264.6 images/s, mixed 130.2 -> 134.2)
-  if ((mt == 8 || mt == 10) && N % 256 == 0 && N >= (plan_latency(ctx) ? 512 : 256) && tune(ctx, T_FCX3_WIDE, 1) != 0) {
-    const int sp = cdiv(256, (N / 256) * tm);
-    wide = stages / (sp > 0 ? sp : 1) >= (F16 ? 8 : 16);
-    // split bf16 at one row block (300 RoIs): three MFMAs per term make the operand bytes a smaller share of the work, and the doubled
-    // K splits cost in the reduction what the kernel gains (fc6: 213.9 + 10.8 us vs 204.5 + 16.9 us) -- the 128-column kernel stays
-    if (!F16 && tm == 1 && !tune_set(ctx, T_FCX3_WIDE)) wide = false;
-  }
-  if (wide1) wide = true;
-  // (the 256-column kernel addresses a stage of the activations by a 32-bit scalar offset: stages x m_stride x 128 bytes)
-  if (wide && (double)stages * (double)(d_pre ? mstride : M) * 128.0 >= 4.0e9) wide = false;
-  const int bn_w = wide ? 256 : kXBN;
-  const int tn = cdiv(N, bn_w);
-  int splits = cdiv(mt == 2 ? 512 : 256, tn * tm);
-  const int min_stages = F16 ? (mt == 2 ? 1 : 4) : (mt == 2 ? 2 : 8);
-  if (splits > stages / min_stages) splits = stages / min_stages;
-  if (splits < 1) splits = 1;
-  if (tm == 1 && mt != 2) {
-    const int full = splits;
-    splits = fc_lowp_ranges(ctx, splits, K, tn);      // (round 6: CU time, not launch time -- mnc_internal.h)
-    if (splits == 1 && full > 1 && d_osm && (ldc != N || osm_rows != M || osm_row0 != 0)) splits = 2;
-  }
-  if (tm > 1 && mt != 2)     // several row blocks: split count by cost (mnc_internal.h: choose_splits)
-    // (round 6, throughput plan: the K ranges fill HALF the chip here too -- ResNet-50 configuration, 1000 RoIs, four images in
-    // flight: f16 249 -> 262 images/s, mixed 126.5 -> 131.6 with 128 slots, 259 with 64; FC_SLOTS overrides)
-    splits = choose_splits(tn * tm, stages, min_stages, tune(ctx, T_FC_SLOTS, plan_latency(ctx) ? 256 : 128),
-                           (double)bm * bn_w * kStage * 2.0 / (F16 ? 2000.0e3 : 1050.0e3), 4.0 * M * (double)N);
-  const int kper = cdiv(stages, splits) * kStage;
-  splits = cdiv(K, kper);
+  const int mt = p.mt, tn = p.tn, tm = p.tm, tm_arg = p.tm_arg, splits = p.splits, kper = p.kper;
+  const bool small = p.small, wide = p.kernel == kFcWide;
   // scratch arena: [split-K partials | the activations in their 2-byte stage-major form (when they arrive as fp32)]
-  const size_t part_bytes = splits > 1 ? (((size_t)splits * M * N * 4 + 255) & ~(size_t)255) : 0;
-  int rc = ensure_scratch(ctx, part_bytes + (d_pre ? 0 : (size_t)M * K * (F16 ? 2 : 4)));
+  const size_t part_bytes = p.part_bytes;
+  int rc = ensure_scratch(ctx, part_bytes + p.conv_bytes);
   if (rc) return rc;
   float* part = splits > 1 ? (float*)ctx->scratch.p : nullptr;
   const uint4* d_ax = d_pre;
@@ -790,12 +730,6 @@ static int fc_lowp(mnc_ctx* ctx, const char* what, const float* d_a, const uint4
   }
   const double flops = 2.0 * M * (double)N * K;
   const double bytes = (F16 ? 2.0 : 4.0) * ((double)N * K + (double)M * K) + 4.0 * (double)M * N;
-  // Block order with several row blocks: row block fastest, so the workgroups that multiply the same weight panel are
-  // neighbours on one XCD and stream it from L2 together instead of once per row block from HBM (measured, fp16, M = 960:
-  // N = 4096, K = 50176: 612 -> 555 us; M = 2000, K = 25088: 302 -> 282 us; with two column tiles (N = 256) it is 3 % slower,
-  // so only from 8 column tiles on).  MNC_FC_ORDER=0 / 1 forces the column-tile-fastest / row-block-fastest order.
-  const bool rows_fastest = tune_set(ctx, T_FC_ORDER) ? tune(ctx, T_FC_ORDER, 0) == 1 : tn >= 8;
-  const int tm_arg = (rows_fastest && tm > 1) ? -tm : tm;
   {
     LaunchScope ls(ctx, F16 == 2 ? (small ? "fc_bf16_small" : "fc_bf16") : F16 ? (small ? "fc_f16_small" : "fc_f16") : (small ? "fc_bf16x3_small" : "fc_bf16x3"), flops, bytes);
 #define MNC_X3_LAUNCH(MT, WR, A)                                                                                              \
@@ -807,13 +741,7 @@ static int fc_lowp(mnc_ctx* ctx, const char* what, const float* d_a, const uint4
 #define MNC_WIDE_LAUNCH(MT)                                                                                                     \
   do {                                                                                                                          \
     constexpr int lds = 2 * (32 * MT + 256) * 128;                                                                              \
-    static std::atomic<unsigned long long> attr_set{0};            /* one bit per device */                                    \
-    const unsigned long long bit = 1ull << (ctx->device & 63);                                                                  \
-    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {                                                                    \
-      MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_lowp_dma_kernel<MT, F16>),                                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                        \
-      attr_set.fetch_or(bit, std::memory_order_relaxed);                                                                        \
-    }                                                                                                                           \
+    MNC_HIP_TRY((lds_limit_once<fc_lowp_dma_kernel<MT, F16>>(ctx->device, lds)));                                               \
     hipLaunchKernelGGL((fc_lowp_dma_kernel<MT, F16>), dim3(tn * splits * tm), dim3(512), lds, ctx->stream, d_ax,                      \
                        (const uint4*)d_w_packed, d_bias, d_out, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, tn, splits, \
                        tm_arg, mstride);                                                                                        \
@@ -871,53 +799,22 @@ template <int F16>
 static int fc_lowp_pair(mnc_ctx* ctx, const char* what, const float* d_a0, const uint4* d_pre0, const float* d_a1, const uint4* d_pre1,
                         int mstride, const void* d_w0, const void* d_w1, const float* d_bias0, const float* d_bias1, float* d_out0,
                         float* d_out1, int M, int N, int K, int ldc, int act, void* d_osm0, void* d_osm1, int osm_fmt) {
-  constexpr int kStage = F16 ? 64 : kXBK;
   if (M == 0) return MNC_OK;
-  const int stages = K / kStage, tn = N / 256;
-  // Several row blocks (round 6, throughput plan only; the ResNet-50 configuration's 1000 RoIs): the pair runs as ONE launch too when
-  // fc_lowp would run each product as one launch -- 256-row blocks, or 320-row blocks without a ragged tail of <= 160 rows
-  int mt = 10, tm = 1;
-  bool multi = false;
-  if (M > 320 && !plan_latency(ctx)) {
-    const int tail = M % 320;
-    const long cost320 = (long)(M / 320) * 448 + (tail == 0 ? 0 : tail <= 160 ? 288 : 448);
-    const long cost256 = (long)cdiv(M, 256) * 384;
-    const bool rows256 = cost256 < cost320 && !tune(ctx, T_FC_NO256, 0);
-    multi = rows256 || tail == 0 || tail > 160 || tune(ctx, T_FC_NOTAIL, 0);
-    mt = rows256 ? 8 : 10;
-    tm = cdiv(M, 32 * mt);
-  }
-  bool paired = M > 160 && (M <= 320 || multi) && N % 256 == 0 && N >= 512 && 2.0 * M * (double)N * K >= 2.0e9 && tune(ctx, T_FCX3_WIDE, 1) != 0 &&
-                (double)stages * (double)((d_pre0 || d_pre1) ? mstride : M) * 128.0 < 4.0e9 &&
-                !tune_set(ctx, T_FCX3_TILE) && tune(ctx, T_FUSE_SMALL, 1) != 0;
-  int splits = 1;
-  if (paired && tm > 1) {
-    splits = choose_splits(2 * tn * tm, stages, F16 ? 4 : 8, tune(ctx, T_FC_SLOTS, 128),
-                           (double)(32 * mt) * 256 * kStage * 2.0 / (F16 ? 2000.0e3 : 1050.0e3), 8.0 * M * (double)N);
-    paired = stages / splits >= (F16 ? 8 : 16);
-    if (splits == 1 && stages >= 2 * (F16 ? 8 : 16) && (d_osm0 || d_osm1) && ldc != N) splits = 2;
-  } else if (paired) {
-    splits = cdiv(256, 2 * tn);
-    if (splits > stages / (F16 ? 4 : 8)) splits = stages / (F16 ? 4 : 8);
-    if (splits < 1) splits = 1;
-    paired = stages / splits >= (F16 ? 8 : 16);                // (the 256-column kernel's own bar: fc_lowp)
-    const int full = splits;
-    splits = fc_lowp_ranges(ctx, splits, K, 2 * tn, true);     // (round 6: CU time, not launch time -- mnc_internal.h)
-    // (a second output in stage-major form is written by the reduction pass; without one only dense rows can be converted)
-    if (splits == 1 && full > 1 && (d_osm0 || d_osm1) && ldc != N) splits = 2;
-  }
-  if (!paired) {
+  FcCall call(M, N, K, ldc);
+  call.f16 = F16;
+  call.osm[0] = d_osm0 != nullptr; call.osm[1] = d_osm1 != nullptr;
+  call.pre[0] = d_pre0 != nullptr; call.pre[1] = d_pre1 != nullptr; call.mstride = mstride;
+  const FcPlan p = fc_lowp_pair_plan(call, ctx->tune);
+  if (p.two_singles) {
     int rc = fc_lowp<F16>(ctx, what, d_a0, d_pre0, d_a0 ? M : mstride, d_w0, d_bias0, d_out0, M, N, K, ldc, act, d_osm0,
                           d_osm0 ? osm_fmt : 0, M, 0);
     if (rc) return rc;
     return fc_lowp<F16>(ctx, what, d_a1, d_pre1, d_a1 ? M : mstride, d_w1, d_bias1, d_out1, M, N, K, ldc, act, d_osm1,
                         d_osm1 ? osm_fmt : 0, M, 0);
   }
-  const int kper = cdiv(stages, splits) * kStage;
-  splits = cdiv(K, kper);
+  const int tn = p.tn / 2, tm = p.tm, splits = p.splits, kper = p.kper;      // (tn: column tiles of ONE product)
   // scratch arena: [partial sums of both products | activations that arrive as fp32, in their 2-byte stage-major form]
-  const size_t part_bytes = splits > 1 ? (((size_t)2 * splits * M * N * 4 + 255) & ~(size_t)255) : 0;
-  const size_t conv_bytes = ((size_t)M * K * (F16 ? 2 : 4) + 255) & ~(size_t)255;
+  const size_t part_bytes = p.part_bytes, conv_bytes = p.conv_bytes;
   int rc = ensure_scratch(ctx, part_bytes + (d_pre0 ? 0 : conv_bytes) + (d_pre1 ? 0 : conv_bytes));
   if (rc) return rc;
   float* part = splits > 1 ? (float*)ctx->scratch.p : nullptr;
@@ -942,25 +839,17 @@ static int fc_lowp_pair(mnc_ctx* ctx, const char* what, const float* d_a0, const
   {
     const double flops = 4.0 * M * (double)N * K, bytes = (F16 ? 4.0 : 8.0) * ((double)N * K + (double)M * K) + 8.0 * (double)M * N;
     LaunchScope ls(ctx, F16 == 2 ? "fc_bf16" : F16 ? "fc_f16" : "fc_bf16x3", flops, bytes);
-    static std::atomic<unsigned long long> attr_set{0};            // one bit per device
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-      MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_lowp_dma_kernel<10, F16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (320 + 256) * 128));
-      MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fc_lowp_dma_kernel<8, F16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 256) * 128));
-      attr_set.fetch_or(bit, std::memory_order_relaxed);
-    }
-    // (several row blocks: row block fastest, so that the workgroups sharing a weight panel are neighbours on one XCD -- fc_lowp)
-    const int tm_arg = tm > 1 ? -tm : 1;
-    if (mt == 8)
-      hipLaunchKernelGGL((fc_lowp_dma_kernel<8, F16>), dim3(2 * tn * splits * tm), dim3(512), 2 * (256 + 256) * 128, ctx->stream, ax[0],
-                         (const uint4*)d_w0, d_bias0, d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, tm_arg,
-                         ms[0], ax[1], (const uint4*)d_w1, d_bias1, d_out1, tn);
-    else
-      hipLaunchKernelGGL((fc_lowp_dma_kernel<10, F16>), dim3(2 * tn * splits * tm), dim3(512), 2 * (320 + 256) * 128, ctx->stream, ax[0],
-                         (const uint4*)d_w0, d_bias0, d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, tm_arg,
-                         ms[0], ax[1], (const uint4*)d_w1, d_bias1, d_out1, tn);
+#define MNC_WIDE_PAIR_LAUNCH(MT)                                                                                                \
+  do {                                                                                                                          \
+    constexpr int lds = 2 * (32 * MT + 256) * 128;                                                                              \
+    MNC_HIP_TRY((lds_limit_once<fc_lowp_dma_kernel<MT, F16>>(ctx->device, lds)));                                               \
+    hipLaunchKernelGGL((fc_lowp_dma_kernel<MT, F16>), dim3(2 * tn * splits * tm), dim3(512), lds, ctx->stream, ax[0],           \
+                       (const uint4*)d_w0, d_bias0, d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, \
+                       p.tm_arg, ms[0], ax[1], (const uint4*)d_w1, d_bias1, d_out1, tn);                                        \
+  } while (0)
+    if (p.mt == 8) MNC_WIDE_PAIR_LAUNCH(8);
+    else MNC_WIDE_PAIR_LAUNCH(10);
+#undef MNC_WIDE_PAIR_LAUNCH
     rc = ls.finish("fc_lowp_dma_kernel<pair>");
     if (rc) return rc;
   }

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <climits>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mnc_hip.h"
+#include "tune.h"
 #include "ws_layout.h"
 
 namespace mnc {
@@ -33,22 +34,6 @@ struct ProfRecord {
 }  // namespace mnc
 
 namespace mnc {
-// Per-context overrides of the launchers' own choices (tile shapes, kernel variants, plan switches): mnc_ctx_set_tuning(ctx, "FC_TILE", 5)
-// or, once, at context creation, the environment variable MNC_<NAME>.  They exist so that every variant a launcher can pick by
-// shape is reachable from a test at a small shape, and for A/B measurements; no launch path calls getenv.  Ablation and
-// superseded kernel builds (FC_ABL, FC_DMA_ABL, FCX3_ABL, CONV_ABL, WINO_V = 1, WINO_VAR != 7) are only compiled with -DMNC_TUNING.
-#define MNC_TUNE_KEYS(X)                                                                                                          \
-  X(CONV_COT) X(CONV_ROWS) X(CONV_KSPLIT) X(CONV_ABL) X(CONV1X1_TILE) X(CONV2D_WIDE) X(WINO_ROWS) X(WINO_TAIL) X(WINO_V) X(WINO_VAR)  \
-  X(WINO_DMA) X(WINO_XCD) X(CONVX3_TILE) X(FC_NOTAIL) X(FC_TILE) X(FC_ABL) X(FC_DMA) X(PLAN) X(FC_RANGE_K) X(FC_SLOTS) X(FC_EVEN) X(FC_SPLIT_DIV) X(WINO_FILL) X(CONVX3_P0MIN) X(CONVX3_P1MIN) X(FC_DMA_ABL) X(FC_DMA_WAVES)    \
-  X(FC_NO256) X(FCX3_TILE) X(FC_ORDER) X(FCX3_ABL) X(FC_SM) X(PACKED_ACT) X(FUSE_POOLS) X(BRANCH_STREAMS) X(TOPK_SINGLE_WG)           \
-  X(ROI_SM_VARIANT) X(ROI_WARP_VARIANT) X(FC_REDUCE) X(WINO_F4) X(FUSE_SMALL) X(FCX3_WIDE) X(FC_HALF) X(WINO_STREAM) X(FC_MFMA16) X(WINO_MFMA16) X(ROI_ROW_SEGS)
-enum TuneKey {
-#define MNC_TUNE_ENUM(n) T_##n,
-  MNC_TUNE_KEYS(MNC_TUNE_ENUM)
-#undef MNC_TUNE_ENUM
-  T_COUNT
-};
-constexpr int kTuneUnset = INT_MIN;
 constexpr int kTickets = 4096;     // mnc_ctx::tickets
 }  // namespace mnc
 
@@ -91,42 +76,14 @@ struct mnc_graph {
 };
 
 namespace mnc {
-inline bool tune_set(const mnc_ctx* ctx, TuneKey k) { return ctx->tune[k] != kTuneUnset; }
-inline int tune(const mnc_ctx* ctx, TuneKey k, int dflt) { return ctx->tune[k] != kTuneUnset ? ctx->tune[k] : dflt; }
-// PLAN (round 6, profiles/r06_fc_ranges.txt): what the launchers' plans minimise.  0 (default) = the CU TIME of a launch -- the
-// deployment the headline measures, several images in flight per GPU: the CUs a launch leaves free run the other images' kernels.
-// 1 = the DURATION of a launch (rounds 1-5: every product cut until it fills the chip) -- one image at a time, latency.  One value
-// per context (MNC_PLAN=1 or mnc_ctx_set_tuning(ctx, "PLAN", "1")); the nets that share results bit for bit must share it.
-inline bool plan_latency(const mnc_ctx* ctx) { return tune(ctx, T_PLAN, 0) == 1; }
-// K ranges of a reduced-precision InnerProduct over ONE row block (round 6, profiles/r06_fc_ranges.txt).  Rounds 2-5 cut K so that
-// tiles x ranges filled all 256 CUs -- the shortest launch when the product has the chip to itself.  With several images in flight it
-// does not: other images' kernels run on the CUs a launch leaves free, and what a product costs is its CU TIME.  Every range pays a
-// prologue, an epilogue that writes 300 KB of partial sums, and its share of the reduction pass -- fc7 + fc7_mask in fp16: 17 us of
-// MFMA loop inside 38 us + a 16 us reduction with 8 ranges of 8 stages.  So: ranges of at least 2048 K values (pairs: 12288, below), and
-// no more ranges than fill HALF the chip (first: fc6 + fc6_mask 8 -> 4 ranges, fc7 + fc7_mask 8 -> 2; then 2 and 1).  Four images in flight: f16 870 -> 914 images/s, bf16
-// 841 -> 902, mixed 553 -> 579, bf16x3 451 -> 472; one image at a time f16 566 -> 555, bf16x3 372 -> 322 (the price: a launch is
-// longer).  One range for fc7 is the same throughput and 5-8 % more latency.  The fp32 InnerProducts keep the full cut (their loops
-// are 10x longer than their fixed costs: 266 -> 260 images/s with half the ranges).
-// FC_SPLIT_DIV (A/B): 0 = the full cut everywhere; otherwise the full cut divided by the low decimal digit (K > 8192) / the high
-// digit (K <= 8192; 0 = the low digit), fp32 included.
-inline int fc_split_div(const mnc_ctx* ctx, int splits, int K) {
-  const int v = tune(ctx, T_FC_SPLIT_DIV, 1), lo = v % 10, hi = (v / 10) % 10 ? (v / 10) % 10 : lo, top = (v / 100) % 10 ? (v / 100) % 10 : lo;
-  const int d = K <= 8192 ? hi : K > 50000 ? top : lo;      // (hundreds digit: K > 50000, fc6_maskest)
-  return d > 1 && splits > 1 ? (splits / d > 1 ? splits / d : 1) : splits;
-}
-inline int fc_lowp_ranges(const mnc_ctx* ctx, int splits, int K, int tiles, bool pair = false) {
-  if (tune_set(ctx, T_FC_SPLIT_DIV)) return fc_split_div(ctx, splits, K);
-  if (plan_latency(ctx)) return splits;
-  // pairs (fc6 + fc6_mask, fc7 + fc7_mask): ranges of >= 12288 K values -- 2 ranges for the fc6 pair, none for the fc7 pair (no
-  // partial sums, no reduction launch): with the images in flight on 16 hardware queues (12 in flight) f16 1087 -> 1118 images/s,
-  // mixed 652 -> 660, bf16x3 506 -> 513; with four in flight 1078 -> 1072 / 638 -> 645 / 499 -> 499; no cut at all (32768): 1119 /
-  // 662 / 515 with twelve but 984 / 627 / 457 with four.  A single product (fc6_maskest: one column tile) keeps 2048.  FC_RANGE_K.
-  const int per = pair ? tune(ctx, T_FC_RANGE_K, 12288) : 2048, part = 128;
-  int r = K / per > 1 ? K / per : 1;
-  const int half = (part + tiles - 1) / tiles;
-  if (r > half) r = half;
-  return r < splits ? r : splits;
-}
+inline bool tune_set(const mnc_ctx* ctx, TuneKey k) { return tune_set(ctx->tune, k); }
+inline int tune(const mnc_ctx* ctx, TuneKey k, int dflt) { return tune(ctx->tune, k, dflt); }
+inline bool plan_latency(const mnc_ctx* ctx) { return plan_latency(ctx->tune); }
+#ifdef MNC_TUNING
+constexpr bool kTuningBuild = true;       // the ablation and superseded kernels are compiled in; plans may have to make room for them
+#else
+constexpr bool kTuningBuild = false;
+#endif
 }  // namespace mnc
 
 namespace mnc {
@@ -170,6 +127,18 @@ void prof_end(mnc_ctx* ctx);
     }                                \
   } while (0)
 
+// Raises a kernel's dynamic-LDS limit the first time the kernel is launched on a device (function attributes are per device): one
+// bitmask per kernel instantiation, one bit per device.
+template <auto kKernel>
+inline hipError_t lds_limit_once(int device, int bytes) {
+  static std::atomic<unsigned long long> done{0};
+  const unsigned long long bit = 1ull << (device & 63);
+  if (done.load(std::memory_order_relaxed) & bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+  return e;
+}
+
 // RAII bracket: records a HIP event pair around the kernels launched inside its scope when profiling is on, and
 // turns a failed launch into MNC_ERR_HIP.
 struct LaunchScope {
@@ -190,27 +159,6 @@ struct LaunchScope {
     return MNC_OK;
   }
 };
-
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
-// K-split count of a GEMM whose `tiles` output tiles do not fill the chip on their own, by a small cost model instead of
-// "tiles x splits ~ #CUs": workgroups run in rounds of `slots` (the CUs x workgroups per CU), a split of `per` stages costs
-// per * stage_us, and every split adds a pass over the M x N partial sums (mn_bytes each way at ~3 TB/s) to the reduction.
-// Used when there are several row blocks (M > one block: the CFM / ResNet configurations), where rounding the split count up
-// could leave a second, nearly empty round (96 tiles x 3 splits = 288 workgroups on 256 CUs: 72 instead of 100 TFLOP/s).
-static inline int choose_splits(int tiles, int stages, int min_stages, int slots, double stage_us, double mn_bytes) {
-  int best = 1;
-  double best_cost = 1e300;
-  const int smax = stages / min_stages > 1 ? stages / min_stages : 1;
-  for (int s = 1; s <= smax && s <= 1024; ++s) {
-    const int per = cdiv(stages, s);
-    if (cdiv(stages, per) != s) continue;                    // this count is not reachable after rounding `per` up
-    const double rounds = (double)cdiv((long)tiles * s, slots);
-    const double cost = rounds * per * stage_us + (s > 1 ? 3.0 + 2.0 * s * mn_bytes / 3.0e6 : 0.0);
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
 
 // XCD-aware block order for the GEMMs.  The dispatcher places block b on XCD b % 8 (observed, used for speed only:
 // a different placement changes nothing but L2 hit rates).  Blocks are re-numbered so that each XCD receives a

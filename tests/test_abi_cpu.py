@@ -175,7 +175,7 @@ def test_tuning_values_are_per_context_and_checked():
     """mnc_ctx_set_tuning is declared and exported; keys are validated by name (no context needed to check the table)."""
     d = _lib.parse_header()
     assert d["mnc_ctx_set_tuning"][2] == ["ctx", "name", "value"]
-    src = open(os.path.join(REPO, "mnc_amd", "csrc", "mnc_internal.h")).read()
+    src = open(os.path.join(REPO, "mnc_amd", "csrc", "tune.h")).read()      # (the key table; mnc_internal.h includes it)
     for key in ("FC_TILE", "FC_HALF", "FCX3_WIDE", "WINO_ROWS", "ROI_WARP_VARIANT", "TOPK_SINGLE_WG"):
         assert "X(%s)" % key in src
     # no launch path reads the environment: getenv appears in ctx.hip (context creation) only
