@@ -190,6 +190,50 @@ MNC_API int mnc_render_instances(const double* boxes, const float* masks, const 
                                  int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n5  The instances themselves: one binary mask per instance at image resolution, one bit per pixel (csrc/inst_masks.hip) --
+ *     the rule of _convert_pred_to_image (clip = 1) and of voc_eval_sds (clip = 0, lib/utils/voc_eval.py:197-199) without the
+ *     painting over one another resp. the counting against ground truth that follow it there.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* One instance of mnc_mask_records / mnc_net_masks (64 bytes).  Its mask is h = y2 - y1 + 1 rows of ceil(w / 64) little-endian
+ * 64-bit words, w = x2 - x1 + 1, at byte `offset` of the bits: bit dx % 64 of word dx / 64 of row dy is pixel (x1 + dx, y1 + dy),
+ * padding bits are 0 -- np.unpackbits(rows.view(np.uint8), axis=1, bitorder='little')[:, :w]; the first ceil(w / 8) bytes of a
+ * row are utils.voc_eval.pack_sds_gt's row.  x2 < x1 or y2 < y1 (mnc_mask_records only): no rows. */
+typedef struct mnc_mask_info {
+  int x1, y1, x2, y2;   /* the rounded (and clipped) box: the bounds of the mask */
+  int cls;              /* the record's class id */
+  float score;          /* the record's score */
+  int row;              /* row of the record array */
+  int reserved0;
+  long long offset;     /* byte offset of the first row; a multiple of 8, instances follow one another without gaps */
+  long long area;       /* set bits */
+  long long work;       /* the pack kernel's own (first work item of the instance) */
+  long long reserved1;
+} mnc_mask_info;
+/* What stands in front of the mnc_mask_info array: 256 bytes. */
+typedef struct mnc_mask_head {
+  int kept;             /* instances */
+  int reserved0;
+  long long bits_bytes; /* bytes of all masks */
+  long long items;      /* the pack kernel's own */
+  long long reserved1[29];
+} mnc_mask_head;
+/* Host pointers, one call per image.  boxes [n][4] float64 (x1, y1, x2, y2), masks [n][mask_size^2] float32.  Per instance i:
+ * every coordinate is rounded half to even (np.round); with clip = 1 it is then clipped to [0, W-1] / [0, H-1] exactly as
+ * _convert_pred_to_image does, with clip = 0 (the evaluation's rule) nothing more happens, the bounds may leave the image and H, W
+ * are not looked at.  w = x2 - x1 + 1, h = y2 - y1 + 1; pixel (dy, dx) of the mask is set when cv2.resize(mask, (w, h)),
+ * INTER_LINEAR, is >= float32(binarize_thresh) there.  Outputs: bounds [n][4] int, offsets [n] (bytes into bits, each a multiple
+ * of 8, in order without gaps), areas [n] (set bits), the rows of every instance in bits (layout: mnc_mask_info above),
+ * *bits_bytes = the bytes they take.  bounds, offsets and *bits_bytes follow from the boxes alone and are computed on the host
+ * before anything is launched: with bits == NULL the call returns them and launches nothing (masks and areas may be NULL then).
+ * n == 0 returns before any device work (*bits_bytes = 0).  Bit-identical to utils.blob.resize_to(...) >= float32(thresh).
+ * MNC_ERR_INVALID, checked before anything is launched: mask_size outside [1, 32], a rounded |coordinate| >= 2^24, more than
+ * 2^26 pixels in one box, clip = 1 with H or W outside [1, 32768], bits_cap < *bits_bytes, and any rounded (and clipped) box with
+ * x2 < x1 or y2 < y1 (cv2.resize raises on it; the rule of mnc_render_instances). */
+MNC_API int mnc_instance_masks(const double* boxes, const float* masks, int n, int mask_size, double binarize_thresh,
+                               int image_height, int image_width, int clip, int* bounds, long long* offsets, long long* areas,
+                               void* bits, size_t bits_cap, size_t* bits_bytes, int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */
@@ -687,6 +731,21 @@ MNC_API int mnc_render_records(mnc_ctx* ctx, const float* d_records, const int* 
                                int mask_size, double vis_thresh, double binarize_thresh, int H, int W,
                                const unsigned char* d_bgr_hwc, float alpha, int* d_inst, int* d_cls, unsigned char* d_inst_rgb,
                                unsigned char* d_cls_rgb, unsigned char* d_overlay_rgb, int* d_kept);
+/* mnc_instance_masks of the records of mnc_vote_instances, everything on the device, asynchronous on ctx's stream, no host
+ * read-back: exactly the rows mnc_render_records keeps at vis_thresh = score_thresh -- the rows [0, min(d_counts[0], record_cap))
+ * of d_records with (double)score >= score_thresh -- in record order, always with clip = 1.  A first kernel (one workgroup) derives
+ * the bounds, the byte sizes and their exclusive prefix; the pack kernel follows it.  As there, a rounded, clipped box with
+ * x2 < x1 or y2 < y1 is not an error: it keeps its place and has no rows (area 0).
+ *   *d_info   device address of [mnc_mask_head | mnc_mask_info[record_cap]], kept entries valid: ONE copy of 256 + 64 * rows bytes
+ *             brings the count, bounds, offsets, areas, classes and scores down
+ *   *d_bits   device address of the masks, head.bits_bytes bytes (a second copy).  d_bits == NULL: sizes only -- the first kernel
+ *             alone runs, every area is 0
+ * Both live in an arena of the context (in no captured graph) that holds record_cap * H * 8 * ceil(W / 64) bytes of bits, which
+ * always suffice for clipped boxes, and stay valid until the next call on this context.  Limits: mask_size <= 32,
+ * num_classes <= 256, H and W in [1, 32768]. */
+MNC_API int mnc_mask_records(mnc_ctx* ctx, const float* d_records, const int* d_counts, int record_cap, int num_classes,
+                             int mask_size, double score_thresh, double binarize_thresh, int H, int W, void** d_info,
+                             void** d_bits);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */
@@ -791,6 +850,15 @@ MNC_API int mnc_net_fetch(mnc_net* net, float* records_host, int record_cap, int
 MNC_API int mnc_net_render(mnc_net* net, double vis_thresh, double binarize_thresh, float alpha, int* inst_host, int* cls_host,
                            unsigned char* inst_rgb_host, unsigned char* cls_rgb_host, unsigned char* overlay_rgb_host,
                            int* kept_host);
+/* mnc_mask_records of the LAST image of the net into host memory, beside mnc_net_render: waits for the image, packs on the net's
+ * stream behind it (never inside the captured graph, which stays as it is, as does a following mnc_net_fetch), waits again and
+ * copies out.  The image's row count is known on the host by then, so the context's arena is sized for those rows only.
+ * info_host receives [mnc_mask_head | mnc_mask_info[kept]] (256 + 64 * info_cap bytes of room; info_cap below the image's rows is
+ * MNC_ERR_INVALID -- (num_classes - 1) * max_per_image always suffices), bits_host the head.bits_bytes bytes of the masks,
+ * *bits_bytes (may be NULL) that number.  bits_host == NULL: sizes only (mnc_mask_records without d_bits); bits_cap below the
+ * bytes needed is MNC_ERR_INVALID.  MNC_ERR_STATE when no image has been forwarded on this net. */
+MNC_API int mnc_net_masks(mnc_net* net, double score_thresh, double binarize_thresh, void* info_host, int info_cap,
+                          void* bits_host, size_t bits_cap, size_t* bits_bytes);
 /* Device address and Caffe-order shape of an intermediate blob of the LAST image, for parity tests: "conv5_3" (c8),
  * "rpn_cls_prob_reshape", "rpn_bbox_pred", "rois", "rois_ext", "mask_proposal" [2R][S][S] (both stages stacked),
  * "seg_cls_prob" [2R][num_classes], "boxes" [2R][4], "head_scores" [2R][6*num_classes] = [cls_score | seg_cls_score | bbox_pred]

@@ -185,6 +185,7 @@ int mnc_ctx_destroy(mnc_ctx* ctx) {
   if (ctx->proposal) mnc::proposal_state_free(ctx->proposal);
   arena_free(&ctx->vote_ws);
   arena_free(&ctx->render_ws);
+  arena_free(&ctx->mask_ws);
   if (ctx->tickets) (void)hipFree(ctx->tickets);
   if (ctx->comm) mnc::comm_free(ctx);
   (void)hipStreamDestroy(ctx->stream);

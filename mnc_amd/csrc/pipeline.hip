@@ -1036,6 +1036,41 @@ int mnc_net_render(mnc_net* net, double vis_thresh, double binarize_thresh, floa
   return MNC_OK;
 }
 
+int mnc_net_masks(mnc_net* net, double score_thresh, double binarize_thresh, void* info_host, int info_cap, void* bits_host,
+                  size_t bits_cap, size_t* bits_bytes) {
+  MNC_REQUIRE(net && info_host && info_cap >= 0, "mnc_net_masks: null pointer");
+  if (net->H <= 0) {
+    set_error("mnc_net_masks: no image has been forwarded on this net");
+    return MNC_ERR_STATE;
+  }
+  const mnc_net_config& c = net->cfg;
+  mnc_ctx* ctx = net->ctx;
+  MNC_HIP_TRY(hipSetDevice(ctx->device));
+  MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  net->in_flight = false;            // the staged image has been consumed (mnc_net_fetch needs no image in flight)
+  if (*(const int*)((const char*)net->pin_out + 256) < c.post_nms_topn) {
+    // fewer proposals than post_nms_topn: the record block is final only after the re-run mnc_net_fetch makes (idempotent)
+    NET_TRY(run_heads_and_vote(net, *(const int*)((const char*)net->pin_out + 256)));
+    NET_TRY(enqueue_outputs(net));
+    MNC_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  const int cap = (c.num_classes - 1) * c.max_per_image, R = *(const int*)net->pin_out;
+  const int rows = R < 0 ? 0 : R < cap ? R : cap;
+  MNC_REQUIRE(info_cap >= rows, "mnc_net_masks: info_cap %d is below the image's %d instances", info_cap, rows);
+  void* d_info = nullptr; void* d_bits = nullptr;
+  NET_TRY(mnc_mask_records(ctx, net->records(), net->counts(), rows, c.num_classes, c.mask_size, score_thresh, binarize_thresh,
+                           net->H, net->W, &d_info, bits_host ? &d_bits : nullptr));
+  NET_TRY(mnc_d2h(ctx, info_host, d_info, sizeof(mnc_mask_head) + (size_t)rows * sizeof(mnc_mask_info)));
+  const size_t need = (size_t)((const mnc_mask_head*)info_host)->bits_bytes;
+  if (bits_bytes) *bits_bytes = need;
+  if (bits_host) {
+    MNC_REQUIRE(bits_cap >= need, "mnc_net_masks: bits_cap %zu is below the %zu bytes of the masks", bits_cap, need);
+    if (need) NET_TRY(mnc_d2h(ctx, bits_host, d_bits, need));
+  }
+  clear_error();
+  return MNC_OK;
+}
+
 int mnc_forward_image(mnc_net* net, const unsigned char* bgr_host, int H, int W, float* records_host, int record_cap,
                       int* counts_host) {
   MNC_REQUIRE(net && records_host && counts_host && record_cap >= 0, "mnc_forward_image: null pointer");

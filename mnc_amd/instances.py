@@ -146,6 +146,18 @@ class InstanceView(object):
         return blk._renderer.render(self.records_ptr, self.counts_ptr, self.rows_cap, self.num_classes, self.S, H, W, vis_thresh,
                                     binarize_thresh, image, alpha)
 
+    def masks(self, H, W, score_thresh=0.0, binarize_thresh=None):
+        """One binary mask per instance scoring >= score_thresh at the resolution of the H x W image, packed one bit per pixel,
+        straight from the device records (mnc_mask_records; no lists() / resize loop): -> a PackedMasks (mnc_amd/masks.py) with
+        .bounds, .offsets, .areas, .classes, .scores and .bits as lazily copied arrays -- the rows and order render() keeps at
+        vis_thresh = score_thresh, the boxes clipped to the image.  The image's row count is read first (head(): a 256-byte copy
+        that waits for the voting), so that the context's bit buffer is sized for these rows and not for the block's capacity;
+        the result's buffers are reused by the next masks() on this net."""
+        from .masks import records_masks
+        rows = min(max(int(self.head()[0]), 0), self.rows_cap)
+        return records_masks(self._blk._net._ctx, self.records_ptr, self.counts_ptr, rows, self.num_classes, self.S, H, W,
+                             score_thresh, binarize_thresh)
+
 
 def split_records(rec, class_counts, S):
     boxes = np.hstack((rec[:, :4].astype(np.int32), rec[:, 4:5]))          # int32 | float32 -> float64, as the reference

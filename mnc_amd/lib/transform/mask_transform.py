@@ -2,7 +2,9 @@
 
 Host orchestration only: 20 per-class NMS calls (HIP), a global score threshold, one IoU row per surviving box, then a
 single call into the fused HIP mask-voting kernels (nms.mv.mv).  The reference's cv2-based cpu_mask_voting (image-space voting,
-cfg.TEST.USE_GPU_MASK_MERGE = False) runs on the GPU as well: cpu_mask_voting below (csrc/mv_image.hip)."""
+cfg.TEST.USE_GPU_MASK_MERGE = False) runs on the GPU as well: cpu_mask_voting below (csrc/mv_image.hip).  instance_masks turns the
+voted instances into per-instance binary masks at image resolution on the GPU (csrc/inst_masks.hip); instance_masks_numpy is the
+same rule as a plain loop on the host."""
 import numpy as np
 
 from mnc_config import cfg
@@ -199,3 +201,18 @@ def cpu_mask_voting(masks, boxes, scores, num_classes, max_per_image, im_width, 
     R = R.value
     rec = np.hstack((out_box[:R].astype(np.float32), out_score[:R, None], np.zeros((R, 1), np.float32), out_mask[:R]))
     return _image_voting_lists(rec, counts, S)
+
+
+def instance_masks(boxes, masks, im_h, im_w, clip=True, binarize_thresh=None, classes=None, scores=None):
+    """Per-instance binary masks at image resolution on the GPU (mnc_instance_masks): boxes [n, 4 or 5], masks [n, S, S] or
+    [n, 1, S, S] -> mnc_amd.masks.PackedMasks.  Each box is rounded half to even and, with clip=True, clipped to the image
+    (utils/vis_seg.py:_convert_pred_to_image; clip=False is utils/voc_eval.py:voc_eval_sds's rule); the mask is resized to it with
+    cv2's INTER_LINEAR rule and binarised with >= float32(cfg.BINARIZE_THRESH)."""
+    from mnc_amd.masks import instance_masks as device_masks
+    return device_masks(boxes, masks, im_h, im_w, clip, binarize_thresh, classes, scores, cfg.GPU_ID)
+
+
+def instance_masks_numpy(boxes, masks, im_h, im_w, clip=True, binarize_thresh=None, classes=None, scores=None):
+    """instance_masks as the plain utils.blob.resize_to loop on the host: the CPU statement of the rule, the same PackedMasks."""
+    from mnc_amd.masks import instance_masks_numpy as host_masks
+    return host_masks(boxes, masks, im_h, im_w, clip, binarize_thresh, classes, scores)

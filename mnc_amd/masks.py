@@ -1,0 +1,264 @@
+"""Per-instance binary masks at image resolution, one bit per pixel (include/mnc_hip.h n5, csrc/inst_masks.hip): what every
+consumer of a voted instance makes first -- round the box, resize the S x S mask to it with cv2's INTER_LINEAR rule, binarise.
+
+    PackedMasks                     the masks of one image: .bounds int32 [n, 4] (x1, y1, x2, y2 of the rounded box), .offsets
+                                    int64 [n] (bytes into .bits), .areas int64 [n] (set pixels), .classes int32 [n], .scores
+                                    float32 [n], .bits uint64 [...]; .dense(i), .full(i, H, W), .as_sds_gt(i)
+    instance_masks(...)             host arrays -> PackedMasks through mnc_instance_masks (the GPU)
+    instance_masks_numpy(...)       the same object from the plain utils.blob.resize_to loop: the CPU statement of the rule
+    records_masks(...)              device-resident instance records -> PackedMasks through mnc_mask_records, copied on first access
+
+Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
+pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
+fallback: without the library or a GPU the device functions raise."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+HEAD_BYTES = 256
+# mnc_mask_head / mnc_mask_info of include/mnc_hip.h
+HEAD = np.dtype({"names": ["kept", "bits_bytes"], "formats": ["<i4", "<i8"], "offsets": [0, 8], "itemsize": HEAD_BYTES})
+INFO = np.dtype({"names": ["bounds", "cls", "score", "row", "offset", "area"],
+                 "formats": [("<i4", 4), "<i4", "<f4", "<i4", "<i8", "<i8"], "offsets": [0, 16, 20, 24, 32, 40], "itemsize": 64})
+MAX_MASK = 32
+MAX_COORD = 2 ** 24
+MAX_AREA = 2 ** 26
+MAX_SIDE = 32768
+
+
+class PackedMasks(object):
+    """The packed masks of one image.  Made from host arrays, or from a device result whose arrays are copied on first access
+    (the instance table in one copy, the bits in a second) and kept; a device result that was never read refuses a later image's."""
+    FIELDS = ("bounds", "offsets", "areas", "classes", "scores", "bits")
+
+    def __init__(self, bounds=None, offsets=None, areas=None, classes=None, scores=None, bits=None, source=None):
+        self._host = {}
+        self._source = source
+        if source is None:
+            n = len(bounds)
+            self._host = {"bounds": np.ascontiguousarray(bounds, np.int32).reshape(n, 4),
+                          "offsets": np.ascontiguousarray(offsets, np.int64).reshape(n),
+                          "areas": np.ascontiguousarray(areas, np.int64).reshape(n),
+                          "classes": np.ascontiguousarray(np.zeros(n) if classes is None else classes, np.int32).reshape(n),
+                          "scores": np.ascontiguousarray(np.zeros(n) if scores is None else scores, np.float32).reshape(n),
+                          "bits": np.ascontiguousarray(bits, np.uint64).reshape(-1)}
+
+    def __getattr__(self, name):
+        if name.startswith("_") or name not in self.FIELDS:       # (also an object whose __init__ has not run)
+            raise AttributeError(name)
+        if name not in self._host:
+            self._source.load(self._host, name == "bits")
+        return self._host[name]
+
+    def fetch(self):
+        """Copy everything now (so that it outlives the next image's masks); -> self."""
+        for name in self.FIELDS:
+            getattr(self, name)
+        return self
+
+    def __len__(self):
+        return len(self.bounds)
+
+    def size(self, i):
+        """-> (h, w) of instance i."""
+        x1, y1, x2, y2 = (int(v) for v in self.bounds[i])
+        return max(y2 - y1 + 1, 0), max(x2 - x1 + 1, 0)
+
+    def _rows(self, i):
+        h, w = self.size(i)
+        if h == 0 or w == 0:
+            return np.zeros((h, 0), np.uint8), w
+        strips = (w + 63) // 64
+        lo = int(self.offsets[i]) // 8
+        return self.bits[lo:lo + h * strips].view(np.uint8).reshape(h, strips * 8), w
+
+    def dense(self, i):
+        """bool [h, w]: the mask of instance i inside its bounds."""
+        rows, w = self._rows(i)
+        return np.unpackbits(rows, axis=1, bitorder="little")[:, :w].astype(bool)
+
+    def full(self, i, H, W):
+        """bool [H, W]: instance i in the image (what of it lies inside, when the bounds were not clipped)."""
+        out = np.zeros((int(H), int(W)), bool)
+        x1, y1, x2, y2 = (int(v) for v in self.bounds[i])
+        ax, ay, bx, by = max(x1, 0), max(y1, 0), min(x2, W - 1), min(y2, H - 1)
+        if ax <= bx and ay <= by:
+            out[ay:by + 1, ax:bx + 1] = self.dense(i)[ay - y1:by - y1 + 1, ax - x1:bx - x1 + 1]
+        return out
+
+    def as_sds_gt(self, i):
+        """uint8 [h, ceil(w / 8)]: the rows utils.voc_eval.pack_sds_gt makes of this mask (np.packbits(axis=1, bitorder='little')):
+        the leading bytes of the packed rows."""
+        rows, w = self._rows(i)
+        return np.ascontiguousarray(rows[:, :(w + 7) // 8])
+
+    def arrays(self):
+        """{name: array} of the six fields (what tools/demo.py --save-masks writes with np.savez)."""
+        return {name: getattr(self, name) for name in self.FIELDS}
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as f:
+            return cls(**{name: f[name] for name in cls.FIELDS})
+
+
+def _flat(boxes, masks):
+    boxes = np.asarray(boxes, np.float64)
+    boxes = boxes.reshape(-1, boxes.shape[-1] if boxes.ndim > 1 else 4)
+    n = boxes.shape[0]
+    masks = np.asarray(masks, np.float32)
+    S = int(masks.shape[-1]) if masks.ndim >= 2 and n else 0
+    return boxes, np.ascontiguousarray(masks.reshape(n, S * S)), n, S
+
+
+def from_lists(list_mask, list_box, score_thresh=0.0):
+    """(list_result_mask, list_result_box) of gpu_mask_voting -> (boxes [n, 5] float64, masks [n, S, S] float32, classes int32
+    [n]) of the instances with score >= score_thresh, class-major: the order and the rows tools/demo.py:get_vis_dict keeps."""
+    boxes, masks, classes = [], [], []
+    for c, (m, b) in enumerate(zip(list_mask, list_box)):
+        keep = np.where(np.asarray(b)[:, -1] >= score_thresh)[0] if len(b) else np.zeros(0, int)
+        boxes.append(np.asarray(b, np.float64).reshape(-1, 5)[keep])
+        mm = np.asarray(m, np.float32)
+        masks.append(mm.reshape(len(b), mm.shape[-1], mm.shape[-1])[keep] if len(b) else None)
+        classes.append(np.full(len(keep), c + 1, np.int32))
+    masks = [m for m in masks if m is not None]
+    S = masks[0].shape[-1] if masks else 0
+    return (np.concatenate(boxes) if boxes else np.zeros((0, 5)), np.concatenate(masks) if masks else np.zeros((0, S, S), np.float32),
+            np.concatenate(classes) if classes else np.zeros(0, np.int32))
+
+
+def _scores_of(boxes, scores):
+    if scores is not None:
+        return scores
+    return boxes[:, 4] if boxes.shape[1] >= 5 else None
+
+
+def instance_masks_numpy(boxes, masks, im_h, im_w, clip=True, binarize_thresh=None, classes=None, scores=None):
+    """The rule as a plain loop on the host: per instance np.round(box) (clipped to the image with clip=True, as
+    utils/vis_seg.py:_convert_pred_to_image; left alone with clip=False, as utils/voc_eval.py:voc_eval_sds),
+    utils.blob.resize_to(mask, w, h) >= float32(binarize_thresh), packed.  boxes [n, 4 or 5] (a fifth column is the score), masks
+    [n, S, S] or [n, 1, S, S] -> PackedMasks.  Raises ValueError where mnc_instance_masks returns MNC_ERR_INVALID."""
+    from mnc_config import cfg
+    from utils.blob import resize_to
+    thr = np.float32(cfg.BINARIZE_THRESH if binarize_thresh is None else binarize_thresh)
+    boxes, masks, n, S = _flat(boxes, masks)
+    if n and not 1 <= S <= MAX_MASK:
+        raise ValueError("instance_masks_numpy: mask_size %d not in [1, %d]" % (S, MAX_MASK))
+    if clip and not (1 <= im_h <= MAX_SIDE and 1 <= im_w <= MAX_SIDE):
+        raise ValueError("instance_masks_numpy: image %d x %d not in [1, %d]" % (im_h, im_w, MAX_SIDE))
+    bounds = np.zeros((n, 4), np.int32)
+    offsets, areas, words, nbytes = np.zeros(n, np.int64), np.zeros(n, np.int64), [], 0
+    for i in range(n):
+        r = np.round(boxes[i, :4])
+        if not (np.abs(r) < MAX_COORD).all():
+            raise ValueError("instance_masks_numpy: box %d out of range" % i)
+        b = r.astype(int)
+        if clip:
+            b = np.array([min(max(b[0], 0), im_w - 1), min(max(b[1], 0), im_h - 1), min(max(b[2], 0), im_w - 1),
+                          min(max(b[3], 0), im_h - 1)])
+        w, h = int(b[2] - b[0] + 1), int(b[3] - b[1] + 1)
+        if w < 1 or h < 1:
+            raise ValueError("instance_masks_numpy: box %d %s is empty once rounded (cv2.resize would raise)" % (i, boxes[i, :4]))
+        if w * h > MAX_AREA:
+            raise ValueError("instance_masks_numpy: box %d covers %d pixels (limit %d)" % (i, w * h, MAX_AREA))
+        m = resize_to(masks[i].reshape(S, S), w, h) >= thr
+        rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
+        rows[:, :(w + 7) // 8] = np.packbits(m, axis=1, bitorder="little")
+        bounds[i], offsets[i], areas[i] = b, nbytes, int(m.sum())
+        words.append(rows.reshape(-1).view(np.uint64))
+        nbytes += rows.size
+    bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
+    return PackedMasks(bounds, offsets, areas, classes, _scores_of(boxes, scores), bits)
+
+
+def instance_masks_call(boxes, masks, n, S, im_h, im_w, clip, binarize_thresh, bits=None, device_id=0):
+    """mnc_instance_masks as it is: boxes float64 [n, 4], masks float32 [n, S*S]; bits None asks for bounds, offsets and the size
+    only (nothing is launched).  -> (bounds, offsets, areas, bytes needed)."""
+    bounds, offsets, areas = np.zeros((n, 4), np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    need = ctypes.c_size_t(0)
+    _lib.call("mnc_instance_masks", _lib.ptr(boxes), _lib.ptr(masks), int(n), int(S), float(binarize_thresh), int(im_h), int(im_w),
+              int(bool(clip)), _lib.ptr(bounds), _lib.ptr(offsets), _lib.ptr(areas), _lib.ptr(bits),
+              bits.nbytes if bits is not None else 0, ctypes.addressof(need), int(device_id))
+    return bounds, offsets, areas, int(need.value)
+
+
+def instance_masks(boxes, masks, im_h, im_w, clip=True, binarize_thresh=None, classes=None, scores=None, device_id=None):
+    """instance_masks_numpy on the GPU (mnc_instance_masks, csrc/inst_masks.hip): same arguments, the same PackedMasks bit for bit.
+    Invalid boxes and sizes raise _lib.MncError (MNC_ERR_INVALID) before anything is launched."""
+    from mnc_config import cfg
+    thr = cfg.BINARIZE_THRESH if binarize_thresh is None else binarize_thresh
+    if device_id is None:
+        device_id = int(cfg.get("GPU_ID", 0))
+    boxes, masks, n, S = _flat(boxes, masks)
+    b4 = np.ascontiguousarray(boxes[:, :4])
+    S = S if n else int(cfg.MASK_SIZE)
+    _, _, _, need = instance_masks_call(b4, masks, n, S, im_h, im_w, clip, thr, None, device_id)
+    bits = np.zeros(need // 8, np.uint64)
+    bounds, offsets, areas, _ = instance_masks_call(b4, masks, n, S, im_h, im_w, clip, thr, bits, device_id)
+    return PackedMasks(bounds, offsets, areas, classes, _scores_of(boxes, scores), bits)
+
+
+def _from_info(raw, kept):
+    info = raw[HEAD_BYTES:HEAD_BYTES + kept * INFO.itemsize].view(INFO)
+    return {"bounds": np.ascontiguousarray(info["bounds"]), "offsets": np.ascontiguousarray(info["offset"]),
+            "areas": np.ascontiguousarray(info["area"]), "classes": np.ascontiguousarray(info["cls"]),
+            "scores": np.ascontiguousarray(info["score"])}
+
+
+class _DeviceResult(object):
+    """One mnc_mask_records result in the context's arena, which the next call on that context reuses."""
+    FIRST = 128                                 # instances the first copy brings along (max_per_image is 100)
+
+    def __init__(self, ctx, d_info, d_bits, rows):
+        self._ctx, self._gen = ctx, ctx._mask_gen
+        self.d_info, self.d_bits, self.rows = d_info, d_bits, int(rows)
+        self._bytes = None
+
+    def load(self, host, want_bits):
+        if self._ctx._mask_gen != self._gen:
+            raise RuntimeError("these masks' device buffers have been reused by a later masks() on this context (read them, or "
+                               ".fetch(), before the next image if they must outlive it)")
+        h = self._ctx.h
+        if self._bytes is None:
+            first = min(self.rows, self.FIRST)
+            raw = np.zeros(HEAD_BYTES + self.rows * INFO.itemsize, np.uint8)
+            _lib.call("mnc_d2h", h, _lib.ptr(raw), self.d_info, HEAD_BYTES + first * INFO.itemsize)
+            head = raw[:HEAD_BYTES].view(HEAD)[0]
+            kept = int(head["kept"])
+            if kept > first:
+                at = HEAD_BYTES + first * INFO.itemsize
+                _lib.call("mnc_d2h", h, raw[at:].ctypes.data, self.d_info + at, (kept - first) * INFO.itemsize)
+            host.update(_from_info(raw, kept))
+            self._bytes = int(head["bits_bytes"])
+        if want_bits:
+            bits = np.zeros(self._bytes // 8, np.uint64)
+            if bits.size:
+                _lib.call("mnc_d2h", h, _lib.ptr(bits), self.d_bits, bits.nbytes)
+            host["bits"] = bits
+
+
+def records_masks(ctx, records_ptr, counts_ptr, record_cap, num_classes, mask_size, H, W, score_thresh=0.0, binarize_thresh=None):
+    """Enqueue mnc_mask_records for the records at (records_ptr, counts_ptr) on the stream of `ctx` (an engine context object);
+    -> PackedMasks whose arrays are copied on first access."""
+    if binarize_thresh is None:
+        from mnc_config import cfg
+        binarize_thresh = cfg.BINARIZE_THRESH
+    d_info, d_bits = ctypes.c_void_p(), ctypes.c_void_p()
+    ctx._mask_gen = getattr(ctx, "_mask_gen", 0) + 1
+    _lib.call("mnc_mask_records", ctx.h, records_ptr, counts_ptr, int(record_cap), int(num_classes), int(mask_size),
+              float(score_thresh), float(binarize_thresh), int(H), int(W), ctypes.addressof(d_info), ctypes.addressof(d_bits))
+    return PackedMasks(source=_DeviceResult(ctx, d_info.value, d_bits.value, record_cap))
+
+
+def net_masks(net_handle, rows_cap, score_thresh, binarize_thresh):
+    """mnc_net_masks: the last image of a native net -> PackedMasks on the host (a sizes-only call, then the call with room)."""
+    raw = np.zeros(HEAD_BYTES + int(rows_cap) * INFO.itemsize, np.uint8)
+    need = ctypes.c_size_t(0)
+    _lib.call("mnc_net_masks", net_handle, float(score_thresh), float(binarize_thresh), _lib.ptr(raw), int(rows_cap), None, 0,
+              ctypes.addressof(need))
+    bits = np.zeros(need.value // 8, np.uint64)
+    _lib.call("mnc_net_masks", net_handle, float(score_thresh), float(binarize_thresh), _lib.ptr(raw), int(rows_cap),
+              _lib.ptr(bits) if bits.size else None, bits.nbytes, ctypes.addressof(need))
+    return PackedMasks(bits=bits, **_from_info(raw, int(raw[:HEAD_BYTES].view(HEAD)[0]["kept"])))

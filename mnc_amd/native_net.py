@@ -194,6 +194,13 @@ class NativeNet(object):
         out["kept"] = int(kept.value)
         return out
 
+    def masks(self, score_thresh=0.0, binarize_thresh=0.4):
+        """One packed binary mask per instance of the LAST image scoring >= score_thresh, at image resolution, boxes clipped to
+        the image (mnc_net_masks: the net's own records, on its stream behind the image, outside the captured graph): -> a
+        PackedMasks (mnc_amd/masks.py) on the host.  A following fetch() / forward_image() is not disturbed."""
+        from .masks import net_masks
+        return net_masks(self.h, self.rows_cap, score_thresh, binarize_thresh)
+
     def detect(self, im):
         """-> (list_result_mask, list_result_box) as the reference's gpu_mask_voting returns them."""
         counts, rec = self.forward_image(im)
@@ -285,12 +292,14 @@ class ImageStream(object):
         for counts, records in stream.map(images): ...
     """
 
-    def __init__(self, weights, in_flight=8, voting="mv", render=False, render_args=None, **kwargs):
+    def __init__(self, weights, in_flight=8, voting="mv", render=False, render_args=None, masks=False, masks_args=None, **kwargs):
         """render=True: every result is (counts, records, rendering) with rendering = NativeNet.render(**render_args) of that
-        image, made when the image is drained (on its own net's stream, so the other images in flight keep running)."""
+        image, made when the image is drained (on its own net's stream, so the other images in flight keep running).
+        masks=True: every result ends with that image's own PackedMasks = NativeNet.masks(**masks_args), made the same way."""
         if in_flight < 1:
             raise ValueError("in_flight must be >= 1")
         self._render = dict(render_args or {}) if render else None
+        self._masks = dict(masks_args or {}) if masks else None
         vote = {"voting": voting}
         if "binarize_thresh" in kwargs:
             vote["binarize_thresh"] = kwargs.pop("binarize_thresh")
@@ -301,9 +310,11 @@ class ImageStream(object):
 
     def _take(self, net, record_cap):
         res = net.fetch(record_cap)
-        if self._render is None:
-            return res
-        return res + (net.render(**self._render),)
+        if self._render is not None:
+            res = res + (net.render(**self._render),)
+        if self._masks is not None:
+            res = res + (net.masks(**self._masks),)
+        return res
 
     def submit(self, im, record_cap=None):
         """Launch `im`; -> (counts, records) of the OLDEST image in flight when every net is busy, else None."""

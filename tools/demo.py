@@ -4,10 +4,12 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
+                         [--save-masks DIR]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
-`--cpu` is accepted and ignored, exactly as in the reference (demo.py:40-42 vs :126)."""
+`--cpu` is accepted and ignored by the network, exactly as in the reference (demo.py:40-42 vs :126); with --save-masks it selects
+the numpy form of the per-instance masks (transform.mask_transform.instance_masks_numpy) instead of the GPU's."""
 import argparse
 import os
 import time
@@ -38,6 +40,9 @@ def parse_args(argv=None):
                    help="score threshold of the drawn instances [0.5, the reference's constant, demo.py:103]")
     p.add_argument("--device-vis", dest="device_vis", action="store_true",
                    help="render the class image and its blend over the photo on the GPU (cfg.TEST.USE_GPU_VIS)")
+    p.add_argument("--save-masks", dest="save_masks", default=None, metavar="DIR",
+                   help="write <image>_masks.npz per image: one binary mask per instance scoring >= --vis-thresh at image "
+                        "resolution, packed one bit per pixel (the arrays of mnc_amd.masks.PackedMasks)")
     return p.parse_args(argv)
 
 
@@ -136,6 +141,24 @@ def _visualise(im_bgr, pred, out_path, view=None, vis_thresh=0.5):
     plt.close(fig)
 
 
+def _save_masks(out_dir, name, im_shape, result_mask, result_box, view=None, score_thresh=0.5, cpu=False):
+    """The instances scoring >= score_thresh as per-instance binary masks at image resolution -> <out_dir>/<name>_masks.npz
+    (mnc_amd.masks.PackedMasks.load reads it back).  From the device records of `view` (InstanceView.masks, csrc/inst_masks.hip) or
+    else from the lists, on the GPU; cpu=True: the numpy loop, with the same arrays."""
+    from mnc_amd.masks import from_lists
+    from transform.mask_transform import instance_masks, instance_masks_numpy
+    h, w = im_shape[:2]
+    if view is not None and not cpu:
+        packed = view.masks(h, w, score_thresh=score_thresh)
+    else:
+        bxs, mks, classes = from_lists(result_mask, result_box, score_thresh)
+        packed = (instance_masks_numpy if cpu else instance_masks)(bxs, mks, h, w, clip=True, classes=classes)
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, name + "_masks.npz")
+    np.savez(out, **packed.arrays())
+    return out, packed
+
+
 def build_net(args):
     from mnc_amd import models, synth
     prototxt = args.prototxt or models.write_mnc_5stage_test_prototxt()
@@ -177,6 +200,13 @@ def main(argv=None):
         print("mask voting time %f" % (time.time() - start))
         pred = get_vis_dict(result_box, result_mask, path or "synthetic", CLASSES, args.vis_thresh)
         print("%d instances with score >= %g" % (len(pred["boxes"]), args.vis_thresh))
+        if args.save_masks:
+            from mnc_amd.devarray import DeviceArray
+            blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
+            name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
+            out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, blk.view() if blk is not None else None,
+                                      args.vis_thresh, args.cpu_mode)
+            print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
         if args.vis and path:
             out = os.path.splitext(path)[0] + "_mnc.png"
             if args.out_dir:

@@ -18,6 +18,12 @@ Seeded synthetic weights, pixels and proposals.  Prints wall time per image and 
                (InstanceView.render, csrc/render.hip, with the copy of one int32 label map and the RGB overlay to the host);
                medians over --iters images, one JSON line.  Synthetic weights give meaningless scores, so the threshold is the
                score of the --vis-keep'th best instance unless --vis-thresh is given.
+
+  --task seg --masks   instead: one binary mask per instance at image resolution (the instances a consumer exports, scores or
+               crops with), in host form (InstanceView.lists() + transform.mask_transform.instance_masks_numpy: the fetch of the
+               records and the resize loop) against device form (InstanceView.masks(), csrc/inst_masks.hip, with the copy of the
+               instance table and the packed bits to the host), on a 600x1000 and a 375x500 synthetic image; the two forms
+               alternate, medians over --iters rounds after one warm-up round, one JSON line.  Threshold as for --vis.
 """
 import argparse
 import json
@@ -42,11 +48,12 @@ def main():
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--vis", action="store_true", help="--task seg: time the visualisation tail, host form against device form")
+    ap.add_argument("--masks", action="store_true", help="--task seg: time the per-instance masks, host form against device form")
     ap.add_argument("--vis-thresh", type=float, default=None)
     ap.add_argument("--vis-keep", type=int, default=40)
     args = ap.parse_args()
-    if args.vis and args.task != "seg":
-        ap.error("--vis goes with --task seg")
+    if (args.vis or args.masks) and args.task != "seg":
+        ap.error("--vis / --masks go with --task seg")
     resnet = args.task == "resnet"
     if resnet:
         args.task = "seg"
@@ -103,6 +110,8 @@ def main():
 
         if args.vis:
             return vis_tail(args, t, body, imread(Imdb().image_path_at(0)))
+        if args.masks:
+            return masks_tail(args, t, body, Imdb().image_path_at(0))
         calls = []
         real = t.net.forward
 
@@ -188,6 +197,46 @@ def vis_tail(args, t, body, im):
                       "device_with_photo_upload_ms_median": ms["device_with_upload"][0],
                       "device_outputs_copied": "cls int32 [H,W] + overlay uint8 [H,W,3]",
                       "note": "device: photograph already on the GPU (as NativeNet's staged image is); with_photo_upload adds its H2D copy"}))
+    t.net.close()
+
+
+def masks_tail(args, t, body, image_path):
+    from mnc_amd.masks import PackedMasks, from_lists
+    from transform.mask_transform import instance_masks_numpy
+    sizes = []
+    for H, W in ((600, 1000), (375, 500)):
+        np.save(image_path, np.random.default_rng(H).integers(0, 256, (H, W, 3), dtype=np.uint8))
+        result_mask, result_box = body()                             # warm-up; the records every timed round turns into masks
+        scores = np.sort(np.concatenate([b[:, 4] for b in result_box]))[::-1]
+        thr = args.vis_thresh if args.vis_thresh is not None else float(scores[min(args.vis_keep, len(scores)) - 1])
+        blk = t.net._inst
+
+        def host():
+            blk._host = None                                         # a fresh copy of the records, as for a new image
+            list_mask, list_box = blk.view().lists()
+            bxs, mks, classes = from_lists(list_mask, list_box, thr)
+            return instance_masks_numpy(bxs, mks, H, W, clip=True, classes=classes)
+
+        def device():
+            return blk.view().masks(H, W, score_thresh=thr).fetch()
+
+        want, got = host(), device()
+        same = all(np.array_equal(getattr(want, f), getattr(got, f)) for f in PackedMasks.FIELDS)
+        ms = {"host": [], "device": []}
+        for _ in range(max(args.iters, 1)):
+            for name, fn in (("host", host), ("device", device)):
+                t.net.sync()
+                t0 = time.perf_counter()
+                fn()
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+        med = {k: round(sorted(v)[len(v) // 2], 3) for k, v in ms.items()}
+        sizes.append({"image": "%dx%d" % (H, W), "kept": len(want), "score_thresh": thr, "pixels_in_boxes": int(sum(
+            want.size(i)[0] * want.size(i)[1] for i in range(len(want)))), "bits_bytes": int(want.bits.nbytes),
+            "device_equals_host": bool(same), "host_ms_median": med["host"], "host_ms_min": round(min(ms["host"]), 3),
+            "device_ms_median": med["device"], "device_ms_min": round(min(ms["device"]), 3)})
+    print(json.dumps({"workload": "per-instance binary masks of mnc 5-stage vgg16's voted instances at image resolution",
+                      "rounds": max(args.iters, 1), "host": "InstanceView.lists() + instance_masks_numpy",
+                      "device": "InstanceView.masks() + copy of the instance table and the packed bits", "sizes": sizes}))
     t.net.close()
 
 
