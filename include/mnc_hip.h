@@ -234,6 +234,41 @@ MNC_API int mnc_instance_masks(const double* boxes, const float* masks, int n, i
                                void* bits, size_t bits_cap, size_t* bits_bytes, int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n6  Comparing the instances: the mask IoU of every pair of two sets of packed masks, and the greedy mask NMS built on it
+ *     (csrc/mask_overlaps.hip) -- the rule of transform.mask_transform.mask_overlap (lib/transform/mask_transform.py:16-46)
+ *     on the layout of n5, without unpacking a mask.  The forms that read a device-resident mnc_mask_records result
+ *     (mnc_mask_overlaps_dev, mnc_mask_nms_dev) stand beside that entry below.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  Two sets A (na instances) and B (nb) in the same image frame, each given as n5 gives them: bounds [n][4] int
+ * (x1, y1, x2, y2), offsets [n] (bytes into bits), areas [n], bits (h rows of ceil(w / 64) little-endian 64-bit words per
+ * instance, layout: mnc_mask_info above), *_bytes = the bytes bits holds.  b_bits == NULL: B is A (the other b arguments and nb
+ * are not looked at).  For every pair (a, b):
+ *   ix1 = max(ax1, bx1), iy1 = max(ay1, by1), ix2 = min(ax2, bx2), iy2 = min(ay2, by2); ix1 > ix2 or iy1 > iy2: inter = 0 and
+ *   iou = 0.0.  Otherwise inter = the pixels of that rectangle set in both masks, union = a_areas[a] + b_areas[b] - inter (the
+ *   areas as given: the reference takes mask.sum() of what it is handed), iou = union < 1 ? 0.0 : (double)inter / (double)union.
+ *   An instance without rows (x2 < x1 or y2 < y1) gives 0 / 0.0 against everything.  Bounds may leave the image (clip = 0);
+ *   pixels outside it count like any others.  Padding bits are not trusted: a bit at column >= w of either operand is never
+ *   counted, whatever it holds.
+ * Outputs inter [na][nb] and iou [na][nb], row-major; either may be NULL.  With the areas the true bit counts every element
+ * equals mask_overlap(A.bounds[a], B.bounds[b], A.dense(a), B.dense(b)) bit for bit (its int 0 read as 0.0).  na == 0 or nb == 0
+ * returns before any device work.  MNC_ERR_INVALID, checked on the host before anything is launched: a negative count,
+ * na * nb > 2^22, both outputs NULL, |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or
+ * not a multiple of 8, rows that reach past *_bytes. */
+MNC_API int mnc_mask_overlaps(const int* a_bounds, const long long* a_offsets, const long long* a_areas, const void* a_bits,
+                              size_t a_bytes, int na, const int* b_bounds, const long long* b_offsets, const long long* b_areas,
+                              const void* b_bits, size_t b_bytes, int nb, long long* inter, double* iou, int device_id);
+/* Greedy mask NMS of one set (host pointers; the set as above, classes [n] (may be NULL when class_aware = 0), scores [n]
+ * float32; n <= 2048).  This library's own rule, the reference has none: order the instances by score descending, equal scores
+ * lower index first (np.argsort(-scores, kind="stable")); walk that order; instance i is kept unless an instance k kept earlier
+ * has iou(k, i) > thresh (strict, as nms_kernel.cu:71) and, with class_aware = 1, classes[k] == classes[i].  keep_out [n]
+ * receives the kept indices in score order, *num_out their count.  Order, IoU, suppression words and the greedy scan (nms.hip's)
+ * run on the device; the count and the kept rows come back in one copy.  MNC_ERR_INVALID as mnc_mask_overlaps, and: n outside
+ * [0, 2048], a NaN score, a NaN thresh, class_aware not 0 / 1. */
+MNC_API int mnc_mask_nms(const int* bounds, const long long* offsets, const long long* areas, const void* bits, size_t bytes,
+                         int n, const int* classes, const float* scores, double thresh, int class_aware, int* keep_out,
+                         int* num_out, int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */
@@ -746,6 +781,24 @@ MNC_API int mnc_render_records(mnc_ctx* ctx, const float* d_records, const int* 
 MNC_API int mnc_mask_records(mnc_ctx* ctx, const float* d_records, const int* d_counts, int record_cap, int num_classes,
                              int mask_size, double score_thresh, double binarize_thresh, int H, int W, void** d_info,
                              void** d_bits);
+/* n6 on the device: mnc_mask_overlaps with A the result of mnc_mask_records on this context -- d_info, d_bits and rows_cap
+ * (= its record_cap) as that call returned them; the instance count (head.kept) is read on the device, the host does not read it
+ * back.  B is a host set as in mnc_mask_overlaps, uploaded stream-ordered into an arena of the context, or b_bits == NULL for A
+ * against itself (nb is then rows_cap).  *d_inter (long long) and *d_iou (double) receive device addresses of [rows_cap][nb]
+ * matrices, row-major with leading dimension nb; rows and columns past the sets' counts hold 0 / 0.0.  Asynchronous on ctx's
+ * stream, in no captured graph; the matrices live in an arena of their own (never the one of mnc_mask_records: the masks stay
+ * as they are) and stay valid until the next mnc_mask_overlaps_dev / mnc_mask_nms_dev on this context.  rows_cap == 0 or
+ * nb == 0: nothing is launched, both addresses are NULL.  MNC_ERR_INVALID as mnc_mask_overlaps (rows_cap in the place of na). */
+MNC_API int mnc_mask_overlaps_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, const int* b_bounds,
+                                  const long long* b_offsets, const long long* b_areas, const void* b_bits, size_t b_bytes, int nb,
+                                  void** d_inter, void** d_iou);
+/* mnc_mask_nms of the result of mnc_mask_records (rows_cap <= 2048), scores and classes taken from its instance table, the score
+ * order computed on the device as well.  *d_keep receives the device address of [int kept | 252 bytes | int rows[rows_cap]]: the
+ * kept instances in score order, ONE copy of 256 + 4 * rows_cap bytes brings the count and the list down.  Asynchronous on
+ * ctx's stream, in no captured graph, buffers as mnc_mask_overlaps_dev's.  A NaN thresh is MNC_ERR_INVALID; a NaN score cannot
+ * be seen from the host: it is ordered by its bit pattern (memory-safe) and the result is then unspecified. */
+MNC_API int mnc_mask_nms_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, double thresh, int class_aware,
+                             void** d_keep);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */

@@ -48,6 +48,7 @@ struct mnc_ctx {
   mnc::DevArena vote_ws;      // gpu_mask_voting scratch (mv.hip), grown on demand
   mnc::DevArena render_ws;    // instance descriptors of mnc_render_records (render.hip), grown on demand; in no captured graph
   mnc::DevArena mask_ws;      // head, instance table and bits of mnc_mask_records (inst_masks.hip), grown on demand; in no captured graph
+  mnc::DevArena overlap_ws;   // uploaded B set, matrices and NMS buffers of mnc_mask_overlaps_dev / mnc_mask_nms_dev (mask_overlaps.hip); in no captured graph
   void* comm = nullptr;       // RCCL communicator state (comm.hip), set by mnc_comm_init
   // Arrival tickets of the K-range reductions that finish INSIDE the launch (gemm.hip, conv_wino4.hip): kTickets counters, zero
   // between launches -- allocated and zeroed with the context, every launch's last arriver of a tile puts its counter back to
@@ -226,7 +227,7 @@ struct CallBuf {
 };
 
 // Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances,
-// mnc_instance_masks): the
+// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms): the
 // device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
 // mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
 // ctypes releases the GIL, so two host threads may be inside such entry points on one device.

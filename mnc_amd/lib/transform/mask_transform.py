@@ -216,3 +216,28 @@ def instance_masks_numpy(boxes, masks, im_h, im_w, clip=True, binarize_thresh=No
     """instance_masks as the plain utils.blob.resize_to loop on the host: the CPU statement of the rule, the same PackedMasks."""
     from mnc_amd.masks import instance_masks_numpy as host_masks
     return host_masks(boxes, masks, im_h, im_w, clip, binarize_thresh, classes, scores)
+
+
+def mask_overlaps(a, b=None):
+    """mask_overlap of every pair of two mnc_amd.masks.PackedMasks (b None: a against itself) on the GPU (mnc_mask_overlaps):
+    -> (inter int64 [na, nb], iou float64 [na, nb])."""
+    from mnc_amd.masks import mask_overlaps as device_overlaps
+    return device_overlaps(a, b, cfg.GPU_ID)
+
+
+def mask_overlaps_numpy(a, b=None):
+    """mask_overlaps as the plain double loop over mask_overlap on the host: the CPU statement of the rule."""
+    from mnc_amd.masks import mask_overlaps_numpy as host_overlaps
+    return host_overlaps(a, b)
+
+
+def mask_nms(pm, thresh, class_aware=False):
+    """Greedy suppression of a PackedMasks by mask IoU in score order on the GPU (mnc_mask_nms) -> kept indices int32."""
+    from mnc_amd.masks import mask_nms as device_nms
+    return device_nms(pm, thresh, class_aware, cfg.GPU_ID)
+
+
+def mask_nms_numpy(pm, thresh, class_aware=False):
+    """mask_nms as a plain loop on the host: the CPU statement of the rule."""
+    from mnc_amd.masks import mask_nms_numpy as host_nms
+    return host_nms(pm, thresh, class_aware)

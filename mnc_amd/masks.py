@@ -7,6 +7,10 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     instance_masks(...)             host arrays -> PackedMasks through mnc_instance_masks (the GPU)
     instance_masks_numpy(...)       the same object from the plain utils.blob.resize_to loop: the CPU statement of the rule
     records_masks(...)              device-resident instance records -> PackedMasks through mnc_mask_records, copied on first access
+    mask_overlaps(a, b=None)        (inter int64 [na, nb], iou float64 [na, nb]) of every pair of two sets: the reference's
+                                    mask_overlap on the packed words (include/mnc_hip.h n6, csrc/mask_overlaps.hip)
+    mask_nms(pm, thresh)            greedy suppression by mask IoU in score order -> kept indices int32
+    mask_overlaps_numpy / mask_nms_numpy   the CPU statements of both; PackedMasks.overlaps / .nms / .take the methods
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -93,6 +97,49 @@ class PackedMasks(object):
         the leading bytes of the packed rows."""
         rows, w = self._rows(i)
         return np.ascontiguousarray(rows[:, :(w + 7) // 8])
+
+    def _device(self):
+        """The device result behind this object when its buffers are still the context's current ones, else None (a stale one
+        whose arrays were not all copied raises what load raises)."""
+        src = self._source
+        if src is None:
+            return None
+        if src.is_current():
+            return src
+        if all(name in self._host for name in self.FIELDS):
+            return None
+        src.check()
+
+    def overlaps(self, other=None):
+        """(inter int64 [n, m], iou float64 [n, m]) against `other` (a PackedMasks in the same image frame; None: against itself)
+        by the rule of mask_overlaps_numpy.  A device-resident result is compared where it lies (mnc_mask_overlaps_dev: its bits
+        are not copied to the host, only the matrices come back); anything else goes through mnc_mask_overlaps."""
+        dev = self._device()
+        if dev is None:
+            return mask_overlaps(self, other)
+        return dev.overlaps(len(self), None if other is None or other is self else other)
+
+    def nms(self, thresh, class_aware=False):
+        """Kept indices int32, in score order, of the greedy mask NMS (mask_nms_numpy's rule) on the GPU; a device-resident
+        result through mnc_mask_nms_dev (only the kept list comes back), anything else through mnc_mask_nms."""
+        dev = self._device()
+        if dev is None:
+            return mask_nms(self, thresh, class_aware)
+        return dev.nms(thresh, class_aware)
+
+    def take(self, indices):
+        """-> a host PackedMasks of these instances, in this order: offsets repacked without gaps, the bits copied."""
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        words, offsets, at = [], np.zeros(len(idx), np.int64), 0
+        for k, i in enumerate(idx):
+            h, w = self.size(i)
+            count = h * ((w + 63) // 64) if h and w else 0
+            lo = int(self.offsets[i]) // 8
+            words.append(self.bits[lo:lo + count])
+            offsets[k] = at
+            at += count * 8
+        bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
+        return PackedMasks(self.bounds[idx], offsets, self.areas[idx], self.classes[idx], self.scores[idx], bits)
 
     def arrays(self):
         """{name: array} of the six fields (what tools/demo.py --save-masks writes with np.savez)."""
@@ -216,10 +263,41 @@ class _DeviceResult(object):
         self.d_info, self.d_bits, self.rows = d_info, d_bits, int(rows)
         self._bytes = None
 
-    def load(self, host, want_bits):
-        if self._ctx._mask_gen != self._gen:
+    def is_current(self):
+        return self._ctx._mask_gen == self._gen
+
+    def check(self):
+        if not self.is_current():
             raise RuntimeError("these masks' device buffers have been reused by a later masks() on this context (read them, or "
                                ".fetch(), before the next image if they must outlive it)")
+
+    def overlaps(self, kept, other):
+        """mnc_mask_overlaps_dev of this result against `other` (a PackedMasks, read on the host; None: itself), the matrices
+        copied to the host: -> (inter [kept, m], iou [kept, m])."""
+        self.check()
+        m = self.rows if other is None else len(other)
+        d_inter, d_iou = ctypes.c_void_p(), ctypes.c_void_p()
+        args = (None, None, None, None, 0, 0) if other is None else _set_args(other)
+        _lib.call("mnc_mask_overlaps_dev", self._ctx.h, self.d_info, self.d_bits, self.rows, *(args + (
+            ctypes.addressof(d_inter), ctypes.addressof(d_iou))))
+        inter, iou = np.zeros((self.rows, m), np.int64), np.zeros((self.rows, m), np.float64)
+        if inter.size:
+            _lib.call("mnc_d2h_async", self._ctx.h, _lib.ptr(inter), d_inter.value, inter.nbytes)
+            _lib.call("mnc_d2h", self._ctx.h, _lib.ptr(iou), d_iou.value, iou.nbytes)
+        cols = kept if other is None else m
+        return np.ascontiguousarray(inter[:kept, :cols]), np.ascontiguousarray(iou[:kept, :cols])
+
+    def nms(self, thresh, class_aware):
+        self.check()
+        d_keep = ctypes.c_void_p()
+        _lib.call("mnc_mask_nms_dev", self._ctx.h, self.d_info, self.d_bits, self.rows, float(thresh), int(bool(class_aware)),
+                  ctypes.addressof(d_keep))
+        raw = np.zeros(HEAD_BYTES // 4 + self.rows, np.int32)
+        _lib.call("mnc_d2h", self._ctx.h, _lib.ptr(raw), d_keep.value, raw.nbytes)
+        return raw[HEAD_BYTES // 4:HEAD_BYTES // 4 + int(raw[0])].copy()
+
+    def load(self, host, want_bits):
+        self.check()
         h = self._ctx.h
         if self._bytes is None:
             first = min(self.rows, self.FIRST)
@@ -262,3 +340,80 @@ def net_masks(net_handle, rows_cap, score_thresh, binarize_thresh):
     _lib.call("mnc_net_masks", net_handle, float(score_thresh), float(binarize_thresh), _lib.ptr(raw), int(rows_cap),
               _lib.ptr(bits) if bits.size else None, bits.nbytes, ctypes.addressof(need))
     return PackedMasks(bits=bits, **_from_info(raw, int(raw[:HEAD_BYTES].view(HEAD)[0]["kept"])))
+
+
+def _pair_numpy(box1, box2, mask1, mask2):
+    """inter of transform.mask_transform.mask_overlap: the same slices, the count alone."""
+    x1, y1 = max(box1[0], box2[0]), max(box1[1], box2[1])
+    x2, y2 = min(box1[2], box2[2]), min(box1[3], box2[3])
+    if x1 > x2 or y1 > y2:
+        return 0
+    w, h = x2 - x1 + 1, y2 - y1 + 1
+    ya, xa, yb, xb = y1 - box1[1], x1 - box1[0], y1 - box2[1], x1 - box2[0]
+    return int(np.logical_and(mask2[yb:yb + h, xb:xb + w], mask1[ya:ya + h, xa:xa + w]).sum())
+
+
+def mask_overlaps_numpy(a, b=None):
+    """The rule as a plain double loop on the host: iou[i, j] = transform.mask_transform.mask_overlap(a.bounds[i], b.bounds[j],
+    a.dense(i), b.dense(j)) (the reference's lib/transform/mask_transform.py:16-46; its int 0 read as 0.0), inter[i, j] the
+    count behind it.  b None: a against itself.  -> (inter int64 [na, nb], iou float64 [na, nb])."""
+    from transform.mask_transform import mask_overlap
+    b = a if b is None else b
+    da, db = [a.dense(i) for i in range(len(a))], [b.dense(j) for j in range(len(b))]
+    ba, bb = [[int(v) for v in r] for r in a.bounds], [[int(v) for v in r] for r in b.bounds]
+    inter, iou = np.zeros((len(a), len(b)), np.int64), np.zeros((len(a), len(b)), np.float64)
+    for i in range(len(a)):
+        for j in range(len(b)):
+            inter[i, j] = _pair_numpy(ba[i], bb[j], da[i], db[j])
+            iou[i, j] = mask_overlap(ba[i], bb[j], da[i], db[j])
+    return inter, iou
+
+
+def mask_nms_numpy(pm, thresh, class_aware=False):
+    """The mask NMS as a plain loop on the host: the instances in score order (descending, equal scores lower index first), each
+    kept unless one kept earlier has iou > thresh with it (strict) and, with class_aware, its class.  -> kept indices int32 in
+    score order.  Raises ValueError on a NaN score or threshold."""
+    thresh = float(thresh)
+    scores = np.asarray(pm.scores, np.float32)
+    if thresh != thresh or np.isnan(scores).any():
+        raise ValueError("mask_nms_numpy: NaN score or threshold")
+    _, iou = mask_overlaps_numpy(pm)
+    keep = []
+    for i in np.argsort(-scores, kind="stable"):
+        if not any(iou[k, i] > thresh and (not class_aware or pm.classes[k] == pm.classes[i]) for k in keep):
+            keep.append(int(i))
+    return np.array(keep, np.int32)
+
+
+def _set_args(pm):
+    """The six arguments of one host set.  (An empty bits array still has an address: NULL would mean "B is A".)"""
+    bits = pm.bits if pm.bits.size else np.zeros(1, np.uint64)
+    return (_lib.ptr(pm.bounds), _lib.ptr(pm.offsets), _lib.ptr(pm.areas), _lib.ptr(bits), int(pm.bits.nbytes), len(pm))
+
+
+def _device_id(device_id):
+    if device_id is not None:
+        return int(device_id)
+    from mnc_config import cfg
+    return int(cfg.get("GPU_ID", 0))
+
+
+def mask_overlaps(a, b=None, device_id=None):
+    """mask_overlaps_numpy on the GPU (mnc_mask_overlaps, csrc/mask_overlaps.hip): the same two matrices bit for bit.  Invalid
+    sets raise _lib.MncError (MNC_ERR_INVALID) before anything is launched."""
+    nb = len(a) if b is None or b is a else len(b)
+    inter, iou = np.zeros((len(a), nb), np.int64), np.zeros((len(a), nb), np.float64)
+    args_b = (None, None, None, None, 0, 0) if b is None or b is a else _set_args(b)
+    _lib.call("mnc_mask_overlaps", *(_set_args(a) + args_b + (_lib.ptr(inter), _lib.ptr(iou), _device_id(device_id))))
+    return inter, iou
+
+
+def mask_nms(pm, thresh, class_aware=False, device_id=None):
+    """mask_nms_numpy on the GPU (mnc_mask_nms): order, IoU, suppression words and the greedy scan on the device, the kept
+    indices back in one copy."""
+    n = len(pm)
+    keep, num = np.zeros(max(n, 1), np.int32), ctypes.c_int(0)
+    _lib.call("mnc_mask_nms", *(_set_args(pm)[:5] + (n, _lib.ptr(pm.classes), _lib.ptr(pm.scores), float(thresh),
+                                                     int(bool(class_aware)), _lib.ptr(keep), ctypes.addressof(num),
+                                                     _device_id(device_id))))
+    return keep[:num.value].copy()
