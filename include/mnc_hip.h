@@ -269,6 +269,42 @@ MNC_API int mnc_mask_nms(const int* bounds, const long long* offsets, const long
                          int* num_out, int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n7  The way out and back: COCO run-length encoding of packed instance masks (csrc/mask_rle.hip) -- the rule of the published
+ *     maskApi.c (rleEncode, rleDecode, rleToBbox) on the layout of n5, without unpacking a mask.  An H x W image is read column
+ *     by column: pixel (x, y) stands at position p = x * H + y.  The counts of a mask are the lengths of its runs of 0 and of 1
+ *     in turn, beginning with a run of 0 (of length 0 when pixel (0, 0) is set): with t_0 < t_1 < ... the positions whose pixel
+ *     differs from the pixel before (the one before position 0 counts as 0), counts = diff([0, t_0, ..., t_{T-1}, H * W]), T + 1
+ *     entries that sum to H * W.  An empty mask gives [H * W], a full one [0, H * W]; apart from the first, no count is 0.  The
+ *     compressed ASCII form of the counts (rleToString) is made on the host: mnc_amd/rle.py.  The form that reads a
+ *     device-resident mnc_mask_records result (mnc_mask_rle_dev) stands beside that entry below.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  The set as mnc_mask_overlaps takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds
+ * (the areas are not needed).  Instance i covers the bits inside its bounds that also lie inside the H x W image (bounds may
+ * leave it: clip = 0); an instance without rows is empty; padding bits (column >= w of a row) are not trusted and never counted.
+ * Outputs: run_ptr [n + 1] (run_ptr[0] = 0; the counts of instance i are runs[run_ptr[i] .. run_ptr[i + 1])), runs (uint32),
+ * *runs_total = run_ptr[n].  runs == NULL: run_ptr and *runs_total only (the counting passes alone run).  Otherwise runs_cap is
+ * the room of runs in entries; runs_cap < *runs_total is MNC_ERR_INVALID with run_ptr and *runs_total set, so that the caller
+ * calls again with room.  The order of the output comes from a scan over columns and instances, never from atomics: the result
+ * is the same bits from run to run.  n == 0 returns before any device work (*runs_total = 0).  MNC_ERR_INVALID, checked on
+ * the host before anything is launched: n outside [0, 2048], H or W outside [1, 32768] (H * W <= 2^30: counts and positions fit
+ * 32 bits), |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or not a multiple of 8, rows
+ * that reach past bytes. */
+MNC_API int mnc_mask_rle(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int H, int W,
+                         long long* run_ptr, unsigned* runs, size_t runs_cap, size_t* runs_total, int device_id);
+/* The reverse (host pointers): n masks of one H x W image given as counts -- run_ptr [n + 1] (non-negative, not decreasing),
+ * runs (uint32) -- to the layout of n5.  Pixel p is set when it lies in a run of odd index; runs of length 0 are accepted
+ * anywhere (the published decoder accepts them; encoding the result gives the canonical counts).  The bounds of an instance are
+ * the tight box of its set pixels (rleToBbox); an empty mask gets (0, 0, -1, -1), no rows and area 0.  Outputs: bounds [n][4],
+ * offsets [n] (multiples of 8, in order without gaps), areas [n] (the true bit counts), the rows in bits (padding bits 0),
+ * *bits_bytes = the bytes they take.  A first kernel reduces bounds and areas over the runs of 1, the host forms the offsets, a
+ * second kernel writes every word of every row once (nothing needs to be zeroed beforehand).  bits == NULL: bounds, offsets,
+ * areas and *bits_bytes only.  n == 0 returns before any device work.  MNC_ERR_INVALID, checked on the host before anything is
+ * launched: n outside [0, 2048], H or W outside [1, 32768], a negative or decreasing run_ptr, a mask whose counts do not sum to
+ * H * W exactly; and, after the bounds pass, bits_cap < *bits_bytes (*bits_bytes is set). */
+MNC_API int mnc_mask_from_rle(const long long* run_ptr, const unsigned* runs, int n, int H, int W, int* bounds, long long* offsets,
+                              long long* areas, void* bits, size_t bits_cap, size_t* bits_bytes, int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */
@@ -799,6 +835,17 @@ MNC_API int mnc_mask_overlaps_dev(mnc_ctx* ctx, const void* d_info, const void* 
  * be seen from the host: it is ordered by its bit pattern (memory-safe) and the result is then unspecified. */
 MNC_API int mnc_mask_nms_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, double thresh, int class_aware,
                              void** d_keep);
+/* n7 on the device: mnc_mask_rle of the result of mnc_mask_records on this context (d_info, d_bits, rows_cap = its record_cap,
+ * H and W the image it was made for; rows_cap <= 2048); the instance count is read on the device, nothing is read back by the
+ * call.  *d_rle receives the device address of
+ *   [256-byte head: int kept at byte 0, long long total_runs at byte 8 | long long run_ptr[rows_cap + 1] | unsigned runs[runs_cap]]
+ * (run_ptr entries past kept repeat total_runs).  Emission is guarded by slot < runs_cap, total_runs is always the true total:
+ * a caller that finds total_runs > runs_cap calls again with room (runs_cap == 0: the counting passes alone).  Two copies bring
+ * the result down: head + run_ptr, then the runs; the bits never leave the device.  Asynchronous on ctx's stream, in no captured
+ * graph; the result lives in an arena of its own (never the one of mnc_mask_records: the masks stay as they are) and stays valid
+ * until the next mnc_mask_rle_dev on this context.  rows_cap == 0: nothing is launched, the head is zero. */
+MNC_API int mnc_mask_rle_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, int H, int W, size_t runs_cap,
+                             void** d_rle);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */

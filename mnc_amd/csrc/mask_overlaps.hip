@@ -165,7 +165,10 @@ namespace {
 
 inline long long ov_bytes(int w, int h) { return w < 1 || h < 1 ? 0 : (long long)h * ((w + 63) >> 6) * 8; }
 
+}  // namespace
+
 // The instance table of a host set, checked: MNC_ERR_INVALID before anything is launched.  *used = the bytes of `bits` the rows reach.
+// (Shared with mask_rle.hip: mnc_internal.h.)
 int ov_table(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
              size_t bytes, int n, const int* classes, const float* scores, std::vector<mnc_mask_info>* info, size_t* used) {
   MNC_REQUIRE(n == 0 || (bounds && offsets && areas), "%s: null pointer in set %s", who, set);
@@ -195,6 +198,8 @@ int ov_table(const char* who, const char* set, const int* bounds, const long lon
   MNC_REQUIRE(*used == 0 || bits, "%s: null bits in set %s", who, set);
   return MNC_OK;
 }
+
+namespace {
 
 void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
                      long long* d_inter, double* d_iou) {

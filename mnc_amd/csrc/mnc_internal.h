@@ -48,6 +48,7 @@ struct mnc_ctx {
   mnc::DevArena vote_ws;      // gpu_mask_voting scratch (mv.hip), grown on demand
   mnc::DevArena render_ws;    // instance descriptors of mnc_render_records (render.hip), grown on demand; in no captured graph
   mnc::DevArena mask_ws;      // head, instance table and bits of mnc_mask_records (inst_masks.hip), grown on demand; in no captured graph
+  mnc::DevArena rle_ws;       // result and scan buffers of mnc_mask_rle_dev (mask_rle.hip), grown on demand; in no captured graph
   mnc::DevArena overlap_ws;   // uploaded B set, matrices and NMS buffers of mnc_mask_overlaps_dev / mnc_mask_nms_dev (mask_overlaps.hip); in no captured graph
   void* comm = nullptr;       // RCCL communicator state (comm.hip), set by mnc_comm_init
   // Arrival tickets of the K-range reductions that finish INSIDE the launch (gemm.hip, conv_wino4.hip): kTickets counters, zero
@@ -227,7 +228,7 @@ struct CallBuf {
 };
 
 // Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances,
-// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms): the
+// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle): the
 // device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
 // mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
 // ctypes releases the GIL, so two host threads may be inside such entry points on one device.
@@ -257,6 +258,10 @@ int nms_mask_launch_indirect(hipStream_t stream, const float* d_boxes, const int
 int nms_scan_launch_indirect(hipStream_t stream, const unsigned long long* d_mask, const int* d_n, int n_cap, int max_keep,
                              int* d_keep, int* d_num, const float* d_gather_boxes = nullptr, const int* d_gather_order = nullptr,
                              float* d_rois = nullptr, int rois_cap = 0);   // d_rois: the ProposalLayer's RoI rows written by the same launch
+// mask_overlaps.hip: the instance table of a host set of packed masks (bounds, offsets, areas as include/mnc_hip.h n5 gives them),
+// checked against the coordinate, pixel and offset limits of mnc_mask_overlaps; *used = the bytes of `bits` the rows reach
+int ov_table(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
+             size_t bytes, int n, const int* classes, const float* scores, std::vector<mnc_mask_info>* info, size_t* used);
 void proposal_state_free(void* state);  // proposal.hip
 void comm_free(mnc_ctx* ctx);           // comm.hip
 void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,

@@ -4,7 +4,7 @@ Host orchestration only: 20 per-class NMS calls (HIP), a global score threshold,
 single call into the fused HIP mask-voting kernels (nms.mv.mv).  The reference's cv2-based cpu_mask_voting (image-space voting,
 cfg.TEST.USE_GPU_MASK_MERGE = False) runs on the GPU as well: cpu_mask_voting below (csrc/mv_image.hip).  instance_masks turns the
 voted instances into per-instance binary masks at image resolution on the GPU (csrc/inst_masks.hip); instance_masks_numpy is the
-same rule as a plain loop on the host."""
+same rule as a plain loop on the host; mask_rle / masks_from_rle take them to COCO's run-length encoding and back (csrc/mask_rle.hip)."""
 import numpy as np
 
 from mnc_config import cfg
@@ -241,3 +241,28 @@ def mask_nms_numpy(pm, thresh, class_aware=False):
     """mask_nms as a plain loop on the host: the CPU statement of the rule."""
     from mnc_amd.masks import mask_nms_numpy as host_nms
     return host_nms(pm, thresh, class_aware)
+
+
+def mask_rle(pm, H, W):
+    """COCO RLEs of a PackedMasks in an H x W image on the GPU (mnc_mask_rle / mnc_mask_rle_dev): -> [{"size": [H, W], "counts":
+    str}] per instance."""
+    from mnc_amd.rle import mask_rle as device_rle
+    return device_rle(pm, H, W, cfg.GPU_ID)
+
+
+def masks_from_rle(rles, classes=None, scores=None):
+    """COCO RLEs of one image size -> mnc_amd.masks.PackedMasks with tight bounds on the GPU (mnc_mask_from_rle)."""
+    from mnc_amd.rle import masks_from_rle as device_from_rle
+    return device_from_rle(rles, classes, scores, cfg.GPU_ID)
+
+
+def rle_counts_numpy(pm, H, W):
+    """The run-length counts as plain numpy on the host: the CPU statement of the rule -> (run_ptr, runs)."""
+    from mnc_amd.rle import rle_counts_numpy as host_counts
+    return host_counts(pm, H, W)
+
+
+def masks_from_counts_numpy(run_ptr, runs, H, W, classes=None, scores=None):
+    """The reverse as plain numpy on the host: the CPU statement of the rule -> PackedMasks."""
+    from mnc_amd.rle import masks_from_counts_numpy as host_masks
+    return host_masks(run_ptr, runs, H, W, classes, scores)

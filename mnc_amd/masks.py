@@ -11,6 +11,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                     mask_overlap on the packed words (include/mnc_hip.h n6, csrc/mask_overlaps.hip)
     mask_nms(pm, thresh)            greedy suppression by mask IoU in score order -> kept indices int32
     mask_overlaps_numpy / mask_nms_numpy   the CPU statements of both; PackedMasks.overlaps / .nms / .take the methods
+    PackedMasks.rle_counts / .rle / .from_rle   COCO run-length encoding of the masks and the way back (mnc_amd/rle.py, n7)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -126,6 +127,29 @@ class PackedMasks(object):
         if dev is None:
             return mask_nms(self, thresh, class_aware)
         return dev.nms(thresh, class_aware)
+
+    def rle_counts(self, H, W, device_id=None):
+        """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major
+        (mnc_amd.rle.rle_counts_numpy's rule; include/mnc_hip.h n7, csrc/mask_rle.hip) on the GPU.  A device-resident result is
+        encoded where it lies (mnc_mask_rle_dev: only run_ptr and the runs come back); anything else goes through mnc_mask_rle on
+        GPU device_id (None: cfg.GPU_ID)."""
+        from . import rle
+        dev = self._device()
+        if dev is None:
+            return rle.rle_counts(self, H, W, device_id)
+        return rle.device_rle_counts(dev, H, W)
+
+    def rle(self, H, W, device_id=None):
+        """-> [{"size": [H, W], "counts": str}] per instance: COCO's compressed RLE of the instance in an H x W image."""
+        from . import rle
+        return rle._to_rles(*(self.rle_counts(H, W, device_id) + (H, W)))
+
+    @classmethod
+    def from_rle(cls, rles, classes=None, scores=None):
+        """COCO RLEs of one image size ({"size": [H, W], "counts": str, bytes or an uncompressed list}) -> PackedMasks with tight
+        bounds, decoded on the GPU (mnc_mask_from_rle)."""
+        from . import rle
+        return rle.masks_from_rle(rles, classes, scores)
 
     def take(self, indices):
         """-> a host PackedMasks of these instances, in this order: offsets repacked without gaps, the bits copied."""

@@ -4,12 +4,13 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR]
+                         [--save-masks DIR] [--save-coco FILE]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
 `--cpu` is accepted and ignored by the network, exactly as in the reference (demo.py:40-42 vs :126); with --save-masks it selects
-the numpy form of the per-instance masks (transform.mask_transform.instance_masks_numpy) instead of the GPU's."""
+the numpy form of the per-instance masks (transform.mask_transform.instance_masks_numpy) instead of the GPU's, with --save-coco
+the numpy form of the run-length encoding as well (mnc_amd.rle.rle_counts_numpy)."""
 import argparse
 import os
 import time
@@ -43,6 +44,9 @@ def parse_args(argv=None):
     p.add_argument("--save-masks", dest="save_masks", default=None, metavar="DIR",
                    help="write <image>_masks.npz per image: one binary mask per instance scoring >= --vis-thresh at image "
                         "resolution, packed one bit per pixel (the arrays of mnc_amd.masks.PackedMasks)")
+    p.add_argument("--save-coco", dest="save_coco", default=None, metavar="FILE",
+                   help="write the instances scoring >= --vis-thresh of all images as one JSON array of COCO results: "
+                        "{image_id, category_id, segmentation: {size, counts}, bbox, score}, the masks run-length encoded")
     return p.parse_args(argv)
 
 
@@ -141,18 +145,48 @@ def _visualise(im_bgr, pred, out_path, view=None, vis_thresh=0.5):
     plt.close(fig)
 
 
-def _save_masks(out_dir, name, im_shape, result_mask, result_box, view=None, score_thresh=0.5, cpu=False):
-    """The instances scoring >= score_thresh as per-instance binary masks at image resolution -> <out_dir>/<name>_masks.npz
-    (mnc_amd.masks.PackedMasks.load reads it back).  From the device records of `view` (InstanceView.masks, csrc/inst_masks.hip) or
-    else from the lists, on the GPU; cpu=True: the numpy loop, with the same arrays."""
+def _packed_masks(im_shape, result_mask, result_box, view=None, score_thresh=0.5, cpu=False):
+    """The instances scoring >= score_thresh as per-instance binary masks at image resolution (mnc_amd.masks.PackedMasks): from
+    the device records of `view` (InstanceView.masks, csrc/inst_masks.hip) or else from the lists, on the GPU; cpu=True: the numpy
+    loop, with the same arrays."""
     from mnc_amd.masks import from_lists
     from transform.mask_transform import instance_masks, instance_masks_numpy
     h, w = im_shape[:2]
     if view is not None and not cpu:
-        packed = view.masks(h, w, score_thresh=score_thresh)
-    else:
-        bxs, mks, classes = from_lists(result_mask, result_box, score_thresh)
-        packed = (instance_masks_numpy if cpu else instance_masks)(bxs, mks, h, w, clip=True, classes=classes)
+        return view.masks(h, w, score_thresh=score_thresh)
+    bxs, mks, classes = from_lists(result_mask, result_box, score_thresh)
+    return (instance_masks_numpy if cpu else instance_masks)(bxs, mks, h, w, clip=True, classes=classes)
+
+
+def _coco_results(image_id, im_shape, packed, cpu=False):
+    """-> COCO result entries of one image's PackedMasks: the mask run-length encoded in the image (on the GPU where the masks
+    lie, csrc/mask_rle.hip; cpu=True: mnc_amd.rle's numpy statement), bbox = [x, y, w, h] of the tight box of its pixels."""
+    from mnc_amd import rle
+    h, w = im_shape[:2]
+    run_ptr, runs = rle.rle_counts_numpy(packed, h, w) if cpu else packed.rle_counts(h, w)
+    out = []
+    for i in range(len(packed)):
+        c = runs[run_ptr[i]:run_ptr[i + 1]]
+        # rleToBbox: the odd positions of the running sum are where the runs of 1 begin, the even ones where they end
+        edge = np.cumsum(c.astype(np.int64))[:len(c) // 2 * 2].reshape(-1, 2)
+        edge = edge[edge[:, 1] > edge[:, 0]]
+        if len(edge):
+            xs, xe = edge[:, 0] // h, (edge[:, 1] - 1) // h
+            ys, ye = np.where(xs == xe, edge[:, 0] % h, 0), np.where(xs == xe, (edge[:, 1] - 1) % h, h - 1)
+            bbox = [int(xs.min()), int(ys.min()), int(xe.max() - xs.min() + 1), int(ye.max() - ys.min() + 1)]
+        else:
+            bbox = [0, 0, 0, 0]
+        out.append({"image_id": image_id, "category_id": int(packed.classes[i]),
+                    "segmentation": {"size": [int(h), int(w)], "counts": rle.counts_to_string(c)}, "bbox": bbox,
+                    "score": float(packed.scores[i])})
+    return out
+
+
+def _save_masks(out_dir, name, im_shape, result_mask, result_box, view=None, score_thresh=0.5, cpu=False, packed=None):
+    """The instances scoring >= score_thresh (_packed_masks) -> <out_dir>/<name>_masks.npz (mnc_amd.masks.PackedMasks.load reads
+    it back)."""
+    if packed is None:
+        packed = _packed_masks(im_shape, result_mask, result_box, view, score_thresh, cpu)
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, name + "_masks.npz")
     np.savez(out, **packed.arrays())
@@ -188,6 +222,7 @@ def main(argv=None):
     if not images:
         print("no images given; running one synthetic 600x1000 image")
         images = [None]
+    coco = []
     for path in images:
         print("~" * 35)
         print("Demo for {}".format(path or "<synthetic 600x1000>"))
@@ -200,13 +235,17 @@ def main(argv=None):
         print("mask voting time %f" % (time.time() - start))
         pred = get_vis_dict(result_box, result_mask, path or "synthetic", CLASSES, args.vis_thresh)
         print("%d instances with score >= %g" % (len(pred["boxes"]), args.vis_thresh))
-        if args.save_masks:
+        if args.save_masks or args.save_coco:
             from mnc_amd.devarray import DeviceArray
             blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
-            out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, blk.view() if blk is not None else None,
-                                      args.vis_thresh, args.cpu_mode)
-            print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
+            packed = _packed_masks(im.shape, result_mask, result_box, blk.view() if blk is not None else None, args.vis_thresh,
+                                   args.cpu_mode)
+            if args.save_coco:                                    # (first: a device-resident result is encoded where it lies)
+                coco.extend(_coco_results(name, im.shape, packed, args.cpu_mode))
+            if args.save_masks:
+                out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, packed=packed)
+                print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
         if args.vis and path:
             out = os.path.splitext(path)[0] + "_mnc.png"
             if args.out_dir:
@@ -219,6 +258,11 @@ def main(argv=None):
             view = blk.view() if cfg.TEST.USE_GPU_VIS and blk is not None and im.dtype == np.uint8 else None
             _visualise(im, pred, out, view, args.vis_thresh)
             print("wrote", out)
+    if args.save_coco:
+        import json
+        with open(args.save_coco, "w") as f:
+            json.dump(coco, f)
+        print("wrote %s (%d instances)" % (args.save_coco, len(coco)))
     net.close()
 
 
