@@ -305,6 +305,45 @@ MNC_API int mnc_mask_from_rle(const long long* run_ptr, const unsigned* runs, in
                               long long* areas, void* bits, size_t bits_cap, size_t* bits_bytes, int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n8  Scoring the instances: COCO's matching of one image's detections to its ground truths (csrc/mask_match.hip) -- the rule of
+ *     the published cocoeval.py (computeIoU, evaluateImg) and of rleIou in maskApi.c on the layout of n5, the counts those of
+ *     n6.  The statement of the rule is mnc_amd/coco_eval.py:match_numpy; accumulation and the twelve summary numbers are host
+ *     numpy there.  The form that reads a device-resident mnc_mask_records result (mnc_mask_match_dev) stands beside that
+ *     entry below.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  The detections (nd, with dt_classes [nd] and dt_scores [nd] float32) and the ground truths (ng, with
+ * gt_classes [ng], gt_crowd [ng] bytes 0 / 1, gt_ignore_in [ng] bytes 0 / 1 or NULL for all 0, gt_eval_area [ng] or NULL for
+ * gt_areas) are two sets in the same image frame as mnc_mask_overlaps takes them.  iou_thrs [T], area_rngs [A][2] (lo, hi),
+ * max_det.  A detection only sees ground truths of its class.
+ *   rank[d]     = the detections of d's class with a higher score, or the same score and a lower index
+ *                 (np.argsort(-scores, kind="mergesort") per class).  rank[d] >= max_det: d takes no part (unmatched, not ignored).
+ *   iou[d][g]   = union < 1 ? 0.0 : (double)inter / (double)union, inter the count of mnc_mask_overlaps (padding bits never
+ *                 counted), union = dt_areas[d] + gt_areas[g] - inter, for a crowd ground truth dt_areas[d]; pairs of different
+ *                 classes included.
+ *   gt_ignore[a][g] = gt_ignore_in[g] or gt_crowd[g] or gt_eval_area[g] < lo_a or gt_eval_area[g] > hi_a.
+ *   Per (a, t) the class's participating detections in rank order; each takes, among the not-ignored ground truths of its class
+ *   that no earlier detection took and whose iou >= min(iou_thrs[t], 1 - 1e-10), the one of largest iou, of several equal the
+ *   highest index; if there is none, the same choice among the ignored ones that are crowd or not yet taken (a not-ignored
+ *   ground truth wins over an ignored one of larger iou) -- the closed form of evaluateImg's walk.  A match m sets
+ *   dt_match[a][t][d] = m, gt_match[a][t][m] = d (a crowd ground truth keeps the last detection that took it) and
+ *   dt_ignore[a][t][d] = gt_ignore[a][m]; a participating detection without a match gets dt_ignore = 1 when dt_areas[d] < lo_a
+ *   or > hi_a.
+ * Outputs, in the caller's index order, -1 for "none": rank [nd], dt_match [A][T][nd], dt_ignore [A][T][nd] (bytes), gt_match
+ * [A][T][ng], gt_ignore [A][ng] (bytes), iou [nd][ng] (may be NULL).  Ranks, lists, IoU table and matching run on the device
+ * without atomics and without a read-back in between: the same bits from run to run.  nd == 0 or ng == 0 returns before any
+ * device work with every table filled as the rule gives.  MNC_ERR_INVALID, checked on the host before anything is launched:
+ * everything mnc_mask_overlaps refuses; nd or ng outside [0, 2048]; T outside [1, 16]; A outside [1, 8]; max_det outside
+ * [1, 2048]; a NaN score, threshold or range bound; lo > hi; a crowd or ignore byte other than 0 / 1; a NULL output other than
+ * iou. */
+MNC_API int mnc_mask_match(const int* dt_bounds, const long long* dt_offsets, const long long* dt_areas, const void* dt_bits,
+                           size_t dt_bytes, int nd, const int* dt_classes, const float* dt_scores, const int* gt_bounds,
+                           const long long* gt_offsets, const long long* gt_areas, const void* gt_bits, size_t gt_bytes, int ng,
+                           const int* gt_classes, const unsigned char* gt_crowd, const unsigned char* gt_ignore_in,
+                           const double* gt_eval_area, const double* iou_thrs, int T, const double* area_rngs, int A, int max_det,
+                           int* rank, int* dt_match, unsigned char* dt_ignore, int* gt_match, unsigned char* gt_ignore,
+                           double* iou, int device_id);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */
@@ -846,6 +885,22 @@ MNC_API int mnc_mask_nms_dev(mnc_ctx* ctx, const void* d_info, const void* d_bit
  * until the next mnc_mask_rle_dev on this context.  rows_cap == 0: nothing is launched, the head is zero. */
 MNC_API int mnc_mask_rle_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, int H, int W, size_t runs_cap,
                              void** d_rle);
+/* n8 on the device: mnc_mask_match with the detections the result of mnc_mask_records on this context (d_info, d_bits, rows_cap
+ * = its record_cap <= 2048; classes, scores and areas from its instance table, the count read on the device); the ground truths
+ * and the parameters are host arrays as in mnc_mask_match, uploaded stream-ordered.  The outputs are device addresses of tables
+ * with rows_cap in the place of nd (leading dimension rows_cap; entries past the count hold -1 / 0 / 0.0): *d_rank,
+ * *d_dt_match, *d_dt_ignore, *d_gt_match, *d_gt_ignore, and with want_iou = 1 *d_iou (else NULL).  Only those tables need to come
+ * back; the bits never leave the device.  Asynchronous on ctx's stream, in no captured graph; everything lives in an arena of
+ * its own (never the one of mnc_mask_records or of mnc_mask_overlaps_dev) and stays valid until the next mnc_mask_match_dev on
+ * this context.  The ranks and the size rule need the device's table, so ng == 0 still launches the list and matching passes;
+ * rows_cap == 0 and ng == 0 launches nothing.  A NaN score cannot be seen from the host: it is ordered by its bit pattern
+ * (memory-safe) and the result is then unspecified.  MNC_ERR_INVALID otherwise as mnc_mask_match. */
+MNC_API int mnc_mask_match_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int rows_cap, const int* gt_bounds,
+                               const long long* gt_offsets, const long long* gt_areas, const void* gt_bits, size_t gt_bytes, int ng,
+                               const int* gt_classes, const unsigned char* gt_crowd, const unsigned char* gt_ignore_in,
+                               const double* gt_eval_area, const double* iou_thrs, int T, const double* area_rngs, int A,
+                               int max_det, int want_iou, void** d_rank, void** d_dt_match, void** d_dt_ignore, void** d_gt_match,
+                               void** d_gt_ignore, void** d_iou);
 /* The tail of im_detect on the device (tools/demo.py:84-100, lib/caffeWrapper/TesterWrapper.py:240-260): d_boxes
  * [R1+R2][4] = clip(rois[:, 1:5] / scale, image) of stage-1 rois followed by stage-2 rois (float32 division, clamp to
  * [0, W-1] x [0, H-1] as transform/bbox_transform.py:clip_boxes). */

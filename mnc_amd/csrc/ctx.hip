@@ -188,6 +188,7 @@ int mnc_ctx_destroy(mnc_ctx* ctx) {
   arena_free(&ctx->mask_ws);
   arena_free(&ctx->overlap_ws);
   arena_free(&ctx->rle_ws);
+  arena_free(&ctx->match_ws);
   if (ctx->tickets) (void)hipFree(ctx->tickets);
   if (ctx->comm) mnc::comm_free(ctx);
   (void)hipStreamDestroy(ctx->stream);

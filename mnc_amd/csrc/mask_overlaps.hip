@@ -42,14 +42,7 @@ constexpr int kOvMaxCoord = 1 << 24;           // |coordinate| limit: widths, he
 constexpr long long kOvMaxArea = 1LL << 26;    // pixels of one bound
 constexpr int kOvMaxNms = 2048;                // instances of one mask NMS
 
-// One set of packed masks on the device: the instance table, the words, and the count (read from *n_ptr when that is set).
-struct OvSet {
-  const mnc_mask_info* info;
-  const u64* bits;
-  const int* n_ptr;
-  int n;
-};
-
+// (OvSet, one set of packed masks on the device, is declared in mnc_internal.h: mask_match.hip launches the overlap kernel too.)
 __device__ __forceinline__ int ov_count(const OvSet& s, int cap) { return min(max(s.n_ptr ? *s.n_ptr : s.n, 0), cap); }
 
 // Word j of a row of `strips` words holding w columns: 0 outside the row, the padding of the last word cleared.
@@ -199,8 +192,7 @@ int ov_table(const char* who, const char* set, const int* bounds, const long lon
   return MNC_OK;
 }
 
-namespace {
-
+// (Shared with mask_match.hip: mnc_internal.h.)
 void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
                      long long* d_inter, double* d_iou) {
   const long long pairs = (long long)rows * cols;
@@ -208,6 +200,8 @@ void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d
   hipLaunchKernelGGL(mask_overlaps_kernel, dim3((unsigned)((pairs + kOvWaves - 1) / kOvWaves)), dim3(kOvThreads), 0, s, A, B, d_order,
                      upper_only, rows, cols, d_inter, d_iou);
 }
+
+namespace {
 
 // Buffers of one mask NMS over a set of capacity `cap`, and its launch sequence: order, the upper triangle of the IoU matrix in
 // score order, the suppression words, nms.hip's scan, the kept rows.

@@ -50,6 +50,7 @@ struct mnc_ctx {
   mnc::DevArena mask_ws;      // head, instance table and bits of mnc_mask_records (inst_masks.hip), grown on demand; in no captured graph
   mnc::DevArena rle_ws;       // result and scan buffers of mnc_mask_rle_dev (mask_rle.hip), grown on demand; in no captured graph
   mnc::DevArena overlap_ws;   // uploaded B set, matrices and NMS buffers of mnc_mask_overlaps_dev / mnc_mask_nms_dev (mask_overlaps.hip); in no captured graph
+  mnc::DevArena match_ws;     // uploaded ground truth, lists, IoU tables and result tables of mnc_mask_match_dev (mask_match.hip); in no captured graph
   void* comm = nullptr;       // RCCL communicator state (comm.hip), set by mnc_comm_init
   // Arrival tickets of the K-range reductions that finish INSIDE the launch (gemm.hip, conv_wino4.hip): kTickets counters, zero
   // between launches -- allocated and zeroed with the context, every launch's last arriver of a tile puts its counter back to
@@ -228,7 +229,7 @@ struct CallBuf {
 };
 
 // Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances,
-// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle): the
+// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle, mnc_mask_match): the
 // device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
 // mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
 // ctypes releases the GIL, so two host threads may be inside such entry points on one device.
@@ -262,6 +263,17 @@ int nms_scan_launch_indirect(hipStream_t stream, const unsigned long long* d_mas
 // checked against the coordinate, pixel and offset limits of mnc_mask_overlaps; *used = the bytes of `bits` the rows reach
 int ov_table(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
              size_t bytes, int n, const int* classes, const float* scores, std::vector<mnc_mask_info>* info, size_t* used);
+// mask_overlaps.hip: one set of packed masks on the device -- the instance table, the words, and the count (read from *n_ptr when
+// that is set) -- and the launch of the overlap kernel over rows x cols pairs of two of them (pairs past the sets' counts store
+// 0 / 0.0; d_order != nullptr: the set against itself in that order; either output may be null)
+struct OvSet {
+  const mnc_mask_info* info;
+  const unsigned long long* bits;
+  const int* n_ptr;
+  int n;
+};
+void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
+                     long long* d_inter, double* d_iou);
 void proposal_state_free(void* state);  // proposal.hip
 void comm_free(mnc_ctx* ctx);           // comm.hip
 void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,

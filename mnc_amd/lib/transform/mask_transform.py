@@ -4,7 +4,8 @@ Host orchestration only: 20 per-class NMS calls (HIP), a global score threshold,
 single call into the fused HIP mask-voting kernels (nms.mv.mv).  The reference's cv2-based cpu_mask_voting (image-space voting,
 cfg.TEST.USE_GPU_MASK_MERGE = False) runs on the GPU as well: cpu_mask_voting below (csrc/mv_image.hip).  instance_masks turns the
 voted instances into per-instance binary masks at image resolution on the GPU (csrc/inst_masks.hip); instance_masks_numpy is the
-same rule as a plain loop on the host; mask_rle / masks_from_rle take them to COCO's run-length encoding and back (csrc/mask_rle.hip)."""
+same rule as a plain loop on the host; mask_rle / masks_from_rle take them to COCO's run-length encoding and back (csrc/mask_rle.hip);
+mask_match matches detections to ground truths by COCO's rule (csrc/mask_match.hip), mask_match_numpy is its statement on the host."""
 import numpy as np
 
 from mnc_config import cfg
@@ -241,6 +242,18 @@ def mask_nms_numpy(pm, thresh, class_aware=False):
     """mask_nms as a plain loop on the host: the CPU statement of the rule."""
     from mnc_amd.masks import mask_nms_numpy as host_nms
     return host_nms(pm, thresh, class_aware)
+
+
+def mask_match(dt, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, return_iou=False):
+    """COCO's matching of one image's detections to its ground truths (two mnc_amd.masks.PackedMasks) on the GPU (mnc_mask_match /
+    mnc_mask_match_dev, csrc/mask_match.hip) -> mnc_amd.coco_eval.Match."""
+    return dt.match(gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, cfg.GPU_ID)
+
+
+def mask_match_numpy(dt, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, return_iou=False):
+    """mask_match as evaluateImg's plain loop on the host: the CPU statement of the rule."""
+    from mnc_amd.coco_eval import match_numpy as host_match
+    return host_match(dt, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou)
 
 
 def mask_rle(pm, H, W):

@@ -12,6 +12,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     mask_nms(pm, thresh)            greedy suppression by mask IoU in score order -> kept indices int32
     mask_overlaps_numpy / mask_nms_numpy   the CPU statements of both; PackedMasks.overlaps / .nms / .take the methods
     PackedMasks.rle_counts / .rle / .from_rle   COCO run-length encoding of the masks and the way back (mnc_amd/rle.py, n7)
+    PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -127,6 +128,18 @@ class PackedMasks(object):
         if dev is None:
             return mask_nms(self, thresh, class_aware)
         return dev.nms(thresh, class_aware)
+
+    def match(self, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, return_iou=False,
+              device_id=None):
+        """COCO's matching of these detections to the ground truths `gt` (a PackedMasks with classes, in the same image frame) by
+        the rule of mnc_amd.coco_eval.match_numpy (include/mnc_hip.h n8, csrc/mask_match.hip) on the GPU -> coco_eval.Match.  A
+        device-resident result is matched where it lies (mnc_mask_match_dev: only the tables come back); anything else goes
+        through mnc_mask_match on GPU device_id (None: cfg.GPU_ID)."""
+        from . import coco_eval
+        dev = self._device()
+        if dev is None:
+            return coco_eval.match(self, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, device_id)
+        return coco_eval.device_match(dev, len(self), gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major
