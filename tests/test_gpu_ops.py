@@ -781,6 +781,51 @@ def test_roi_warp_row_kernel_at_head_width(dev, pool2, C, tune):
     assert np.array_equal(res["3"].transpose(0, 3, 1, 2), want)
 
 
+@pytest.mark.parametrize("pool2", [0, 1])
+@pytest.mark.parametrize("P", [7, 14])
+@pytest.mark.parametrize("C", [64, 320])
+def test_roi_warp_row_kernel_segment_counts(dev, pool2, P, C, tune):
+    """ROI_ROW_SEGS with ROI_WARP_VARIANT=3: a row of PW positions is walked by nseg waves, positions [seg * PW / nseg,
+    (seg + 1) * PW / nseg) each.  1 (one wave per row), 3 and 4 (segments of unequal length: 14 = 4 + 5 + 5, 7 = 1 + 2 + 2 + 2),
+    7 and 14 (one position per wave at P = 7 / 14; 14 > 7 makes the launcher fall back to 1), 15 (> PW at both sizes: 1).  64
+    channels (a quarter of a wave's lanes busy) and 320 (a ragged second 256-channel piece); the roi set of
+    test_roi_warp_row_kernel_at_head_width.  Every count: the fp32 output bit-exact with the oracle, and the stage-major fp16
+    second output of mnc_roi_warp_sm bit for bit what mnc_fc_pack_act makes of those rows -- also with the fp32 output omitted."""
+    rng = np.random.default_rng(57 + 4 * pool2 + P + C)
+    H, W, R = 38, 63, 24
+    feat = rng.normal(size=(C, H, W)).astype(np.float32)
+    rois = _rois(rng, R, 1000, 600)
+    rois[5] = [0, 0, 0, 999, 40]                 # full width, thin
+    rois[6] = [0, 980, 560, 999, 599]            # bottom-right corner region
+    rois[7] = [0, 0, 0, 5, 5]                    # inside one cell
+    rois[8] = [0, -50, -30, 80, 70]              # partly left / above the map
+    rois[9] = [0, 300.5, 200.25, 310.75, 590.0]  # thin and tall
+    rois[10] = [0, 1200, 700, 1300, 800]         # wholly outside the map
+    want = native.maxpool2(native.roi_warp(feat, rois, 2 * P, 2 * P, 0.0625)) if pool2 else native.roi_warp(feat, rois, P, P, 0.0625)
+    want = np.ascontiguousarray(want.transpose(0, 2, 3, 1))
+    K = P * P * C
+    d_feat, d_rois = dev.put(to_c8(feat)), dev.put(rois)
+    d_out, d_out2 = dev.empty((R * K,), fill=np.nan), dev.empty((R * K,), fill=np.nan)
+    d_sm, d_sm2 = dev.empty((R * K * 2,), dtype=np.uint8, fill=0xAB), dev.empty((R * K * 2,), dtype=np.uint8, fill=0xAB)
+    d_shadow = dev.empty((R * K * 2,), dtype=np.uint8, fill=0)
+    dev.call("mnc_fc_pack_act", dev.put(want), d_shadow, R, K, 1)
+    shadow = dev.get(d_shadow, (R * K * 2,), dtype=np.uint8)
+    tune("ROI_WARP_VARIANT", "3")
+    for nseg in (1, 3, 4, 7, 14, 15):
+        tune("ROI_ROW_SEGS", nseg)
+        dev.put_into(d_out, np.full((R * K,), np.nan, np.float32))
+        dev.put_into(d_out2, np.full((R * K,), np.nan, np.float32))
+        for d in (d_sm, d_sm2):
+            dev.put_into(d, np.full((R * K * 2,), 0xAB, np.uint8))
+        dev.call("mnc_roi_warp", d_feat, C, H, W, d_rois, R, P, P, 0.0625, pool2, d_out)
+        assert np.array_equal(dev.get(d_out, (R, P, P, C)), want), nseg
+        dev.call("mnc_roi_warp_sm", d_feat, C, H, W, d_rois, R, P, P, 0.0625, pool2, d_out2, d_sm, 1)
+        assert np.array_equal(dev.get(d_out2, (R, P, P, C)), want), nseg
+        assert np.array_equal(dev.get(d_sm, (R * K * 2,), dtype=np.uint8), shadow), nseg
+        dev.call("mnc_roi_warp_sm", d_feat, C, H, W, d_rois, R, P, P, 0.0625, pool2, None, d_sm2, 1)
+        assert np.array_equal(dev.get(d_sm2, (R * K * 2,), dtype=np.uint8), shadow), nseg
+
+
 @pytest.mark.parametrize("fmt", [1, 2, 3])
 @pytest.mark.parametrize("variant", [None, "4", "8"])
 def test_per_roi_producers_write_the_fc_activation_form(dev, monkeypatch, fmt, variant, tune):
