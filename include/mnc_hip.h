@@ -344,6 +344,49 @@ MNC_API int mnc_mask_match(const int* dt_bounds, const long long* dt_offsets, co
                            double* iou, int device_id);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n9  The way in from annotation files: COCO polygon segmentations rasterised into the layout of n5 (csrc/mask_poly.hip) -- the
+ *     rule of the published maskApi.c (rleFrPoly per polygon, then the union of an annotation's polygons as annToRLE's
+ *     frPyObjects + merge).  The statement of the rule is mnc_amd/polygons.py:polygon_counts_numpy / masks_from_polygons_numpy.
+ *     One polygon of k >= 1 vertices (x_j, y_j) (doubles) in an H x W image; all arithmetic IEEE double in exactly this order,
+ *     nothing contracted into an FMA, (int) truncates toward zero:
+ *     1. X[j] = (int)(5 * x_j + .5), Y[j] = (int)(5 * y_j + .5) for j < k; X[k] = X[0], Y[k] = Y[0].
+ *     2. Edge j: xs, xe, ys, ye = X[j], X[j+1], Y[j], Y[j+1]; dx = |xe - xs|, dy = |ys - ye|; flip = (dx >= dy && xs > xe) ||
+ *        (dx < dy && ys > ye), and a flipped edge swaps xs with xe and ys with ye.  dx >= dy: s = (double)(ye - ys) / dx and for
+ *        d = 0 .. dx, t = flip ? dx - d : d, the point u = t + xs, v = (int)(ys + s * t + .5).  Otherwise s = (double)(xe - xs) / dy
+ *        and for d = 0 .. dy, t = flip ? dy - d : d, the point v = t + ys, u = (int)(xs + s * t + .5).  dx == dy == 0 gives the one
+ *        point (xs, ys) (the published code forms 0 / 0 for a v that is never read).  The points of all edges are one list.
+ *     3. Every point j >= 1 of the list with u[j] != u[j-1] is a crossing when xd = ((u[j] < u[j-1] ? u[j] : u[j] - 1) + .5) / 5
+ *        - .5 is an integer with 0 <= xd <= W - 1; its row is yd = ceil(clamp(((v[j] < v[j-1] ? v[j] : v[j-1]) + .5) / 5 - .5,
+ *        0, H)), and it toggles position a = (int)xd * H + (int)yd of the column-major pixel order of n7 (p = x * H + y).
+ *     4. The positions sorted, H * W appended, their differences taken and every run of length 0 merged into its neighbours are
+ *        the polygon's counts: pixel p is set when the number of toggles at positions <= p is odd.  A crossing clamped to yd == H
+ *        stands at position (x + 1) * H, the first pixel of the next column: parity is carried from a column into the next one.
+ *     The mask of an annotation is the OR of its polygons' masks; an annotation without polygons is empty.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  Annotation i owns the polygons poly_ptr[i] .. poly_ptr[i + 1]), polygon q the vertices vert_ptr[q] ..
+ * vert_ptr[q + 1]) (counted in vertices); xy holds two doubles per vertex, x then y.  Outputs exactly as mnc_mask_from_rle gives
+ * them: bounds [n][4] the tight box of the set pixels (rleToBbox; an empty mask gets (0, 0, -1, -1), no rows and area 0),
+ * offsets [n] (multiples of 8, in order without gaps), areas [n] (the true bit counts), the rows in bits (padding bits 0),
+ * *bits_bytes = the bytes they take.  bits == NULL: bounds, offsets, areas and *bits_bytes only; bits_cap < *bits_bytes is
+ * MNC_ERR_INVALID with *bits_bytes set.  n == 0 returns before any device work.
+ * The host rounds the vertices and makes the table of edges with the prefix of their walk lengths (O(vertices)); one thread per
+ * walk point forms its point and the one before it in closed form and XORs a crossing's bit into its polygon's toggle plane
+ * (atomic XOR commutes: the same bits from run to run); one workgroup per annotation turns the toggles into pixels -- a running
+ * XOR down every column plus the parity carried in from the columns to its left -- ORs the polygons together and reduces the
+ * tight box and the area; the host forms the offsets; a last kernel shifts the rows into the box and writes every word once.
+ * MNC_ERR_INVALID, checked on the host before anything is launched: n outside [0, 2048]; H or W outside [1, 32768] or
+ * H * W > 2^30; a negative or decreasing poly_ptr or vert_ptr (vert_ptr has poly_ptr[n] + 1 entries); a polygon without
+ * vertices; a coordinate that is NaN, infinite or of magnitude > 2^20; walks of more than 2^30 points in all. */
+MNC_API int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const long long* poly_ptr, int n, int H, int W,
+                                   int* bounds, long long* offsets, long long* areas, void* bits, size_t bits_cap,
+                                   size_t* bits_bytes, int device_id);
+/* For tools/mask_poly_bench.py.  on = 1: the following mnc_mask_from_polygons calls put a HIP event pair around their fill and
+ * launches (the plane fill, the toggle and fill kernels; the write kernel) and keep the sum of the last call, in milliseconds; on
+ * = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none;
+ * switching on forgets it. */
+MNC_API int mnc_mask_poly_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -12,6 +12,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     mask_nms(pm, thresh)            greedy suppression by mask IoU in score order -> kept indices int32
     mask_overlaps_numpy / mask_nms_numpy   the CPU statements of both; PackedMasks.overlaps / .nms / .take the methods
     PackedMasks.rle_counts / .rle / .from_rle   COCO run-length encoding of the masks and the way back (mnc_amd/rle.py, n7)
+    PackedMasks.from_polygons / .from_segmentations   COCO polygon segmentations rasterised into the layout (mnc_amd/polygons.py, n9)
     PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
@@ -163,6 +164,21 @@ class PackedMasks(object):
         bounds, decoded on the GPU (mnc_mask_from_rle)."""
         from . import rle
         return rle.masks_from_rle(rles, classes, scores)
+
+    @classmethod
+    def from_polygons(cls, segs, H, W, classes=None, scores=None):
+        """COCO polygon segmentations of one H x W image -- segs[i] the list of annotation i's polygons, each a flat list [x0, y0,
+        x1, y1, ...] -> PackedMasks with tight bounds, rasterised on the GPU by maskApi.c's rule (mnc_mask_from_polygons).  A
+        coordinate list of odd length raises ValueError naming its indices."""
+        from . import polygons
+        return polygons.masks_from_polygons(segs, H, W, classes, scores)
+
+    @classmethod
+    def from_segmentations(cls, segs, H, W, classes=None, scores=None):
+        """COCO `segmentation` entries of one H x W image, each a polygon list, a compressed RLE dict or an uncompressed RLE dict
+        -> PackedMasks in the entries' order: one device call per kind, merged on the host."""
+        from . import polygons
+        return polygons.masks_from_segmentations(segs, H, W, classes, scores)
 
     def take(self, indices):
         """-> a host PackedMasks of these instances, in this order: offsets repacked without gaps, the bits copied."""

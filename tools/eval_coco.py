@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Score a file of COCO results by COCO's `segm` protocol (mnc_amd/coco_eval.py; the matching on the GPU, csrc/mask_match.hip).
 
-    python tools/eval_coco.py --gt GT.json --dt RESULTS.json [--cpu] [--out FILE]
+    python tools/eval_coco.py --gt GT.json --dt RESULTS.json [--polygons] [--cpu] [--out FILE]
 
 RESULTS.json is what tools/demo.py --save-coco writes: a JSON array of {image_id, category_id, segmentation: {size, counts},
 score}.  GT.json holds `images` ({id, height, width}), `categories` ({id}) and `annotations` ({id, image_id, category_id,
 segmentation, iscrowd, area, optional ignore}).  A ground-truth segmentation must be run-length encoded -- compressed, or an
 uncompressed counts list -- which is what PackedMasks.from_rle accepts; a polygon is refused with the annotation's id
-(rasterising polygons is not done here, nor are the bbox and keypoints protocols).  The masks are decoded on the GPU
+(nor are the bbox and keypoints protocols done here).  With --polygons a segmentation of a ground truth or of a result may also
+be a list of polygons, as in standard COCO annotation files: it is rasterised by maskApi.c's rule (mnc_mask_from_polygons on the
+GPU, mnc_amd.polygons.masks_from_polygons_numpy with --cpu), and an annotation without `area` still takes it from the mask.  The masks are decoded on the GPU
 (mnc_mask_from_rle) and matched there (mnc_mask_match); --cpu uses the numpy statements of both
 (mnc_amd.rle.masks_from_counts_numpy, mnc_amd.coco_eval.match_numpy) and needs no GPU.  Prints the twelve lines in COCO's
 wording and writes them as JSON (--out, default: not written)."""
@@ -24,6 +26,7 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="COCO segm evaluation of a results file")
     p.add_argument("--gt", required=True, help="ground truth: images, categories, annotations with RLE segmentations")
     p.add_argument("--dt", required=True, help="results: what tools/demo.py --save-coco writes")
+    p.add_argument("--polygons", action="store_true", help="rasterise polygon segmentations instead of refusing them")
     p.add_argument("--cpu", action="store_true", help="the numpy statements instead of the GPU")
     p.add_argument("--out", default=None, metavar="FILE", help="write the twelve numbers as JSON")
     return p.parse_args(argv)
@@ -37,34 +40,48 @@ def _rle_of(seg, what, ident, size=None):
     return seg
 
 
-def _masks(rles, size, classes, scores, cpu):
-    """RLEs of one image -> PackedMasks (an image without any gets an empty set of its size)."""
+def _seg_of(seg, what, ident, size):
+    """--polygons: a list of polygons passes (mnc_amd.polygons checks its coordinates), anything else must be an RLE."""
+    if isinstance(seg, (list, tuple)):
+        return seg
+    return _rle_of(seg, what, ident, size)
+
+
+def _masks(rles, size, classes, scores, cpu, polygons=False):
+    """RLEs of one image -> PackedMasks (an image without any gets an empty set of its size); polygons: polygon lists among them."""
     from mnc_amd import rle
+    if polygons:
+        from mnc_amd.polygons import masks_from_segmentations
+        try:
+            return masks_from_segmentations(rles, size[0], size[1], np.asarray(classes, np.int32), np.asarray(scores, np.float32), cpu=cpu)
+        except ValueError as e:
+            raise SystemExit("eval_coco: %s" % e)
     run_ptr, runs, _, _ = rle.counts_of_rles(rles)
     make = rle.masks_from_counts_numpy if cpu else rle.masks_from_counts
     return make(run_ptr, runs, size[0], size[1], np.asarray(classes, np.int32), np.asarray(scores, np.float32))
 
 
-def evaluate(gt, results, cpu=False):
+def evaluate(gt, results, cpu=False, polygons=False):
     """gt: the ground-truth file's dict, results: the list of results -> a summarised mnc_amd.coco_eval.CocoSegmEval."""
+    check = _seg_of if polygons else _rle_of
     from mnc_amd.coco_eval import CocoSegmEval
     sizes = {im["id"]: (int(im["height"]), int(im["width"])) for im in gt["images"]}
     anns, dets = {i: [] for i in sizes}, {i: [] for i in sizes}
     for a in gt["annotations"]:
         if a["image_id"] not in sizes:
             raise SystemExit("eval_coco: annotation %r names the unknown image %r" % (a.get("id"), a["image_id"]))
-        _rle_of(a.get("segmentation"), "annotation", a.get("id"), sizes[a["image_id"]])
+        check(a.get("segmentation"), "annotation", a.get("id"), sizes[a["image_id"]])
         anns[a["image_id"]].append(a)
     for k, r in enumerate(results):
         if r["image_id"] not in sizes:
             raise SystemExit("eval_coco: result %d names the unknown image %r" % (k, r["image_id"]))
-        _rle_of(r.get("segmentation"), "result", k, sizes[r["image_id"]])
+        check(r.get("segmentation"), "result", k, sizes[r["image_id"]])
         dets[r["image_id"]].append(r)
     ev = CocoSegmEval(device=not cpu, classes=sorted(c["id"] for c in gt["categories"]))
     for i, size in sizes.items():
         a, d = anns[i], dets[i]
-        gm = _masks([x["segmentation"] for x in a], size, [x["category_id"] for x in a], np.zeros(len(a)), cpu)
-        dm = _masks([x["segmentation"] for x in d], size, [x["category_id"] for x in d], [x["score"] for x in d], cpu)
+        gm = _masks([x["segmentation"] for x in a], size, [x["category_id"] for x in a], np.zeros(len(a)), cpu, polygons)
+        dm = _masks([x["segmentation"] for x in d], size, [x["category_id"] for x in d], [x["score"] for x in d], cpu, polygons)
         ev.add(i, dm, gm, [int(x.get("iscrowd", 0)) for x in a], [int(x.get("ignore", 0)) for x in a],
                [float(x["area"]) if "area" in x else float(gm.areas[k]) for k, x in enumerate(a)])
     ev.summarize()
@@ -77,7 +94,7 @@ def main(argv=None):
         gt = json.load(f)
     with open(args.dt) as f:
         results = json.load(f)
-    ev = evaluate(gt, results, args.cpu)
+    ev = evaluate(gt, results, args.cpu, args.polygons)
     for line in ev.lines():
         print(line)
     if args.out:
