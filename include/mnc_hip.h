@@ -387,6 +387,41 @@ MNC_API int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, 
 MNC_API int mnc_mask_poly_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n10 Scoring a whole set: COCO's accumulate -- the match tables of n8 of all images turned into precision [T][R][K][A][M] and
+ *     recall [T][K][A][M] (the published cocoeval.py:accumulate) -- in one call (csrc/coco_accum.hip).  The statement of the rule
+ *     is mnc_amd/coco_eval.py:accumulate; mnc_amd/coco_eval.py:flatten_records makes the arguments.
+ *     The image records flattened in image order, within an image in the caller's index order: N detections with dt_class_idx [N]
+ *     (the index into the K evaluated classes, -1 for a class not evaluated), dt_score [N] float32, dt_rank [N] (the rank of n8),
+ *     dt_flags [A][T][N] bytes (bit 0: dt_match >= 0, bit 1: dt_ignore != 0); Gn ground truths with gt_class_idx [Gn] (-1 alike)
+ *     and gt_ignore [A][Gn] bytes 0 / 1; max_dets [M] (int), rec_thrs [R].
+ *     npig[k][a] = the ground truths of class k with gt_ignore[a] == 0; a cell (k, a, m) with npig == 0 stays -1 everywhere.
+ *     The list of cell (k, a, m): the detections with dt_class_idx == k and dt_rank < max_dets[m], by score descending, equal
+ *     scores (-0.0 == +0.0) in the order given (np.argsort(-scores, kind="mergesort") over the images' concatenation).  Per
+ *     threshold t along a list of nd entries: tp_i, fp_i the inclusive counts of flags == 1 (matched, not ignored) and flags == 0
+ *     (not matched, not ignored); rc_i = (double)tp_i / (double)npig; pr_i = (double)tp_i / ((double)(fp_i + tp_i) + 2^-52);
+ *     recall[t][k][a][m] = rc_{nd-1} (0 when nd == 0); precision[t][r][k][a][m] = max over j >= at_r of pr_j, at_r the first i
+ *     with rc_i >= rec_thrs[r] (0 when there is none).  All arithmetic IEEE double in this order.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  Outputs precision [T][R][K][A][M], recall [T][K][A][M], npig [K][A] (may be NULL).  One stable
+ * least-significant-digit radix sort of all detections by (class, score descending) on the device (per pass: tile histograms, a
+ * scan, a scatter ranked by wave ballots), the flag planes gathered into that order once, then one workgroup per (k, a, m, t)
+ * over its class segment: a count, and a walk from the right with the carried maximum of pr.  Integer atomics only where the
+ * result is a sum (histograms, npig), no floating-point atomics: the same bits from run to run, and the bits of the host rule.
+ * N == 0 or Gn == 0 returns before any device work with the tables as the rule gives them (-1 where npig == 0, else 0).
+ * MNC_ERR_INVALID, checked on the host before anything is launched: N or Gn outside [0, 2^24]; K outside [1, 4096]; T outside
+ * [1, 16]; A outside [1, 8]; M outside [1, 8]; R outside [1, 1024]; a max_det outside [1, 2048]; a class index outside [-1, K);
+ * a negative rank; a NaN score or recall threshold; a flag byte above 3; an ignore byte above 1; a NULL precision or recall (or
+ * a NULL input that has entries). */
+MNC_API int mnc_coco_accumulate(const int* dt_class_idx, const float* dt_score, const int* dt_rank, const unsigned char* dt_flags,
+                                int N, const int* gt_class_idx, const unsigned char* gt_ignore, int Gn, int K, int T, int A,
+                                const int* max_dets, int M, const double* rec_thrs, int R, double* precision, double* recall,
+                                long long* npig, int device_id);
+/* For tools/coco_accum_bench.py.  on = 1: the following mnc_coco_accumulate calls put a HIP event pair around their launches (from
+ * the keys to the cells, without the copies) and keep the last call's time in milliseconds; on = 0: they do not (the default).
+ * *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on forgets it. */
+MNC_API int mnc_coco_accum_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -7,12 +7,18 @@ cocoeval.py (computeIoU, evaluateImg, accumulate, summarize) and of rleIou in ma
     match(dt, gt, iscrowd, ...)         the same tables through mnc_mask_match (the GPU); PackedMasks.match is the method, which
                                         matches a device-resident result where it lies (mnc_mask_match_dev)
     accumulate(images, ...)             per-image tables -> precision [T, R, K, A, M] and recall [T, K, A, M], host numpy
+    flatten_records(images, ...)        the image records as the flat arrays of mnc_coco_accumulate (include/mnc_hip.h n10)
+    accumulate_flat_numpy(flat, ...)    the same tables from the flat arrays by the closed form csrc/coco_accum.hip uses (one stable
+                                        sort by (class, score); per cell the least tp count that reaches each recall threshold)
+    accumulate_flat(flat, ...)          mnc_coco_accumulate on those arrays
+    accumulate_device(images, ...)      accumulate through it (the GPU): the same tables bit for bit
     summarize(acc)                      -> the twelve numbers, an ordered dict
     CocoSegmEval                        .add(image_id, dt, gt, iscrowd, ...) per image, .accumulate(), .summarize(), .stats
 
 Every table of a match is in the caller's index order with -1 for "none": rank int32 [D], dt_match int32 [A, T, D], dt_ignore uint8
 [A, T, D], gt_match int32 [A, T, G], gt_ignore uint8 [A, G], iou float64 [D, G] (None unless asked for).  There is no fallback:
-without the library or a GPU match() raises; device=False / match_numpy is the path that needs neither."""
+without the library or a GPU match() and accumulate_device() raise; device=False / match_numpy / accumulate is the path that needs
+neither."""
 import collections
 import ctypes
 
@@ -23,6 +29,14 @@ from . import _lib
 MAX_N = 2048
 MAX_T = 16
 MAX_A = 8
+# csrc/coco_accum.hip: the keys of one sort workgroup and the elements of one step of a cell's walk (tests size their cases
+# from these; tests/test_coco_accum_host.py checks them against the source), and the limits of mnc_coco_accumulate
+ACCUM_SORT_TILE = 2048
+ACCUM_SCAN_CHUNK = 1024
+ACCUM_MAX_N = 1 << 24
+ACCUM_MAX_K = 4096
+ACCUM_MAX_M = 8
+ACCUM_MAX_R = 1024
 IOU_THRS = np.linspace(.5, .95, 10)
 AREA_RNGS = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], np.float64)
 AREA_LABELS = ("all", "small", "medium", "large")
@@ -251,6 +265,161 @@ def accumulate(images, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, classes
             "rec_thrs": rec_thrs}
 
 
+def _accum_params(iou_thrs, area_rngs, max_dets, rec_thrs):
+    thrs = np.asarray(IOU_THRS if iou_thrs is None else iou_thrs, np.float64).reshape(-1)
+    rngs = np.asarray(AREA_RNGS if area_rngs is None else area_rngs, np.float64).reshape(-1, 2)
+    rec_thrs = np.ascontiguousarray(REC_THRS if rec_thrs is None else rec_thrs, np.float64).reshape(-1)
+    return thrs, rngs, [int(m) for m in max_dets], rec_thrs
+
+
+def _class_list(images, classes):
+    if classes is None:
+        seen = [im[key] for im in images for key in ("dt_classes", "gt_classes")]
+        classes = np.unique(np.concatenate(seen)) if seen else np.zeros(0, np.int32)
+    return [int(k) for k in classes]
+
+
+def _class_index(values, uniq):
+    """The index of each value in the sorted, distinct `uniq`, -1 where it is not there.  -> int32."""
+    values = np.asarray(values, np.int64).reshape(-1)
+    if not len(uniq):
+        return np.full(len(values), -1, np.int32)
+    pos = np.minimum(np.searchsorted(uniq, values), len(uniq) - 1)
+    return np.where(uniq[pos] == values, pos, -1).astype(np.int32)
+
+
+def flatten_records(images, classes, max_dets, T=None, A=None):
+    """The image_record()s, in the order given, as the flat arrays of mnc_coco_accumulate: within an image the caller's index
+    order; a detection whose rank reaches the largest of max_dets is in no list and is left out.  classes: the sorted, distinct
+    category ids that are evaluated.  T, A: the planes of an empty list of images (else taken from the records).  -> {"dt_class_idx"
+    int32 [N], "dt_score" float32 [N], "dt_rank" int32 [N], "dt_flags" uint8 [A, T, N] (bit 0: matched, bit 1: ignored),
+    "gt_class_idx" int32 [Gn], "gt_ignore" uint8 [A, Gn]}.  No loop over classes."""
+    images = list(images)
+    uniq = np.asarray(classes, np.int64).reshape(-1)
+    if len(uniq) > 1 and not (np.diff(uniq) > 0).all():
+        raise ValueError("flatten_records: classes must be sorted and distinct")
+    for im in images:
+        A = im["dt_match"].shape[0] if A is None else A
+        T = im["dt_match"].shape[1] if T is None else T
+        D, G = len(im["dt_classes"]), len(im["gt_classes"])
+        if im["dt_match"].shape != (A, T, D) or im["dt_ignore"].shape != (A, T, D) or im["gt_ignore"].shape != (A, G) or \
+                len(im["dt_scores"]) != D or len(im["rank"]) != D:
+            raise ValueError("flatten_records: an image record's tables do not have the shapes [%d, %d, D] / [%d, G]" % (A, T, A))
+    A, T = int(A or 0), int(T or 0)
+
+    def cat(parts, dtype, shape, axis=0):
+        return np.ascontiguousarray(np.concatenate(parts, axis=axis), dtype) if parts else np.zeros(shape, dtype)
+
+    rank = cat([im["rank"] for im in images], np.int32, 0)
+    keep = rank < max(int(m) for m in max_dets)
+    matched = cat([im["dt_match"] for im in images], np.int32, (A, T, 0), 2) >= 0
+    ignored = cat([im["dt_ignore"] for im in images], np.uint8, (A, T, 0), 2) != 0
+    flags = matched.astype(np.uint8) | (ignored.astype(np.uint8) << 1)
+    return {"dt_class_idx": _class_index(cat([im["dt_classes"] for im in images], np.int64, 0)[keep], uniq),
+            "dt_score": cat([im["dt_scores"] for im in images], np.float32, 0)[keep],
+            "dt_rank": np.ascontiguousarray(rank[keep]),
+            "dt_flags": np.ascontiguousarray(flags[:, :, keep]),
+            "gt_class_idx": _class_index(cat([im["gt_classes"] for im in images], np.int64, 0), uniq),
+            "gt_ignore": cat([im["gt_ignore"] for im in images], np.uint8, (A, 0), 1)}
+
+
+def accumulate_flat_numpy(flat, K, max_dets, rec_thrs):
+    """What csrc/coco_accum.hip computes, stated on the host: one stable sort of all detections by (class, score descending);
+    per cell, tp being non-decreasing and c -> c / npig monotone, the first entry with rc >= rec_thrs[r] is the one where tp
+    first reaches need_r, the least count c with c / npig >= rec_thrs[r] (entry 0 when need_r == 0); an entry at or above the
+    max_det counts as neither tp nor fp and repeats its left neighbour's pr.  -> precision [T, R, K, A, M], recall [T, K, A, M],
+    npig int64 [K, A]; equal to accumulate's bit for bit (tests/test_coco_accum_host.py)."""
+    cls, rank, flags = flat["dt_class_idx"], flat["dt_rank"], flat["dt_flags"]
+    A, T, N = flags.shape
+    R, M = len(rec_thrs), len(max_dets)
+    score = flat["dt_score"].astype(np.float32) + np.float32(0)
+    order = np.lexsort((-score, np.where(cls < 0, K, cls)))                     # (stable: equal keys keep the input order)
+    seg = np.searchsorted(np.where(cls < 0, K, cls)[order], np.arange(K + 1))
+    npig = np.zeros((K, A), np.int64)
+    for a in range(A):
+        g = flat["gt_class_idx"][flat["gt_ignore"][a] == 0]
+        npig[:, a] = np.bincount(g[g >= 0], minlength=K)[:K]
+    precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
+    for k in range(K):
+        sel = order[seg[k]:seg[k + 1]]
+        for a in range(A):
+            if npig[k, a] == 0:
+                continue
+            counts = np.arange(len(sel) + 2, dtype=np.float64) / float(npig[k, a])
+            need = np.searchsorted(counts, rec_thrs, side="left")                 # the least c with c / npig >= the threshold
+            for m, max_det in enumerate(max_dets):
+                inside = rank[sel] < max_det
+                for t in range(T):
+                    f = flags[a, t, sel]
+                    tp, fp = np.cumsum(inside & (f == 1)), np.cumsum(inside & (f == 0))
+                    recall[t, k, a, m] = (tp[-1] / float(npig[k, a])) if len(sel) else 0.0
+                    pr = tp.astype(np.float64) / ((fp + tp).astype(np.float64) + np.spacing(1))
+                    best = np.maximum.accumulate(pr[::-1])[::-1]
+                    at = np.where(need == 0, 0, np.searchsorted(tp, need, side="left"))
+                    q = np.zeros(R)
+                    q[at < len(sel)] = best[at[at < len(sel)]]
+                    precision[t, :, k, a, m] = q
+    return precision, recall, npig
+
+
+def _check_flat(who, flat, K, T, A, max_dets, rec_thrs):
+    """mnc_coco_accumulate's refusals (ValueError in the place of MNC_ERR_INVALID)."""
+    N, Gn = len(flat["dt_class_idx"]), len(flat["gt_class_idx"])
+    if N > ACCUM_MAX_N or Gn > ACCUM_MAX_N:
+        raise ValueError("%s: %d detections / %d ground truths not in [0, 2^24]" % (who, N, Gn))
+    if not 1 <= K <= ACCUM_MAX_K or not 1 <= T <= MAX_T or not 1 <= A <= MAX_A or not 1 <= len(max_dets) <= ACCUM_MAX_M or \
+            not 1 <= len(rec_thrs) <= ACCUM_MAX_R:
+        raise ValueError("%s: K=%d not in [1, %d], T=%d not in [1, %d], A=%d not in [1, %d], M=%d not in [1, %d] or R=%d not in [1, %d]"
+                         % (who, K, ACCUM_MAX_K, T, MAX_T, A, MAX_A, len(max_dets), ACCUM_MAX_M, len(rec_thrs), ACCUM_MAX_R))
+    if any(not 1 <= m <= MAX_N for m in max_dets):
+        raise ValueError("%s: a max_det not in [1, %d]" % (who, MAX_N))
+    if np.isnan(rec_thrs).any() or np.isnan(flat["dt_score"]).any():
+        raise ValueError("%s: a NaN score or recall threshold" % who)
+    if (flat["dt_rank"] < 0).any():
+        raise ValueError("%s: a negative rank" % who)
+    if flat["dt_flags"].shape != (A, T, N) or flat["gt_ignore"].shape != (A, Gn) or (flat["gt_ignore"] > 1).any():
+        raise ValueError("%s: tables not of the shapes [%d, %d, N] / [%d, Gn], or an ignore value other than 0 / 1" % (who, A, T, A))
+
+
+def accumulate_flat(flat, K, max_dets, rec_thrs, device_id=None):
+    """mnc_coco_accumulate on the flat arrays of flatten_records (T and A are the planes of flat["dt_flags"]).  -> precision
+    [T, R, K, A, M], recall [T, K, A, M], npig int64 [K, A]."""
+    from .masks import _device_id
+    A, T = flat["dt_flags"].shape[:2]
+    max_dets = [int(m) for m in max_dets]
+    rec_thrs = np.ascontiguousarray(rec_thrs, np.float64).reshape(-1)
+    _check_flat("accumulate_flat", flat, K, T, A, max_dets, rec_thrs)
+    R, M = len(rec_thrs), len(max_dets)
+    precision, recall, npig = np.zeros((T, R, K, A, M)), np.zeros((T, K, A, M)), np.zeros((K, A), np.int64)
+    md = np.asarray(max_dets, np.int32)
+    _lib.call("mnc_coco_accumulate", _lib.ptr(flat["dt_class_idx"]), _lib.ptr(flat["dt_score"]), _lib.ptr(flat["dt_rank"]),
+              _lib.ptr(flat["dt_flags"]), len(flat["dt_class_idx"]), _lib.ptr(flat["gt_class_idx"]), _lib.ptr(flat["gt_ignore"]),
+              len(flat["gt_class_idx"]), K, T, A, _lib.ptr(md), M, _lib.ptr(rec_thrs), R, _lib.ptr(precision), _lib.ptr(recall),
+              _lib.ptr(npig), _device_id(device_id))
+    return precision, recall, npig
+
+
+def accumulate_device(images, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, classes=None, rec_thrs=None, device_id=None):
+    """accumulate on the GPU (mnc_coco_accumulate, csrc/coco_accum.hip): the same arguments, the same dict, the same bits.  The
+    records are flattened on the host (flatten_records), sorted and accumulated in one call.  Invalid arguments raise ValueError or
+    _lib.MncError (MNC_ERR_INVALID) before anything is launched; without the library or a GPU it raises."""
+    thrs, rngs, max_dets, rec_thrs = _accum_params(iou_thrs, area_rngs, max_dets, rec_thrs)
+    images = list(images)
+    classes = _class_list(images, classes)
+    T, R, K, A, M = len(thrs), len(rec_thrs), len(classes), len(rngs), len(max_dets)
+    out = {"classes": classes, "iou_thrs": thrs, "area_rngs": rngs, "max_dets": max_dets, "rec_thrs": rec_thrs}
+    if K == 0:                                                     # nothing to evaluate: accumulate's empty tables
+        return dict(out, precision=-np.ones((T, R, 0, A, M)), recall=-np.ones((T, 0, A, M)))
+    if M == 0:
+        raise ValueError("accumulate_device: no max_dets")
+    uniq, inverse = np.unique(np.asarray(classes, np.int64), return_inverse=True)
+    flat = flatten_records(images, uniq, max_dets, T, A)
+    precision, recall, _ = accumulate_flat(flat, len(uniq), max_dets, rec_thrs, device_id)
+    if len(uniq) != K or (inverse != np.arange(K)).any():          # classes given unsorted or twice: the tables in their order
+        precision, recall = np.ascontiguousarray(precision[:, :, inverse]), np.ascontiguousarray(recall[:, inverse])
+    return dict(out, precision=precision, recall=recall)
+
+
 def _mean(s):
     s = s[s > -1]
     return float(np.mean(s)) if s.size else -1.0
@@ -297,13 +466,16 @@ def summary_lines(acc, stats):
 
 class CocoSegmEval(object):
     """COCO's segm protocol over the images added.  device=True matches on the GPU (PackedMasks.match: a device-resident result
-    where it lies), device=False with match_numpy, so that the whole path works without one."""
+    where it lies), device=False with match_numpy, so that the whole path works without one.  accumulate_on_device: the tables
+    through accumulate_device (True) or accumulate (False); None: as `device`.  device=False with nothing else said never touches
+    the GPU.  The tables, and so the stats, are the same bits either way."""
 
-    def __init__(self, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, device=True, classes=None):
+    def __init__(self, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, device=True, classes=None, accumulate_on_device=None):
         self.iou_thrs = np.asarray(IOU_THRS if iou_thrs is None else iou_thrs, np.float64).reshape(-1)
         self.area_rngs = np.asarray(AREA_RNGS if area_rngs is None else area_rngs, np.float64).reshape(-1, 2)
         self.max_dets = tuple(int(m) for m in max_dets)
         self.device, self.classes = bool(device), classes
+        self.accumulate_on_device = self.device if accumulate_on_device is None else bool(accumulate_on_device)
         self._images = {}
         self.eval = self.stats = None
 
@@ -322,7 +494,8 @@ class CocoSegmEval(object):
             ids = sorted(self._images)
         except TypeError:
             ids = list(self._images)
-        self.eval = accumulate([self._images[i] for i in ids], self.iou_thrs, self.area_rngs, self.max_dets, self.classes)
+        run = accumulate_device if self.accumulate_on_device else accumulate
+        self.eval = run([self._images[i] for i in ids], self.iou_thrs, self.area_rngs, self.max_dets, self.classes)
         return self.eval
 
     def summarize(self):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Score a file of COCO results by COCO's `segm` protocol (mnc_amd/coco_eval.py; the matching on the GPU, csrc/mask_match.hip).
+"""Score a file of COCO results by COCO's `segm` protocol (mnc_amd/coco_eval.py; the matching on the GPU, csrc/mask_match.hip, and
+the accumulation of the precision / recall tables too, csrc/coco_accum.hip).
 
     python tools/eval_coco.py --gt GT.json --dt RESULTS.json [--polygons] [--cpu] [--out FILE]
 
@@ -10,8 +11,10 @@ uncompressed counts list -- which is what PackedMasks.from_rle accepts; a polygo
 (nor are the bbox and keypoints protocols done here).  With --polygons a segmentation of a ground truth or of a result may also
 be a list of polygons, as in standard COCO annotation files: it is rasterised by maskApi.c's rule (mnc_mask_from_polygons on the
 GPU, mnc_amd.polygons.masks_from_polygons_numpy with --cpu), and an annotation without `area` still takes it from the mask.  The masks are decoded on the GPU
-(mnc_mask_from_rle) and matched there (mnc_mask_match); --cpu uses the numpy statements of both
-(mnc_amd.rle.masks_from_counts_numpy, mnc_amd.coco_eval.match_numpy) and needs no GPU.  Prints the twelve lines in COCO's
+(mnc_mask_from_rle), matched there (mnc_mask_match) and the matches of all images accumulated there in one call
+(mnc_coco_accumulate): the tool follows the evaluator, CocoSegmEval(device=True).  With --cpu everything runs in numpy -- the
+statements of all three (mnc_amd.rle.masks_from_counts_numpy, mnc_amd.coco_eval.match_numpy, mnc_amd.coco_eval.accumulate) --
+and no GPU is needed or touched.  Prints the twelve lines in COCO's
 wording and writes them as JSON (--out, default: not written)."""
 import argparse
 import json
