@@ -637,8 +637,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(const float* __re
 // padding: a lane's 144 bytes are 9 x 16, and an odd multiple of 16 bytes as lane pitch is what keeps ds_read_b128 free of bank
 // conflicts.
 __global__ void pack_conv3x3_wino4_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin) {
-  const double G[6][3] = {{0.25, 0.0, 0.0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                          {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
+  // 24 G: whole numbers, so that G f G^T = (24 G) f (24 G)^T / 576 is evaluated without the representation error of 1/6, 1/12 and
+  // 1/24 -- with those, terms that cancel exactly left residues of ~1e-17 where the transformed weight is 0, and weights that are
+  // whole multiples of 576 units did not pack to whole multiples of the unit (tests/test_gpu_exact_arithmetic.py)
+  const double G[6][3] = {{6.0, 0.0, 0.0}, {-4.0, -4.0, -4.0}, {-4.0, 4.0, -4.0}, {1.0, 2.0, 4.0}, {1.0, -2.0, 4.0}, {0.0, 0.0, 24.0}};
   const int ncot = Cout >> 5;
   const long items = (long)(Cin >> 3) * ncot * 2 * 2 * 64;        // (cb, ct, h, hp, lane)
   for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < items; r += (long)gridDim.x * blockDim.x) {
@@ -652,12 +654,12 @@ __global__ void pack_conv3x3_wino4_kernel(const float* __restrict__ w, float* __
       for (int cg = 0; cg < 2; ++cg) {
         const int co = ct * 32 + cg * 16 + i;
         const float* f = w + ((long)co * Cin + ci) * 9;
-        double tmp[3];                                            // row `row` of G f
+        double tmp[3];                                            // row `row` of 24 G f
 #pragma unroll
         for (int b = 0; b < 3; ++b) tmp[b] = G[row][0] * (double)f[b] + G[row][1] * (double)f[3 + b] + G[row][2] * (double)f[6 + b];
 #pragma unroll
-        for (int b = 0; b < 6; ++b)                               // (G f) G^T, column b
-          dst[12 * m + 2 * b + cg] = (float)(tmp[0] * G[b][0] + tmp[1] * G[b][1] + tmp[2] * G[b][2]);
+        for (int b = 0; b < 6; ++b)                               // (24 G f) (24 G)^T / 576, column b
+          dst[12 * m + 2 * b + cg] = (float)((tmp[0] * G[b][0] + tmp[1] * G[b][1] + tmp[2] * G[b][2]) / 576.0);
       }
     }
   }

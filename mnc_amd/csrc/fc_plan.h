@@ -336,6 +336,9 @@ inline FcPlan fc_lowp_pair_plan(const FcCall& c, const int* t) {
   bool paired = M > 160 && one_launch && N % 256 == 0 && N >= 512 && !fc_small(M, N, K) && tune(t, T_FCX3_WIDE, 1) != 0 &&
                 fc_wide_in_range(stages, (c.pre[0] || c.pre[1]) ? c.mstride : M) && !tune_set(t, T_FCX3_TILE) &&
                 tune(t, T_FUSE_SMALL, 1) != 0;
+  // (one launch reads both panels with ONE row stride: a panel converted here has M rows per stage, so a single pre-packed panel
+  // of another stride keeps the singles -- decided here, before the launcher enqueues a conversion)
+  if (c.pre[0] != c.pre[1] && c.mstride != M) paired = false;
   const int min_stages = fc_lowp_min_stages(f16, mt);
   int splits = 1;
   if (paired && tm > 1) {

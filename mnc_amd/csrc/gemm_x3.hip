@@ -812,6 +812,9 @@ static int fc_lowp_pair(mnc_ctx* ctx, const char* what, const float* d_a0, const
     return fc_lowp<F16>(ctx, what, d_a1, d_pre1, d_a1 ? M : mstride, d_w1, d_bias1, d_out1, M, N, K, ldc, act, d_osm1,
                         d_osm1 ? osm_fmt : 0, M, 0);
   }
+  // one launch reads both panels with ONE row stride; a panel converted below has M rows per stage.  fc_lowp_pair_plan keeps a single
+  // pre-packed panel of another stride as two singles: held here, before anything is enqueued
+  MNC_REQUIRE((d_pre0 != nullptr) == (d_pre1 != nullptr) || mstride == M, "%s: the two activation panels need one row stride", what);
   const int tn = p.tn / 2, tm = p.tm, splits = p.splits, kper = p.kper;      // (tn: column tiles of ONE product)
   // scratch arena: [partial sums of both products | activations that arrive as fp32, in their 2-byte stage-major form]
   const size_t part_bytes = p.part_bytes, conv_bytes = p.conv_bytes;
@@ -835,7 +838,6 @@ static int fc_lowp_pair(mnc_ctx* ctx, const char* what, const float* d_a0, const
       conv += conv_bytes;
     }
   }
-  MNC_REQUIRE(ms[0] == ms[1], "%s: the two activation panels need one row stride", what);
   {
     const double flops = 4.0 * M * (double)N * K, bytes = (F16 ? 4.0 : 8.0) * ((double)N * K + (double)M * K) + 8.0 * (double)M * N;
     LaunchScope ls(ctx, F16 == 2 ? "fc_bf16" : F16 ? "fc_f16" : "fc_bf16x3", flops, bytes);

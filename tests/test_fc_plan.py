@@ -256,6 +256,24 @@ def test_what_keeps_an_fp32_pair_two_singles(shim):
     assert shim.plan(FC_PAIR, call, tuning=("FC_DMA_ABL", 16), tuning_build=1)["two_singles"]
 
 
+def test_a_mixed_reduced_precision_pair_of_two_row_strides_is_two_singles(shim):
+    """One fp32 input and one stage-major input (include/mnc_hip.h: each product takes either form): the paired launch reads both
+    panels with one row stride and the panel converted in the launcher has M rows per stage, so a pre-packed panel of m_stride > M
+    beside an fp32 one is planned as the two single calls -- in the plan, before anything is enqueued -- and each single keeps its own
+    stride.  m_stride == M, or both inputs of one form, stay one launch."""
+    for f16 in (0, 1, 2):
+        for M, N, K in ((290, 2048, 8192), (300, 4096, 25088), (640, 512, 8192)):
+            base = dict(M=M, N=N, K=K, ldc=2 * N, f16=f16)
+            for pre in ((1, 0), (0, 1)):
+                call = dict(base, pre0=pre[0], pre1=pre[1])
+                assert not shim.plan(LOWP_PAIR, dict(call, mstride=M))["two_singles"], (f16, M, pre)
+                assert shim.plan(LOWP_PAIR, dict(call, mstride=M + 20))["two_singles"], (f16, M, pre)
+                ls = shim.launches(LOWP_PAIR, dict(call, mstride=M + 20))
+                assert [(c["pre0"], c["mstride"]) for _, c, _ in ls] == [(pre[0], M + 20 if pre[0] else M), (pre[1], M + 20 if pre[1] else M)]
+            assert not shim.plan(LOWP_PAIR, dict(base, pre0=1, pre1=1, mstride=M + 20))["two_singles"]
+            assert not shim.plan(LOWP_PAIR, dict(base, mstride=0))["two_singles"]
+
+
 def _shapes():
     for r in grid():
         yield r
