@@ -422,6 +422,61 @@ MNC_API int mnc_coco_accumulate(const int* dt_class_idx, const float* dt_score, 
 MNC_API int mnc_coco_accum_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n11 Scoring the contours: the boundary bands of packed masks and COCO's matching on min(mask IoU, boundary IoU)
+ *     (csrc/mask_boundary.hip, csrc/mask_match.hip) -- Boundary IoU (Cheng et al., CVPR 2021; iouType = "boundary" of the COCO
+ *     toolkit, the measure of LVIS) on the layout of n5.  The statements of the rule are mnc_amd/boundary.py:boundary_numpy and
+ *     mnc_amd/coco_eval.py:match_boundary_numpy.
+ *     The distance is made on the host: d = max(1, (int)round(ratio * sqrt(H * H + W * W))), round half to even (Python 3's round
+ *     of the double), ratio 0.02 by default (mnc_amd/boundary.py:boundary_distance; 375 x 500 gives 12, 600 x 1000 gives 23).
+ *     The boundary of a mask M in an H x W image at distance d >= 1: M is first cropped to the image (bounds may leave it;
+ *     padding bits are never trusted).  E = the pixels p of M for which every q with |qx - px| <= d and |qy - py| <= d lies
+ *     inside the image and in M; B = M \ E.  This is the published mask_to_boundary: a one-pixel zero border, cv2.erode with a
+ *     3 x 3 kernel of ones d times, the border removed, the difference.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  The set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds (the areas
+ * are not needed).  The result has the layout of n5: instance i has the input bounds intersected with [0, W-1] x [0, H-1], not
+ * tightened; an instance without rows or with an empty intersection gets (0, 0, -1, -1), no rows and area 0; out_offsets [n] are
+ * multiples of 8, in order without gaps; out_areas [n] are the true bit counts of B; padding bits are 0.  out_bounds, out_offsets
+ * and *bits_bytes follow from the bounds alone and are computed on the host before anything is launched: with out_bits == NULL the
+ * call returns them and launches nothing (out_areas may be NULL then); bits_cap < *bits_bytes is MNC_ERR_INVALID with *bits_bytes
+ * set.  n == 0 returns before any device work.
+ * The erosion is separable.  One thread per output word erodes along the row -- in the word itself a log-step shift-OR of the
+ * mask's zeros by min(d, 63), from each of the ceil(d / 64) words to either side the reach of its nearest zero, everything beyond
+ * the row's ends counting as zero -- into a scratch plane in device memory; for d > 4 a second kernel turns blocks of 2d + 1 rows
+ * of every word column into prefix and suffix ANDs, so that the last kernel reads two words per output word whatever d is (for
+ * d <= 4 it reads the 2d + 1 rows themselves); it stores B = M & ~E, every word once (nothing is zeroed beforehand), and adds
+ * the bit counts to the areas with integer atomics: the same bits from run to run.
+ * MNC_ERR_INVALID, checked on the host before anything is launched: everything mnc_mask_rle refuses about a set (n outside
+ * [0, 2048], |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or not a multiple of 8, rows
+ * that reach past bytes); H or W outside [1, 32768]; d outside [1, 1024]. */
+MNC_API int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int H, int W,
+                              int d, int* out_bounds, long long* out_offsets, long long* out_areas, void* out_bits,
+                              size_t bits_cap, size_t* bits_bytes, int device_id);
+/* mnc_mask_match (n8; the same 23 inputs, the same five tables) on the overlap min(iou[d][g], biou[d][g]) in an H x W image at
+ * distance d.  With Db, Gb the boundaries of the detections and of the ground truths as mnc_mask_boundary gives them, biou[d][g]
+ * is iou exactly as n8 defines it, computed on (Db, Gb): inter the count of n6 on the two bands, union = area(Db[d]) +
+ * area(Gb[g]) - inter, for a crowd ground truth area(Db[d]); union < 1 gives 0.0; (double)inter / (double)union.  Everything else
+ * of the rule is n8's: ranks and class lists, the area-range rules on dt_areas and gt_eval_area (not on the bands' areas), the
+ * min(thr, 1 - 1e-10) rule and the tie rules.  iou [nd][ng] (may be NULL) receives the minimum that was matched on, biou [nd][ng]
+ * (may be NULL) the boundary IoU alone.  Both sets are uploaded once; both boundary sets are made on the device and never visit the
+ * host; the counts of n6 run twice, on the masks and on the bands; then the lists and the cells of n8 run on the minimum.  nd == 0
+ * or ng == 0 returns before any device work, as n8 does.  MNC_ERR_INVALID, checked on the host before anything is launched:
+ * everything mnc_mask_match refuses, H or W outside [1, 32768], d outside [1, 1024].  (There is no form that reads a
+ * device-resident result: PackedMasks.match_boundary fetches such a result first.) */
+MNC_API int mnc_mask_match_boundary(const int* dt_bounds, const long long* dt_offsets, const long long* dt_areas, const void* dt_bits,
+                                    size_t dt_bytes, int nd, const int* dt_classes, const float* dt_scores, const int* gt_bounds,
+                                    const long long* gt_offsets, const long long* gt_areas, const void* gt_bits, size_t gt_bytes,
+                                    int ng, const int* gt_classes, const unsigned char* gt_crowd, const unsigned char* gt_ignore_in,
+                                    const double* gt_eval_area, const double* iou_thrs, int T, const double* area_rngs, int A,
+                                    int max_det, int H, int W, int d, int* rank, int* dt_match, unsigned char* dt_ignore,
+                                    int* gt_match, unsigned char* gt_ignore, double* iou, double* biou, int device_id);
+/* For tools/mask_boundary_bench.py.  on = 1: the following mnc_mask_boundary and mnc_mask_match_boundary calls put a HIP event
+ * pair around their launches (the boundary kernels; for the matching also the uploads of the ground truths, the fills, the counts
+ * and the matching kernels) and keep the last call's time in milliseconds; on = 0: they do not (the default).  *last_ms (may be
+ * NULL) receives the figure kept before this call, -1.0 when there is none; switching on forgets it. */
+MNC_API int mnc_mask_boundary_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -6,6 +6,8 @@ cocoeval.py (computeIoU, evaluateImg, accumulate, summarize) and of rleIou in ma
                                         of several equal the highest index; not-ignored before ignored)
     match(dt, gt, iscrowd, ...)         the same tables through mnc_mask_match (the GPU); PackedMasks.match is the method, which
                                         matches a device-resident result where it lies (mnc_mask_match_dev)
+    match_boundary_numpy(dt, gt, H, W, ...) / match_boundary(...)   the matching on min(mask IoU, boundary IoU) (n11,
+                                        mnc_amd/boundary.py): the statement and mnc_mask_match_boundary (the GPU)
     accumulate(images, ...)             per-image tables -> precision [T, R, K, A, M] and recall [T, K, A, M], host numpy
     flatten_records(images, ...)        the image records as the flat arrays of mnc_coco_accumulate (include/mnc_hip.h n10)
     accumulate_flat_numpy(flat, ...)    the same tables from the flat arrays by the closed form csrc/coco_accum.hip uses (one stable
@@ -13,7 +15,8 @@ cocoeval.py (computeIoU, evaluateImg, accumulate, summarize) and of rleIou in ma
     accumulate_flat(flat, ...)          mnc_coco_accumulate on those arrays
     accumulate_device(images, ...)      accumulate through it (the GPU): the same tables bit for bit
     summarize(acc)                      -> the twelve numbers, an ordered dict
-    CocoSegmEval                        .add(image_id, dt, gt, iscrowd, ...) per image, .accumulate(), .summarize(), .stats
+    CocoSegmEval                        .add(image_id, dt, gt, iscrowd, ...) per image, .accumulate(), .summarize(), .stats;
+                                        iou_type="boundary" scores by the boundary protocol (add then needs image_size=(H, W))
 
 Every table of a match is in the caller's index order with -1 for "none": rank int32 [D], dt_match int32 [A, T, D], dt_ignore uint8
 [A, T, D], gt_match int32 [A, T, G], gt_ignore uint8 [A, G], iou float64 [D, G] (None unless asked for).  There is no fallback:
@@ -98,11 +101,12 @@ def _gt_ignore(crowd, ign, area, rngs):
     return np.array([(ign != 0) | (crowd != 0) | (area < lo) | (area > hi) for lo, hi in rngs], np.uint8).reshape(len(rngs), len(area))
 
 
-def _match_tables(dt, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, who, choose):
+def _match_tables(dt, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, who, choose, _overlap=None):
+    """_overlap: a function of the crowd flags -> the [D, G] table to match on in the place of iou_numpy's (match_boundary_numpy)."""
     thrs, rngs, crowd, ign, area, max_det = _params(who, len(dt), dt.scores, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det)
     D, G, T, A = len(dt), len(gt), len(thrs), len(rngs)
     rank = ranks_numpy(dt.classes, dt.scores)
-    iou = iou_numpy(dt, gt, crowd)
+    iou = iou_numpy(dt, gt, crowd) if _overlap is None else _overlap(crowd)
     gig = _gt_ignore(crowd, ign, area, rngs)
     dt_match, dt_ignore = np.full((A, T, D), -1, np.int32), np.zeros((A, T, D), np.uint8)
     gt_match = np.full((A, T, G), -1, np.int32)
@@ -206,6 +210,50 @@ def device_match(dev, kept, gt, iscrowd=None, ignore=None, eval_area=None, iou_t
         _lib.call("mnc_d2h" if i == len(tables) - 1 else "mnc_d2h_async", dev._ctx.h, _lib.ptr(host), d_ptr.value, host.nbytes)
     return Match(rank[:kept].copy(), np.ascontiguousarray(dt_match[:, :, :kept]), np.ascontiguousarray(dt_ignore[:, :, :kept]),
                  gt_match, gt_ignore, None if iou is None else np.ascontiguousarray(iou[:kept]))
+
+
+def match_boundary_numpy(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100,
+                         d=None, ratio=0.02, return_iou=False):
+    """match_numpy on the overlap min(mask IoU, boundary IoU) (include/mnc_hip.h n11) -- the specification mnc_mask_match_boundary
+    is tested against.  The boundary IoU is iou_numpy of the two sets' boundary bands (mnc_amd.boundary.boundary_numpy in the H x W
+    image at distance d; None: boundary_distance(H, W, ratio)): for a crowd ground truth the union is the area of the detection's
+    band.  Everything else is match_numpy's: the area-range rules look at the masks' areas and eval_area, not at the bands'.
+    -> Match, whose iou (with return_iou) is the minimum that was matched on; with return_iou (Match, biou)."""
+    from .boundary import _distance, boundary_numpy
+    H, W, d = _distance("match_boundary_numpy", H, W, d, ratio)
+    kept = {}
+
+    def overlap(crowd):
+        kept["biou"] = iou_numpy(boundary_numpy(dt, H, W, d), boundary_numpy(gt, H, W, d), crowd)
+        return np.minimum(iou_numpy(dt, gt, crowd), kept["biou"])
+
+    m = _match_tables(dt, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, "match_boundary_numpy", _choose_loop,
+                      overlap)
+    return (m, kept["biou"]) if return_iou else m
+
+
+def match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
+                   ratio=0.02, return_iou=False, device_id=None):
+    """match_boundary_numpy on the GPU (mnc_mask_match_boundary: csrc/mask_boundary.hip makes both boundary sets on the device,
+    csrc/mask_match.hip matches on the minimum): the same tables bit for bit.  Invalid sets and parameters raise ValueError or
+    _lib.MncError (MNC_ERR_INVALID) before anything is launched."""
+    from .boundary import _distance
+    from .masks import _device_id, _set_args
+    H, W, d = _distance("match_boundary", H, W, d, ratio)
+    thrs, rngs, crowd, ign, area, max_det = _params("match_boundary", len(dt), dt.scores, gt, iscrowd, ignore, eval_area, iou_thrs,
+                                                    area_rngs, max_det)
+    D, G, T, A = len(dt), len(gt), len(thrs), len(rngs)
+    rank = np.zeros(D, np.int32)
+    dt_match, dt_ignore = np.zeros((A, T, D), np.int32), np.zeros((A, T, D), np.uint8)
+    gt_match, gt_ignore = np.zeros((A, T, G), np.int32), np.zeros((A, G), np.uint8)
+    iou = np.zeros((D, G), np.float64) if return_iou else None
+    biou = np.zeros((D, G), np.float64) if return_iou else None
+    _lib.call("mnc_mask_match_boundary", *(_set_args(dt) + (_lib.ptr(dt.classes), _lib.ptr(dt.scores)) +
+                                           _gt_args(gt, crowd, ign, area, thrs, rngs, max_det) +
+                                           (H, W, d, _lib.ptr(rank), _lib.ptr(dt_match), _lib.ptr(dt_ignore), _lib.ptr(gt_match),
+                                            _lib.ptr(gt_ignore), _lib.ptr(iou), _lib.ptr(biou), _device_id(device_id))))
+    m = Match(rank, dt_match, dt_ignore, gt_match, gt_ignore, iou)
+    return (m, biou) if return_iou else m
 
 
 def image_record(dt, gt, m):
@@ -468,9 +516,15 @@ class CocoSegmEval(object):
     """COCO's segm protocol over the images added.  device=True matches on the GPU (PackedMasks.match: a device-resident result
     where it lies), device=False with match_numpy, so that the whole path works without one.  accumulate_on_device: the tables
     through accumulate_device (True) or accumulate (False); None: as `device`.  device=False with nothing else said never touches
-    the GPU.  The tables, and so the stats, are the same bits either way."""
+    the GPU.  The tables, and so the stats, are the same bits either way.  iou_type="boundary": COCO's boundary protocol -- the
+    matching on min(mask IoU, boundary IoU) (match_boundary / match_boundary_numpy) at dilation_ratio of the image diagonal; add()
+    then needs image_size=(H, W).  With "segm" (the default) neither argument is looked at."""
 
-    def __init__(self, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, device=True, classes=None, accumulate_on_device=None):
+    def __init__(self, iou_thrs=None, area_rngs=None, max_dets=MAX_DETS, device=True, classes=None, accumulate_on_device=None,
+                 iou_type="segm", dilation_ratio=0.02):
+        if iou_type not in ("segm", "boundary"):
+            raise ValueError("CocoSegmEval: iou_type %r is not 'segm' or 'boundary'" % (iou_type,))
+        self.iou_type, self.dilation_ratio = iou_type, float(dilation_ratio)
         self.iou_thrs = np.asarray(IOU_THRS if iou_thrs is None else iou_thrs, np.float64).reshape(-1)
         self.area_rngs = np.asarray(AREA_RNGS if area_rngs is None else area_rngs, np.float64).reshape(-1, 2)
         self.max_dets = tuple(int(m) for m in max_dets)
@@ -479,12 +533,20 @@ class CocoSegmEval(object):
         self._images = {}
         self.eval = self.stats = None
 
-    def add(self, image_id, dt, gt, iscrowd, ignore=None, eval_area=None):
-        """Match one image's detections to its ground truths (max_det = the largest of max_dets) and keep the tables.  -> Match."""
+    def add(self, image_id, dt, gt, iscrowd, ignore=None, eval_area=None, image_size=None):
+        """Match one image's detections to its ground truths (max_det = the largest of max_dets) and keep the tables.  image_size:
+        (H, W), required with iou_type="boundary" (ValueError without it), ignored with "segm".  -> Match."""
         if image_id in self._images:
             raise ValueError("CocoSegmEval.add: image %r was added before" % (image_id,))
         args = (gt, iscrowd, ignore, eval_area, self.iou_thrs, self.area_rngs, max(self.max_dets))
-        m = dt.match(*args) if self.device else match_numpy(dt, *args)
+        if self.iou_type == "boundary":
+            if image_size is None:
+                raise ValueError("CocoSegmEval.add: iou_type='boundary' needs image_size=(H, W) of image %r" % (image_id,))
+            H, W = (int(v) for v in image_size)
+            args = (gt, H, W) + args[1:] + (None, self.dilation_ratio)
+            m = dt.match_boundary(*args) if self.device else match_boundary_numpy(dt, *args)
+        else:
+            m = dt.match(*args) if self.device else match_numpy(dt, *args)
         self._images[image_id] = image_record(dt, gt, m)
         return m
 

@@ -11,6 +11,9 @@
 //   match_iou_kernel        one thread per pair: union = crowd ? area_d : area_d + area_g - inter, iou = union < 1 ? 0.0 :
 //                           (double)inter / (double)union, stored in the caller's order (the optional output) and once more at
 //                           [dpos[d]][gpos[g]]: a class's block of that table is contiguous in both directions.
+//   match_iou_min_kernel    (mnc_mask_match_boundary, n11) match_iou_kernel's sibling: the same arithmetic on the masks' counts and
+//                           once more on the counts of the two sets' boundary bands (mask_boundary.hip), the smaller of the two
+//                           IoUs stored where match_iou_kernel stores its one, the boundary IoU alone in a table of its own.
 //   match_cells_kernel      one wave per (class, area range, threshold) cell -- they are independent.  The cell of a class is
 //                           run by the wave numbered after the class's best detection (rank 0); every other wave leaves at once.
 //                           The wave walks the class's detections in rank order; its 64 lanes hold the class's ground truths in
@@ -145,6 +148,33 @@ __global__ __launch_bounds__(kMtThreads) void match_iou_kernel(OvSet D, int dcap
   const double iou = uni < 1 ? 0.0 : (double)in / (double)uni;
   if (iou_out) iou_out[p] = iou;
   siou[(long long)dpos[d] * gt.G + gpos[g]] = iou;
+}
+
+// grid ceil(dcap * G / 256), block 256.  match_iou_kernel with a second pair of sets: Db / gb_info the boundary bands of the
+// detections and of the ground truths, binter their counts.  iou_out and siou receive min(iou, biou), biou_out (may be null) biou.
+__global__ __launch_bounds__(kMtThreads) void match_iou_min_kernel(OvSet D, OvSet Db, int dcap, MtGt gt, const mnc_mask_info* __restrict__ gb_info,
+                                                                   const long long* __restrict__ inter, const long long* __restrict__ binter,
+                                                                   const int* __restrict__ dpos, const int* __restrict__ gpos,
+                                                                   double* __restrict__ iou_out, double* __restrict__ biou_out,
+                                                                   double* __restrict__ siou) {
+  const long long p = (long long)blockIdx.x * kMtThreads + threadIdx.x;
+  if (p >= (long long)dcap * gt.G) return;
+  const int d = (int)(p / gt.G), g = (int)(p % gt.G);
+  if (d >= mt_count(D, dcap)) {
+    if (iou_out) iou_out[p] = 0.0;
+    if (biou_out) biou_out[p] = 0.0;
+    return;
+  }
+  const long long in = inter[p];
+  const long long uni = gt.crowd[g] ? D.info[d].area : D.info[d].area + gt.info[g].area - in;
+  const double iou = uni < 1 ? 0.0 : (double)in / (double)uni;
+  const long long bin = binter[p];
+  const long long buni = gt.crowd[g] ? Db.info[d].area : Db.info[d].area + gb_info[g].area - bin;
+  const double biou = buni < 1 ? 0.0 : (double)bin / (double)buni;
+  const double low = biou < iou ? biou : iou;
+  if (iou_out) iou_out[p] = low;
+  if (biou_out) biou_out[p] = biou;
+  siou[(long long)dpos[d] * gt.G + gpos[g]] = low;
 }
 
 __device__ __forceinline__ double mt_wave_max(double v) {
@@ -316,9 +346,22 @@ struct MtWs {
     if (bytes) MNC_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));                          \
   } while (0)
 
-// Uploads the ground truths and the parameters, then the passes.  D.info / D.bits are device pointers already.
+// What mnc_mask_match_boundary adds to a call: the image and the distance, the plans and the device buffers of the two boundary
+// sets (their instance tables uploaded by the caller), the scratch planes both launches use in turn, the second count table and
+// the boundary IoU's table (null: not wanted).
+struct MtBd {
+  int H, W, d;
+  BdPlan dplan, gplan;
+  mnc_mask_info *dinfo, *ginfo;
+  u64 *dbits, *gbits, *scratch;
+  long long* inter;
+  double* biou;
+};
+
+// Uploads the ground truths and the parameters, then the passes.  D.info / D.bits are device pointers already.  bd != nullptr:
+// the matching runs on min(iou, boundary iou).
 int mt_launch(hipStream_t s, const OvSet& D, int dcap, const MtHost& h, const void* gt_bits, int G, const double* iou_thrs, int T, const double* area_rngs,
-              int A, int max_det, bool want_iou, const MtWs& w) {
+              int A, int max_det, bool want_iou, const MtWs& w, const MtBd* bd = nullptr) {
   const size_t cells = (size_t)A * T;
   MT_UP(w.ginfo, h.ginfo.data(), (size_t)G * sizeof(mnc_mask_info));
   MT_UP(w.gbits, gt_bits, h.gused);
@@ -340,13 +383,50 @@ int mt_launch(hipStream_t s, const OvSet& D, int dcap, const MtHost& h, const vo
   if (pairs > 0) {
     const OvSet B = {w.ginfo, w.gbits, nullptr, G};
     overlaps_launch(s, D, B, nullptr, 0, dcap, G, w.inter, nullptr);
-    hipLaunchKernelGGL(match_iou_kernel, dim3((unsigned)((pairs + kMtThreads - 1) / kMtThreads)), dim3(kMtThreads), 0, s, D, dcap, gt,
-                       w.inter, w.L.dpos, w.L.gpos, want_iou ? w.iou : nullptr, w.siou);
+    if (!bd) {
+      hipLaunchKernelGGL(match_iou_kernel, dim3((unsigned)((pairs + kMtThreads - 1) / kMtThreads)), dim3(kMtThreads), 0, s, D, dcap, gt,
+                         w.inter, w.L.dpos, w.L.gpos, want_iou ? w.iou : nullptr, w.siou);
+    } else {
+      // the two boundary sets, one after the other through the same scratch planes, then their counts
+      boundary_launch(s, D, bd->H, bd->W, bd->d, bd->dplan, bd->dinfo, bd->dbits, bd->scratch);
+      boundary_launch(s, B, bd->H, bd->W, bd->d, bd->gplan, bd->ginfo, bd->gbits, bd->scratch);
+      const OvSet Db = {bd->dinfo, bd->dbits, nullptr, dcap}, Gb = {bd->ginfo, bd->gbits, nullptr, G};
+      overlaps_launch(s, Db, Gb, nullptr, 0, dcap, G, bd->inter, nullptr);
+      hipLaunchKernelGGL(match_iou_min_kernel, dim3((unsigned)((pairs + kMtThreads - 1) / kMtThreads)), dim3(kMtThreads), 0, s, D, Db,
+                         dcap, gt, bd->ginfo, w.inter, bd->inter, w.L.dpos, w.L.gpos, want_iou ? w.iou : nullptr, bd->biou, w.siou);
+    }
   }
   if (dcap > 0)
     hipLaunchKernelGGL(match_cells_kernel, dim3((unsigned)(((long long)dcap * cells + kMtWaves - 1) / kMtWaves)), dim3(kMtThreads), 0, s,
                        D, dcap, gt, w.L, w.siou, w.dt_match, w.dt_ignore, w.gt_match);
   return MNC_OK;
+}
+
+// nd == 0 or ng == 0: nothing can match -- the ranks, the ground truths' flags and the size rule of the unmatched, on the host.
+void mt_nothing(const MtHost& h, int nd, const int* dt_classes, const float* dt_scores, const long long* dt_areas, int ng, int T,
+                const double* area_rngs, int A, int max_det, int* rank, int* dt_match, unsigned char* dt_ignore, int* gt_match,
+                unsigned char* gt_ignore) {
+  for (int d = 0; d < nd; ++d) {
+    int r = 0;
+    for (int j = 0; j < nd; ++j) {
+      const float sj = dt_scores[j], sd = dt_scores[d];
+      r += (dt_classes[j] == dt_classes[d] && (sj > sd || (sj == sd && j < d))) ? 1 : 0;
+    }
+    rank[d] = r;
+  }
+  for (int a = 0; a < A; ++a) {
+    const double lo = area_rngs[2 * a], hi = area_rngs[2 * a + 1];
+    for (int g = 0; g < ng; ++g)
+      gt_ignore[(size_t)a * ng + g] = (h.ignore[g] || h.crowd[g] || h.eval_area[g] < lo || h.eval_area[g] > hi) ? 1 : 0;
+    for (int t = 0; t < T; ++t) {
+      for (int g = 0; g < ng; ++g) gt_match[((size_t)a * T + t) * ng + g] = -1;
+      for (int d = 0; d < nd; ++d) {
+        const double area = (double)dt_areas[d];
+        dt_match[((size_t)a * T + t) * nd + d] = -1;
+        dt_ignore[((size_t)a * T + t) * nd + d] = (rank[d] < max_det && (area < lo || area > hi)) ? 1 : 0;
+      }
+    }
+  }
 }
 
 }  // namespace
@@ -377,28 +457,7 @@ int mnc_mask_match(const int* dt_bounds, const long long* dt_offsets, const long
   if (rc) return rc;
   const size_t cells = (size_t)A * T;
   if (nd == 0 || ng == 0) {
-    // nothing can match: the ranks, the ground truths' flags and the size rule of the unmatched, on the host
-    for (int d = 0; d < nd; ++d) {
-      int r = 0;
-      for (int j = 0; j < nd; ++j) {
-        const float sj = dt_scores[j], sd = dt_scores[d];
-        r += (dt_classes[j] == dt_classes[d] && (sj > sd || (sj == sd && j < d))) ? 1 : 0;
-      }
-      rank[d] = r;
-    }
-    for (int a = 0; a < A; ++a) {
-      const double lo = area_rngs[2 * a], hi = area_rngs[2 * a + 1];
-      for (int g = 0; g < ng; ++g)
-        gt_ignore[(size_t)a * ng + g] = (h.ignore[g] || h.crowd[g] || h.eval_area[g] < lo || h.eval_area[g] > hi) ? 1 : 0;
-      for (int t = 0; t < T; ++t) {
-        for (int g = 0; g < ng; ++g) gt_match[((size_t)a * T + t) * ng + g] = -1;
-        for (int d = 0; d < nd; ++d) {
-          const double area = (double)dt_areas[d];
-          dt_match[((size_t)a * T + t) * nd + d] = -1;
-          dt_ignore[((size_t)a * T + t) * nd + d] = (rank[d] < max_det && (area < lo || area > hi)) ? 1 : 0;
-        }
-      }
-    }
+    mt_nothing(h, nd, dt_classes, dt_scores, dt_areas, ng, T, area_rngs, A, max_det, rank, dt_match, dt_ignore, gt_match, gt_ignore);
     clear_error();
     return MNC_OK;
   }
@@ -426,6 +485,85 @@ int mnc_mask_match(const int* dt_bounds, const long long* dt_offsets, const long
   MNC_HIP_TRY(hs.down(gt_ignore, w.L.gig, (size_t)A * ng));
   if (iou) MNC_HIP_TRY(hs.down(iou, w.iou, (size_t)nd * ng * 8));
   MNC_HIP_TRY(hs.sync());
+  clear_error();
+  return MNC_OK;
+}
+
+// see include/mnc_hip.h
+int mnc_mask_match_boundary(const int* dt_bounds, const long long* dt_offsets, const long long* dt_areas, const void* dt_bits,
+                            size_t dt_bytes, int nd, const int* dt_classes, const float* dt_scores, const int* gt_bounds,
+                            const long long* gt_offsets, const long long* gt_areas, const void* gt_bits, size_t gt_bytes, int ng,
+                            const int* gt_classes, const unsigned char* gt_crowd, const unsigned char* gt_ignore_in,
+                            const double* gt_eval_area, const double* iou_thrs, int T, const double* area_rngs, int A, int max_det,
+                            int H, int W, int d, int* rank, int* dt_match, unsigned char* dt_ignore, int* gt_match,
+                            unsigned char* gt_ignore, double* iou, double* biou, int device_id) {
+  const char* who = "mnc_mask_match_boundary";
+  MNC_REQUIRE(nd >= 0 && nd <= kMtMaxN, "%s: %d detections not in [0, %d]", who, nd, kMtMaxN);
+  MNC_REQUIRE(rank && dt_match && dt_ignore && gt_match && gt_ignore, "%s: null output pointer", who);
+  MNC_REQUIRE(nd == 0 || (dt_classes && dt_scores), "%s: null classes or scores of the detections", who);
+  for (int k = 0; k < nd; ++k) MNC_REQUIRE(!std::isnan(dt_scores[k]), "%s: score %d is NaN", who, k);
+  int rc = boundary_check_image(who, H, W, d);
+  if (rc) return rc;
+  MtHost h;
+  rc = mt_check(who, gt_bounds, gt_offsets, gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area,
+                iou_thrs, T, area_rngs, A, max_det, &h);
+  if (rc) return rc;
+  std::vector<mnc_mask_info> dinfo;
+  size_t dused = 0;
+  rc = ov_table(who, "dt", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores, &dinfo, &dused);
+  if (rc) return rc;
+  const size_t cells = (size_t)A * T, pairs = (size_t)nd * ng;
+  if (nd == 0 || ng == 0) {                              // (no pair: neither IoU table has an entry)
+    mt_nothing(h, nd, dt_classes, dt_scores, dt_areas, ng, T, area_rngs, A, max_det, rank, dt_match, dt_ignore, gt_match, gt_ignore);
+    clear_error();
+    return MNC_OK;
+  }
+  // the boundary sets' instance tables follow from the bounds alone
+  std::vector<mnc_mask_info> dbinfo, gbinfo;
+  MtBd bd;
+  bd.H = H; bd.W = W; bd.d = d;
+  boundary_plan(dinfo, H, W, d, &dbinfo, &bd.dplan);
+  boundary_plan(h.ginfo, H, W, d, &gbinfo, &bd.gplan);
+  const size_t plane = bd.dplan.bytes > bd.gplan.bytes ? bd.dplan.bytes : bd.gplan.bytes;
+  mnc_mask_info* d_dinfo; u64* d_dbits; MtWs w;
+  auto layout = [&](WsLayout l) {
+    d_dinfo = l.take<mnc_mask_info>(nd);
+    d_dbits = l.take<u64>(dused / 8);
+    w.layout(l, nd, h, ng, T, A, iou != nullptr);
+    bd.dinfo = l.take<mnc_mask_info>(nd);
+    bd.ginfo = l.take<mnc_mask_info>(ng);
+    bd.dbits = l.take<u64>(bd.dplan.bytes / 8);
+    bd.gbits = l.take<u64>(bd.gplan.bytes / 8);
+    bd.scratch = l.take<u64>(plane / 8 * bd.dplan.planes);
+    bd.inter = l.take<long long>(pairs);
+    bd.biou = l.take<double>(biou ? pairs : 0);
+    return l.bytes();
+  };
+  HostScope hs;
+  rc = hs.open(device_id, layout(WsLayout()));
+  if (rc) return rc;
+  layout(WsLayout(hs.buf));
+  if (!biou) bd.biou = nullptr;
+  MNC_HIP_TRY(hs.up(d_dinfo, dinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
+  MNC_HIP_TRY(hs.up(d_dbits, dt_bits, dused));
+  MNC_HIP_TRY(hs.up(bd.dinfo, dbinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
+  MNC_HIP_TRY(hs.up(bd.ginfo, gbinfo.data(), (size_t)ng * sizeof(mnc_mask_info)));
+  const OvSet D = {d_dinfo, d_dbits, nullptr, nd};
+  BdSpan span;
+  span.begin(hs.stream);
+  rc = mt_launch(hs.stream, D, nd, h, gt_bits, ng, iou_thrs, T, area_rngs, A, max_det, iou != nullptr, w, &bd);
+  if (rc) return rc;
+  span.end(hs.stream);
+  MNC_HIP_TRY(hipGetLastError());
+  MNC_HIP_TRY(hs.down(rank, w.L.rank, (size_t)nd * 4));
+  MNC_HIP_TRY(hs.down(dt_match, w.dt_match, cells * nd * 4));
+  MNC_HIP_TRY(hs.down(dt_ignore, w.dt_ignore, cells * nd));
+  MNC_HIP_TRY(hs.down(gt_match, w.gt_match, cells * ng * 4));
+  MNC_HIP_TRY(hs.down(gt_ignore, w.L.gig, (size_t)A * ng));
+  if (iou) MNC_HIP_TRY(hs.down(iou, w.iou, pairs * 8));
+  if (biou) MNC_HIP_TRY(hs.down(biou, bd.biou, pairs * 8));
+  MNC_HIP_TRY(hs.sync());
+  span.keep();
   clear_error();
   return MNC_OK;
 }

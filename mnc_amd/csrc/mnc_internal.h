@@ -274,6 +274,31 @@ struct OvSet {
 };
 void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
                      long long* d_inter, double* d_iou);
+// mask_boundary.hip: the boundary bands (include/mnc_hip.h n11) of one set of packed masks on the device.  boundary_plan makes, on
+// the host, the instance table of the result from the input's (bounds clipped to the H x W image, not tightened; (0, 0, -1, -1)
+// for an instance without rows or outside the image; offsets in order without gaps; areas 0, which the launch adds to; class,
+// score and row carried over) and what the launch needs; boundary_launch writes every word of d_out_bits once and adds the bit
+// counts to d_out_info[i].area.  d_out_info holds the uploaded table of boundary_plan, d_scratch plan.planes * plan.bytes bytes.
+struct BdPlan {
+  int n;                  // instances
+  int planes;             // scratch planes of `bytes` each: the row-eroded words, and for a large d their block prefix ANDs
+  size_t bytes;           // of the clipped masks = of the result's bits
+  long long most_words;   // of one instance
+  long long most_scan;    // (word columns x blocks of 2d + 1 rows) of one instance
+};
+void boundary_plan(const std::vector<mnc_mask_info>& in, int H, int W, int d, std::vector<mnc_mask_info>* out, BdPlan* plan);
+void boundary_launch(hipStream_t s, const OvSet& in, int H, int W, int d, const BdPlan& plan, mnc_mask_info* d_out_info,
+                     unsigned long long* d_out_bits, unsigned long long* d_scratch);
+int boundary_check_image(const char* who, int H, int W, int d);   // MNC_ERR_INVALID: H or W outside [1, 32768], d outside [1, 1024]
+// mnc_mask_boundary_timing's event pair around the launches of one call; keep() after the stream was synchronised
+struct BdSpan {
+  hipEvent_t a = nullptr, b = nullptr;
+  bool on = false;
+  ~BdSpan();
+  void begin(hipStream_t s);
+  void end(hipStream_t s);
+  void keep();
+};
 void proposal_state_free(void* state);  // proposal.hip
 void comm_free(mnc_ctx* ctx);           // comm.hip
 void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,

@@ -256,6 +256,19 @@ def mask_match_numpy(dt, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs
     return host_match(dt, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou)
 
 
+def mask_boundary(pm, H, W, d=None):
+    """The boundary bands of a PackedMasks in an H x W image at distance d (None: 2 % of the image diagonal, rounded) on the GPU
+    (mnc_mask_boundary, csrc/mask_boundary.hip) -> mnc_amd.masks.PackedMasks in the same layout."""
+    return pm.boundary(H, W, d, device_id=cfg.GPU_ID)
+
+
+def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
+                        ratio=0.02, return_iou=False):
+    """mask_match on the overlap min(mask IoU, boundary IoU) in an H x W image -- COCO's iouType "boundary" -- on the GPU
+    (mnc_mask_match_boundary) -> mnc_amd.coco_eval.Match, with return_iou (Match, biou)."""
+    return dt.match_boundary(gt, H, W, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, d, ratio, return_iou, cfg.GPU_ID)
+
+
 def mask_rle(pm, H, W):
     """COCO RLEs of a PackedMasks in an H x W image on the GPU (mnc_mask_rle / mnc_mask_rle_dev): -> [{"size": [H, W], "counts":
     str}] per instance."""

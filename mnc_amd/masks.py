@@ -14,6 +14,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     PackedMasks.rle_counts / .rle / .from_rle   COCO run-length encoding of the masks and the way back (mnc_amd/rle.py, n7)
     PackedMasks.from_polygons / .from_segmentations   COCO polygon segmentations rasterised into the layout (mnc_amd/polygons.py, n9)
     PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
+    PackedMasks.boundary / .match_boundary   the boundary bands and the matching on min(mask IoU, boundary IoU) (mnc_amd/boundary.py, n11)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -141,6 +142,23 @@ class PackedMasks(object):
         if dev is None:
             return coco_eval.match(self, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou, device_id)
         return coco_eval.device_match(dev, len(self), gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, return_iou)
+
+    def boundary(self, H, W, d=None, ratio=0.02, device_id=None):
+        """The boundary bands of these masks in an H x W image at distance d (None: mnc_amd.boundary.boundary_distance(H, W, ratio))
+        -> a host PackedMasks in the same layout, by the rule of mnc_amd.boundary.boundary_numpy (include/mnc_hip.h n11,
+        csrc/mask_boundary.hip) on the GPU.  A device-resident result is fetched to the host first."""
+        from . import boundary
+        return boundary.boundary(self, H, W, d, ratio, device_id)
+
+    def match_boundary(self, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
+                       ratio=0.02, return_iou=False, device_id=None):
+        """match() on the overlap min(mask IoU, boundary IoU) in an H x W image (COCO's iouType "boundary"), by the rule of
+        mnc_amd.coco_eval.match_boundary_numpy through mnc_mask_match_boundary -> coco_eval.Match, with return_iou (Match, biou).
+        There is no form that matches a device-resident result where it lies: such a result is fetched to the host first (the
+        instance table and the bits, two copies), then uploaded with the call."""
+        from . import coco_eval
+        return coco_eval.match_boundary(self, gt, H, W, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, d, ratio, return_iou,
+                                        device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

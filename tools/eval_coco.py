@@ -2,7 +2,8 @@
 """Score a file of COCO results by COCO's `segm` protocol (mnc_amd/coco_eval.py; the matching on the GPU, csrc/mask_match.hip, and
 the accumulation of the precision / recall tables too, csrc/coco_accum.hip).
 
-    python tools/eval_coco.py --gt GT.json --dt RESULTS.json [--polygons] [--cpu] [--out FILE]
+    python tools/eval_coco.py --gt GT.json --dt RESULTS.json [--polygons] [--iou-type segm|boundary] [--dilation-ratio R] [--cpu]
+                              [--out FILE]
 
 RESULTS.json is what tools/demo.py --save-coco writes: a JSON array of {image_id, category_id, segmentation: {size, counts},
 score}.  GT.json holds `images` ({id, height, width}), `categories` ({id}) and `annotations` ({id, image_id, category_id,
@@ -14,7 +15,10 @@ GPU, mnc_amd.polygons.masks_from_polygons_numpy with --cpu), and an annotation w
 (mnc_mask_from_rle), matched there (mnc_mask_match) and the matches of all images accumulated there in one call
 (mnc_coco_accumulate): the tool follows the evaluator, CocoSegmEval(device=True).  With --cpu everything runs in numpy -- the
 statements of all three (mnc_amd.rle.masks_from_counts_numpy, mnc_amd.coco_eval.match_numpy, mnc_amd.coco_eval.accumulate) --
-and no GPU is needed or touched.  Prints the twelve lines in COCO's
+and no GPU is needed or touched.  With --iou-type boundary the matching runs on min(mask IoU, boundary IoU) (Boundary IoU, the
+COCO toolkit's iouType "boundary": mnc_mask_match_boundary, csrc/mask_boundary.hip; mnc_amd.coco_eval.match_boundary_numpy with
+--cpu), the bands --dilation-ratio (default 0.02) of each image's diagonal wide, H and W taken from the ground-truth file's
+`images`.  Prints the twelve lines in COCO's
 wording and writes them as JSON (--out, default: not written)."""
 import argparse
 import json
@@ -30,6 +34,8 @@ def parse_args(argv=None):
     p.add_argument("--gt", required=True, help="ground truth: images, categories, annotations with RLE segmentations")
     p.add_argument("--dt", required=True, help="results: what tools/demo.py --save-coco writes")
     p.add_argument("--polygons", action="store_true", help="rasterise polygon segmentations instead of refusing them")
+    p.add_argument("--iou-type", default="segm", choices=("segm", "boundary"), help="the overlap to match on (default segm)")
+    p.add_argument("--dilation-ratio", type=float, default=0.02, metavar="R", help="boundary: the band's width as a share of the diagonal")
     p.add_argument("--cpu", action="store_true", help="the numpy statements instead of the GPU")
     p.add_argument("--out", default=None, metavar="FILE", help="write the twelve numbers as JSON")
     return p.parse_args(argv)
@@ -64,7 +70,7 @@ def _masks(rles, size, classes, scores, cpu, polygons=False):
     return make(run_ptr, runs, size[0], size[1], np.asarray(classes, np.int32), np.asarray(scores, np.float32))
 
 
-def evaluate(gt, results, cpu=False, polygons=False):
+def evaluate(gt, results, cpu=False, polygons=False, iou_type="segm", dilation_ratio=0.02):
     """gt: the ground-truth file's dict, results: the list of results -> a summarised mnc_amd.coco_eval.CocoSegmEval."""
     check = _seg_of if polygons else _rle_of
     from mnc_amd.coco_eval import CocoSegmEval
@@ -80,13 +86,14 @@ def evaluate(gt, results, cpu=False, polygons=False):
             raise SystemExit("eval_coco: result %d names the unknown image %r" % (k, r["image_id"]))
         check(r.get("segmentation"), "result", k, sizes[r["image_id"]])
         dets[r["image_id"]].append(r)
-    ev = CocoSegmEval(device=not cpu, classes=sorted(c["id"] for c in gt["categories"]))
+    ev = CocoSegmEval(device=not cpu, classes=sorted(c["id"] for c in gt["categories"]), iou_type=iou_type,
+                      dilation_ratio=dilation_ratio)
     for i, size in sizes.items():
         a, d = anns[i], dets[i]
         gm = _masks([x["segmentation"] for x in a], size, [x["category_id"] for x in a], np.zeros(len(a)), cpu, polygons)
         dm = _masks([x["segmentation"] for x in d], size, [x["category_id"] for x in d], [x["score"] for x in d], cpu, polygons)
         ev.add(i, dm, gm, [int(x.get("iscrowd", 0)) for x in a], [int(x.get("ignore", 0)) for x in a],
-               [float(x["area"]) if "area" in x else float(gm.areas[k]) for k, x in enumerate(a)])
+               [float(x["area"]) if "area" in x else float(gm.areas[k]) for k, x in enumerate(a)], image_size=size)
     ev.summarize()
     return ev
 
@@ -97,7 +104,7 @@ def main(argv=None):
         gt = json.load(f)
     with open(args.dt) as f:
         results = json.load(f)
-    ev = evaluate(gt, results, args.cpu, args.polygons)
+    ev = evaluate(gt, results, args.cpu, args.polygons, args.iou_type, args.dilation_ratio)
     for line in ev.lines():
         print(line)
     if args.out:
