@@ -94,13 +94,13 @@ def boundary_numpy(pm, H, W, d):
 def boundary_call(pm, H, W, d, bits=None, device_id=0):
     """mnc_mask_boundary as it is: bits None asks for bounds, offsets and the size only (nothing is launched).  -> (bounds,
     offsets, areas, bytes needed)."""
+    from .masks import _set_args
     n = len(pm)
-    src = pm.bits if pm.bits.size else np.zeros(1, np.uint64)
     bounds, offsets, areas = np.zeros((n, 4), np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
     need = ctypes.c_size_t(0)
-    _lib.call("mnc_mask_boundary", _lib.ptr(pm.bounds), _lib.ptr(pm.offsets), _lib.ptr(src), int(pm.bits.nbytes), n, int(H), int(W),
-              int(d), _lib.ptr(bounds), _lib.ptr(offsets), _lib.ptr(areas), _lib.ptr(bits), bits.nbytes if bits is not None else 0,
-              ctypes.addressof(need), int(device_id))
+    _lib.call("mnc_mask_boundary", *(_set_args(pm, areas=False) + (
+        int(H), int(W), int(d), _lib.ptr(bounds), _lib.ptr(offsets), _lib.ptr(areas), _lib.ptr(bits),
+        bits.nbytes if bits is not None else 0, ctypes.addressof(need), int(device_id))))
     return bounds, offsets, areas, int(need.value)
 
 

@@ -172,22 +172,23 @@ def _gt_args(gt, crowd, ign, area, thrs, rngs, max_det):
                             _lib.ptr(rngs), len(rngs), max_det)
 
 
+def _tables(D, G, T, A, return_iou):
+    """The output tables of one matching, zeroed: rank, dt_match, dt_ignore, gt_match, gt_ignore, iou (None: not wanted)."""
+    return (np.zeros(D, np.int32), np.zeros((A, T, D), np.int32), np.zeros((A, T, D), np.uint8), np.zeros((A, T, G), np.int32),
+            np.zeros((A, G), np.uint8), np.zeros((D, G), np.float64) if return_iou else None)
+
+
 def match(dt, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, return_iou=False,
           device_id=None):
     """match_numpy on the GPU (mnc_mask_match, csrc/mask_match.hip): the same tables bit for bit.  Invalid sets and parameters
     raise ValueError or _lib.MncError (MNC_ERR_INVALID) before anything is launched."""
     from .masks import _device_id, _set_args
     thrs, rngs, crowd, ign, area, max_det = _params("match", len(dt), dt.scores, gt, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det)
-    D, G, T, A = len(dt), len(gt), len(thrs), len(rngs)
-    rank = np.zeros(D, np.int32)
-    dt_match, dt_ignore = np.zeros((A, T, D), np.int32), np.zeros((A, T, D), np.uint8)
-    gt_match, gt_ignore = np.zeros((A, T, G), np.int32), np.zeros((A, G), np.uint8)
-    iou = np.zeros((D, G), np.float64) if return_iou else None
+    tables = _tables(len(dt), len(gt), len(thrs), len(rngs), return_iou)
     _lib.call("mnc_mask_match", *(_set_args(dt) + (_lib.ptr(dt.classes), _lib.ptr(dt.scores)) +
                                   _gt_args(gt, crowd, ign, area, thrs, rngs, max_det) +
-                                  (_lib.ptr(rank), _lib.ptr(dt_match), _lib.ptr(dt_ignore), _lib.ptr(gt_match), _lib.ptr(gt_ignore),
-                                   _lib.ptr(iou), _device_id(device_id))))
-    return Match(rank, dt_match, dt_ignore, gt_match, gt_ignore, iou)
+                                  tuple(_lib.ptr(t) for t in tables) + (_device_id(device_id),)))
+    return Match(*tables)
 
 
 def device_match(dev, kept, gt, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100,
@@ -201,10 +202,7 @@ def device_match(dev, kept, gt, iscrowd=None, ignore=None, eval_area=None, iou_t
     out = [ctypes.c_void_p() for _ in range(6)]
     _lib.call("mnc_mask_match_dev", dev._ctx.h, dev.d_info, dev.d_bits, R, *(_gt_args(gt, crowd, ign, area, thrs, rngs, max_det) + (
         int(bool(return_iou)),) + tuple(ctypes.addressof(o) for o in out)))
-    rank = np.zeros(R, np.int32)
-    dt_match, dt_ignore = np.zeros((A, T, R), np.int32), np.zeros((A, T, R), np.uint8)
-    gt_match, gt_ignore = np.zeros((A, T, G), np.int32), np.zeros((A, G), np.uint8)
-    iou = np.zeros((R, G), np.float64) if return_iou else None
+    rank, dt_match, dt_ignore, gt_match, gt_ignore, iou = _tables(R, G, T, A, return_iou)
     tables = [t for t in zip((rank, dt_match, dt_ignore, gt_match, gt_ignore, iou), out) if t[0] is not None and t[0].size]
     for i, (host, d_ptr) in enumerate(tables):
         _lib.call("mnc_d2h" if i == len(tables) - 1 else "mnc_d2h_async", dev._ctx.h, _lib.ptr(host), d_ptr.value, host.nbytes)
@@ -242,17 +240,12 @@ def match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_
     H, W, d = _distance("match_boundary", H, W, d, ratio)
     thrs, rngs, crowd, ign, area, max_det = _params("match_boundary", len(dt), dt.scores, gt, iscrowd, ignore, eval_area, iou_thrs,
                                                     area_rngs, max_det)
-    D, G, T, A = len(dt), len(gt), len(thrs), len(rngs)
-    rank = np.zeros(D, np.int32)
-    dt_match, dt_ignore = np.zeros((A, T, D), np.int32), np.zeros((A, T, D), np.uint8)
-    gt_match, gt_ignore = np.zeros((A, T, G), np.int32), np.zeros((A, G), np.uint8)
-    iou = np.zeros((D, G), np.float64) if return_iou else None
-    biou = np.zeros((D, G), np.float64) if return_iou else None
+    tables = _tables(len(dt), len(gt), len(thrs), len(rngs), return_iou)
+    biou = np.zeros((len(dt), len(gt)), np.float64) if return_iou else None
     _lib.call("mnc_mask_match_boundary", *(_set_args(dt) + (_lib.ptr(dt.classes), _lib.ptr(dt.scores)) +
-                                           _gt_args(gt, crowd, ign, area, thrs, rngs, max_det) +
-                                           (H, W, d, _lib.ptr(rank), _lib.ptr(dt_match), _lib.ptr(dt_ignore), _lib.ptr(gt_match),
-                                            _lib.ptr(gt_ignore), _lib.ptr(iou), _lib.ptr(biou), _device_id(device_id))))
-    m = Match(rank, dt_match, dt_ignore, gt_match, gt_ignore, iou)
+                                           _gt_args(gt, crowd, ign, area, thrs, rngs, max_det) + (H, W, d) +
+                                           tuple(_lib.ptr(t) for t in tables) + (_lib.ptr(biou), _device_id(device_id))))
+    m = Match(*tables)
     return (m, biou) if return_iou else m
 
 

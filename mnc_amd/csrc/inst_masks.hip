@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "cv_resize.h"
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
 
@@ -54,9 +54,6 @@ __host__ __device__ inline long long mask_items(int w, int h) {
   if (w < 1 || h < 1) return 0;
   const int rows = kMaskChunk * (64 / mask_wpad(w));
   return ((long long)h + rows - 1) / rows;
-}
-__host__ __device__ inline long long mask_bytes(int w, int h) {
-  return w < 1 || h < 1 ? 0 : (long long)h * ((w + 63) >> 6) * 8;
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(kMaskThreads) void inst_masks_pack_kernel(const mnc
     __syncthreads();                      // the previous item's mask has been read
     for (int i = threadIdx.x; i < S * S; i += kMaskThreads) mk[i] = masks[(long)row * mask_stride + i];
     __syncthreads();
-    const int wpad = mask_wpad(w), fold = 64 / wpad, strips = (w + 63) >> 6;
+    const int wpad = mask_wpad(w), fold = 64 / wpad, strips = mask_strips(w);
     const int row_lo = (int)(it - first) * (kMaskChunk * fold), row_hi = min(h, row_lo + kMaskChunk * fold);
     const double ifx = cv_inv(w, S), ify = cv_inv(h, S);
     unsigned long long* out = bits + offset / 8;
@@ -279,7 +276,7 @@ int mnc_mask_records(mnc_ctx* ctx, const float* d_records, const int* d_counts, 
   MNC_REQUIRE(H >= 1 && W >= 1 && H <= kMaskMaxSide && W <= kMaskMaxSide, "mnc_mask_records: image %d x %d not in [1, %d]", H, W,
               kMaskMaxSide);
   // clipped boxes: no instance has more than H rows of ceil(W / 64) words
-  const size_t words = d_bits ? (size_t)record_cap * H * ((W + 63) >> 6) : 0;
+  const size_t words = d_bits ? (size_t)record_cap * H * mask_strips(W) : 0;
   mnc_mask_head* head; mnc_mask_info* info; unsigned long long* bits;
   auto layout = [&](WsLayout l) {
     head = l.take<mnc_mask_head>(1);

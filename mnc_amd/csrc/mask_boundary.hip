@@ -7,9 +7,9 @@
 // where the mask's bounds do, and the mask is 0 beyond those).
 //
 //   bd_src_word             the one crop step, at the read of the input words: word j of a row of the clipped box is 64 bits of the
-//                           input row from bit max(0, -x1) + 64 j on, funnel-shifted together from two neighbouring input words
-//                           (shift 0 apart: a 64-bit shift by 64 is undefined), the input's padding masked before use -- padding
-//                           bits are not trusted -- and the columns >= the clipped width cleared; a word outside the row reads 0.
+//                           input row from bit max(0, -x1) + 64 j on (mask_word_at: funnel-shifted together from two neighbouring
+//                           input words, the input's padding masked before use) and the columns >= the clipped width cleared; a
+//                           word outside the row reads 0.
 //   boundary_rows_kernel    one thread per output word (instance = blockIdx.y, consecutive lanes = consecutive words of a row).
 //                           eroded = ~dilate(~row): in the word itself a log-step shift-OR dilation by min(d, 63); from each of
 //                           the ceil(d / 64) words to either side only the zero nearest to this word matters (__clzll / __ffsll):
@@ -35,11 +35,9 @@
 // image, d = 23: the three kernels take 31 us of a 0.14 ms call that is launches and copies (profiles/mask_boundary_bench.txt).
 #include <vector>
 
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
-
-typedef unsigned long long u64;
 
 constexpr int kBdThreads = 256;
 constexpr int kBdMaxN = 2048;                  // instances of one call (mnc_mask_rle's limit)
@@ -49,22 +47,11 @@ constexpr int kBdMaxD = 1024;
 // instead of paying a third launch that reads and writes both planes; above it the reads per output word would grow with d.
 constexpr int kBdPlainMaxD = 4;
 
-// Word j of row `row` (of `sa` words holding `wa` columns) of the input, 0 outside the row, the padding of the last word cleared.
-__device__ __forceinline__ u64 bd_in_word(const u64* __restrict__ row, int j, int sa, int wa) {
-  if (j < 0 || j >= sa) return 0ull;
-  u64 v = row[j];
-  const int valid = wa - (j << 6);
-  if (valid < 64) v &= (1ull << valid) - 1ull;
-  return v;
-}
-
-// The crop: word j of the clipped row (w columns in `strips` words) whose column 0 is bit sx >= 0 of the input row.
+// The crop: word j of the clipped row (w columns in `strips` words) whose column 0 is bit sx >= 0 of the input row (of `sa` words
+// holding `wa` columns).
 __device__ __forceinline__ u64 bd_src_word(const u64* __restrict__ row, int j, int strips, int w, int sx, int sa, int wa) {
   if (j < 0 || j >= strips) return 0ull;
-  const int bit = sx + (j << 6);
-  const int q = bit >> 6, s = bit & 63;
-  u64 v = bd_in_word(row, q, sa, wa);
-  if (s) v = (v >> s) | (bd_in_word(row, q + 1, sa, wa) << (64 - s));
+  u64 v = mask_word_at(row, sx + (j << 6), sa, wa);
   const int valid = w - (j << 6);
   if (valid < 64) v &= (1ull << valid) - 1ull;
   return v;
@@ -79,18 +66,18 @@ __device__ __forceinline__ BdBox bd_box(const mnc_mask_info& a, const mnc_mask_i
   BdBox b;
   b.w = o.x2 - o.x1 + 1;
   b.h = o.y2 - o.y1 + 1;
-  b.strips = (b.w + 63) >> 6;
+  b.strips = mask_strips(b.w);
   b.sx = o.x1 - a.x1;                          // >= 0: the clipped box lies inside the input's bounds
   b.sy = o.y1 - a.y1;
   b.wa = a.x2 - a.x1 + 1;
-  b.sa = (b.wa + 63) >> 6;
+  b.sa = mask_strips(b.wa);
   b.in_words = a.offset / 8;
   b.out_words = o.offset / 8;
   return b;
 }
 
 // grid (ceil(most_words / 256), n), block 256.  plane0[word] = the row-eroded word.
-__global__ __launch_bounds__(kBdThreads) void boundary_rows_kernel(OvSet A, const mnc_mask_info* __restrict__ out, int d,
+__global__ __launch_bounds__(kBdThreads) void boundary_rows_kernel(MaskSet A, const mnc_mask_info* __restrict__ out, int d,
                                                                    u64* __restrict__ plane0) {
   const int i = blockIdx.y;
   const mnc_mask_info o = out[i];
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_scan_kernel(const mnc_mas
                                                                    u64* __restrict__ plane1) {
   const mnc_mask_info o = out[blockIdx.y];
   if (o.x2 < o.x1 || o.y2 < o.y1) return;
-  const int w = o.x2 - o.x1 + 1, h = o.y2 - o.y1 + 1, strips = (w + 63) >> 6;
+  const int w = o.x2 - o.x1 + 1, h = o.y2 - o.y1 + 1, strips = mask_strips(w);
   const int len = 2 * d + 1, blocks = (h + len - 1) / len;
   const long long t = (long long)blockIdx.x * kBdThreads + threadIdx.x;
   if (t >= (long long)blocks * strips) return;
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_scan_kernel(const mnc_mas
 }
 
 // grid (ceil(most_words / 256), n), block 256.  bits[word] = M & ~E; out[i].area += the bits set (uploaded as 0).
-__global__ __launch_bounds__(kBdThreads) void boundary_final_kernel(OvSet A, mnc_mask_info* out, int d,
+__global__ __launch_bounds__(kBdThreads) void boundary_final_kernel(MaskSet A, mnc_mask_info* out, int d,
                                                                     const u64* __restrict__ plane0, const u64* __restrict__ plane1,
                                                                     u64* __restrict__ bits) {
   const int i = blockIdx.y;
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_final_kernel(OvSet A, mnc
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((u64*)&out[i].area, (u64)cnt);
 }
 
-// (Shared with mask_match.hip: mnc_internal.h.)
+// (Declared in mask_set.h: mask_match.hip plans and launches the two boundary sets of its call.)
 void boundary_plan(const std::vector<mnc_mask_info>& in, int H, int W, int d, std::vector<mnc_mask_info>* out, BdPlan* plan) {
   const size_t n = in.size();
   out->assign(n, mnc_mask_info());
@@ -215,8 +202,7 @@ void boundary_plan(const std::vector<mnc_mask_info>& in, int H, int W, int d, st
   }
 }
 
-// (Shared with mask_match.hip: mnc_internal.h.)
-void boundary_launch(hipStream_t s, const OvSet& in, int H, int W, int d, const BdPlan& plan, mnc_mask_info* d_out_info, u64* d_out_bits,
+void boundary_launch(hipStream_t s, const MaskSet& in, int H, int W, int d, const BdPlan& plan, mnc_mask_info* d_out_info, u64* d_out_bits,
                      u64* d_scratch) {
   (void)H; (void)W;                                      // (the clipped bounds in d_out_info carry them)
   if (plan.n < 1 || plan.most_words < 1) return;
@@ -275,15 +261,15 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
   MNC_REQUIRE(bits_bytes, "%s: null bits_bytes", who);
   MNC_REQUIRE(n == 0 || (out_bounds && out_offsets), "%s: null output pointer", who);
   MNC_REQUIRE(n == 0 || !out_bits || out_areas, "%s: null out_areas", who);
-  std::vector<mnc_mask_info> info, out;
+  HostMaskSet set;
+  std::vector<mnc_mask_info> out;
   std::vector<long long> areas((size_t)n, 0);
-  size_t used = 0;
-  rc = ov_table(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr, &info, &used);
+  rc = set.check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   *bits_bytes = 0;
   if (n == 0) { clear_error(); return MNC_OK; }
   BdPlan plan;
-  boundary_plan(info, H, W, d, &out, &plan);
+  boundary_plan(set.info, H, W, d, &out, &plan);
   for (int i = 0; i < n; ++i) {
     out_bounds[4 * (size_t)i] = out[i].x1; out_bounds[4 * (size_t)i + 1] = out[i].y1;
     out_bounds[4 * (size_t)i + 2] = out[i].x2; out_bounds[4 * (size_t)i + 3] = out[i].y2;
@@ -294,10 +280,9 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
   MNC_REQUIRE(bits_cap >= plan.bytes, "%s: bits_cap %zu is below the %zu bytes of the boundaries", who, bits_cap, plan.bytes);
   for (int i = 0; i < n; ++i) out_areas[i] = 0;
   if (plan.bytes == 0) { clear_error(); return MNC_OK; } // no instance meets the image
-  mnc_mask_info *d_in, *d_out; u64 *d_bits, *d_obits, *d_scratch;
+  mnc_mask_info* d_out; u64 *d_obits, *d_scratch;
   auto layout = [&](WsLayout l) {
-    d_in = l.take<mnc_mask_info>(n);
-    d_bits = l.take<u64>(used / 8);
+    set.take(l);
     d_out = l.take<mnc_mask_info>(n);
     d_obits = l.take<u64>(plan.bytes / 8);
     d_scratch = l.take<u64>(plan.bytes / 8 * plan.planes);
@@ -307,13 +292,11 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  MNC_HIP_TRY(hs.up(d_in, info.data(), (size_t)n * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_bits, bits, used));
+  MNC_HIP_TRY(set.upload(hs));
   MNC_HIP_TRY(hs.up(d_out, out.data(), (size_t)n * sizeof(mnc_mask_info)));
-  const OvSet A = {d_in, d_bits, nullptr, n};
   BdSpan span;
   span.begin(hs.stream);
-  boundary_launch(hs.stream, A, H, W, d, plan, d_out, d_obits, d_scratch);
+  boundary_launch(hs.stream, set.view(), H, W, d, plan, d_out, d_obits, d_scratch);
   span.end(hs.stream);
   MNC_HIP_TRY(hipGetLastError());
   MNC_HIP_TRY(hs.down(out.data(), d_out, (size_t)n * sizeof(mnc_mask_info)));

@@ -37,11 +37,9 @@
 #include <cmath>
 #include <vector>
 
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
-
-typedef unsigned long long u64;
 
 constexpr int kMtThreads = 256;
 constexpr int kMtWaves = kMtThreads / 64;
@@ -75,27 +73,18 @@ struct MtLists {
   unsigned char* gig;                          // [A][G] the output gt_ignore
 };
 
-__device__ __forceinline__ int mt_count(const OvSet& s, int cap) { return min(max(s.n_ptr ? *s.n_ptr : s.n, 0), cap); }
-
-// mask_overlaps.hip's key: float32 -> unsigned with the floats' order, -0.0 as 0.0; a NaN (refused by the host entry) by its bits.
-__device__ __forceinline__ unsigned mt_score_key(float s) {
-  if (s == 0.f) s = 0.f;
-  const unsigned u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // grid ceil(max(dcap, G) / 256), block 256.  Thread i: detection i (i < the detections' count) and ground truth i (i < G).
-__global__ __launch_bounds__(kMtThreads) void match_lists_kernel(OvSet D, int dcap, MtGt gt, MtLists L) {
-  const int nd = mt_count(D, dcap);
+__global__ __launch_bounds__(kMtThreads) void match_lists_kernel(MaskSet D, int dcap, MtGt gt, MtLists L) {
+  const int nd = mask_count(D, dcap);
   const int i = blockIdx.x * kMtThreads + threadIdx.x;
   if (i < dcap && i >= nd) L.rank[i] = -1;
   if (i < nd) {
     const int cls = D.info[i].cls;
-    const unsigned mine = mt_score_key(D.info[i].score);
+    const unsigned mine = mask_score_key(D.info[i].score);
     int lower = 0, rank = 0, same = 0;
     for (int j = 0; j < nd; ++j) {
       const int c = D.info[j].cls;
-      const unsigned k = mt_score_key(D.info[j].score);
+      const unsigned k = mask_score_key(D.info[j].score);
       lower += c < cls ? 1 : 0;
       same += c == cls ? 1 : 0;
       rank += (c == cls && (k > mine || (k == mine && j < i))) ? 1 : 0;
@@ -133,13 +122,13 @@ __global__ __launch_bounds__(kMtThreads) void match_lists_kernel(OvSet D, int dc
 
 // grid ceil(dcap * G / 256), block 256.  inter [dcap][G] of the overlap kernel -> iou_out [dcap][G] in the caller's order (may be
 // null) and siou [dcap][G] at [dpos[d]][gpos[g]]; rows past the detections' count store 0.0 in iou_out and nothing in siou.
-__global__ __launch_bounds__(kMtThreads) void match_iou_kernel(OvSet D, int dcap, MtGt gt, const long long* __restrict__ inter,
+__global__ __launch_bounds__(kMtThreads) void match_iou_kernel(MaskSet D, int dcap, MtGt gt, const long long* __restrict__ inter,
                                                                const int* __restrict__ dpos, const int* __restrict__ gpos,
                                                                double* __restrict__ iou_out, double* __restrict__ siou) {
   const long long p = (long long)blockIdx.x * kMtThreads + threadIdx.x;
   if (p >= (long long)dcap * gt.G) return;
   const int d = (int)(p / gt.G), g = (int)(p % gt.G);
-  if (d >= mt_count(D, dcap)) {
+  if (d >= mask_count(D, dcap)) {
     if (iou_out) iou_out[p] = 0.0;
     return;
   }
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(kMtThreads) void match_iou_kernel(OvSet D, int dcap
 
 // grid ceil(dcap * G / 256), block 256.  match_iou_kernel with a second pair of sets: Db / gb_info the boundary bands of the
 // detections and of the ground truths, binter their counts.  iou_out and siou receive min(iou, biou), biou_out (may be null) biou.
-__global__ __launch_bounds__(kMtThreads) void match_iou_min_kernel(OvSet D, OvSet Db, int dcap, MtGt gt, const mnc_mask_info* __restrict__ gb_info,
+__global__ __launch_bounds__(kMtThreads) void match_iou_min_kernel(MaskSet D, MaskSet Db, int dcap, MtGt gt, const mnc_mask_info* __restrict__ gb_info,
                                                                    const long long* __restrict__ inter, const long long* __restrict__ binter,
                                                                    const int* __restrict__ dpos, const int* __restrict__ gpos,
                                                                    double* __restrict__ iou_out, double* __restrict__ biou_out,
@@ -160,7 +149,7 @@ __global__ __launch_bounds__(kMtThreads) void match_iou_min_kernel(OvSet D, OvSe
   const long long p = (long long)blockIdx.x * kMtThreads + threadIdx.x;
   if (p >= (long long)dcap * gt.G) return;
   const int d = (int)(p / gt.G), g = (int)(p % gt.G);
-  if (d >= mt_count(D, dcap)) {
+  if (d >= mask_count(D, dcap)) {
     if (iou_out) iou_out[p] = 0.0;
     if (biou_out) biou_out[p] = 0.0;
     return;
@@ -185,7 +174,7 @@ __device__ __forceinline__ double mt_wave_max(double v) {
 
 // grid ceil(dcap * A * T / 4), block 256.  Wave (d0, a, t) runs the cell of d0's class when rank[d0] == 0.  dt_match / dt_ignore
 // [A][T][dcap], gt_match [A][T][G], filled with -1 / 0 / -1 before the launch.
-__global__ __launch_bounds__(kMtThreads) void match_cells_kernel(OvSet D, int dcap, MtGt gt, MtLists L, const double* __restrict__ siou,
+__global__ __launch_bounds__(kMtThreads) void match_cells_kernel(MaskSet D, int dcap, MtGt gt, MtLists L, const double* __restrict__ siou,
                                                                  int* __restrict__ dt_match, unsigned char* __restrict__ dt_ignore,
                                                                  int* __restrict__ gt_match) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -193,7 +182,7 @@ __global__ __launch_bounds__(kMtThreads) void match_cells_kernel(OvSet D, int dc
   const int cells = gt.A * gt.T;
   if (cell >= (long long)dcap * cells) return;
   const int d0 = (int)(cell / cells), a = (int)(cell % cells) / gt.T, t = (int)(cell % cells) % gt.T;
-  if (d0 >= mt_count(D, dcap) || L.rank[d0] != 0) return;
+  if (d0 >= mask_count(D, dcap) || L.rank[d0] != 0) return;
   const int G = gt.G;
   const int dstart = L.dstart[d0], dn = min(L.dcount[d0], gt.max_det);
   const int gstart = L.gstart[d0], gn = L.gcount[d0];
@@ -266,10 +255,9 @@ namespace {
 
 // The parts of a call every form shares: checked parameters, and the host's tables of the ground truths.
 struct MtHost {
-  std::vector<mnc_mask_info> ginfo;
+  HostMaskSet gt;
   std::vector<unsigned char> crowd, ignore;
   std::vector<double> eval_area;
-  size_t gused = 0;
 };
 
 int mt_check(const char* who, const int* g_bounds, const long long* g_offsets, const long long* g_areas, const void* g_bits,
@@ -295,16 +283,15 @@ int mt_check(const char* who, const int* g_bounds, const long long* g_offsets, c
     h->crowd[g] = g_crowd[g];
     h->ignore[g] = g_ignore ? g_ignore[g] : 0;
   }
-  const int rc = ov_table(who, "gt", g_bounds, g_offsets, g_areas, g_bits, g_bytes, ng, g_classes, nullptr, &h->ginfo, &h->gused);
+  const int rc = h->gt.check(who, "gt", g_bounds, g_offsets, g_areas, g_bits, g_bytes, ng, g_classes, nullptr);
   if (rc) return rc;
   for (int g = 0; g < ng; ++g) h->eval_area[g] = g_eval_area ? g_eval_area[g] : (double)g_areas[g];
   return MNC_OK;
 }
 
-// Device buffers of one call over dcap detections and G ground truths, and its launch sequence.
+// Device buffers of one call over dcap detections and G ground truths (the ground truths' set takes its place first), and its
+// launch sequence.
 struct MtWs {
-  mnc_mask_info* ginfo;
-  u64* gbits;
   unsigned char *crowd, *ignore;
   double *eval_area, *thrs, *rngs;
   MtLists L;
@@ -312,10 +299,9 @@ struct MtWs {
   double *iou, *siou;
   int *dt_match, *gt_match;
   unsigned char* dt_ignore;
-  void layout(WsLayout& l, int dcap, const MtHost& h, int G, int T, int A, bool want_iou) {
+  void layout(WsLayout& l, int dcap, MtHost& h, int G, int T, int A, bool want_iou) {
     const size_t pairs = (size_t)dcap * G, cells = (size_t)A * T;
-    ginfo = l.take<mnc_mask_info>(G);
-    gbits = l.take<u64>(h.gused / 8);
+    h.gt.take(l);
     crowd = l.take<unsigned char>(G);
     ignore = l.take<unsigned char>(G);
     eval_area = l.take<double>(G);
@@ -341,16 +327,12 @@ struct MtWs {
   }
 };
 
-#define MT_UP(dst, src, bytes)                                                                                  \
-  do {                                                                                                          \
-    if (bytes) MNC_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));                          \
-  } while (0)
-
-// What mnc_mask_match_boundary adds to a call: the image and the distance, the plans and the device buffers of the two boundary
-// sets (their instance tables uploaded by the caller), the scratch planes both launches use in turn, the second count table and
-// the boundary IoU's table (null: not wanted).
+// What mnc_mask_match_boundary adds to a call: the image, the distance and where the boundary IoU goes on the host (null: not
+// wanted) -- its arguments; then the plans and the device buffers of the two boundary sets (their instance tables uploaded by the
+// caller), the scratch planes both launches use in turn, the second count table and the boundary IoU's table (null: not wanted).
 struct MtBd {
   int H, W, d;
+  double* biou_out;
   BdPlan dplan, gplan;
   mnc_mask_info *dinfo, *ginfo;
   u64 *dbits, *gbits, *scratch;
@@ -360,28 +342,30 @@ struct MtBd {
 
 // Uploads the ground truths and the parameters, then the passes.  D.info / D.bits are device pointers already.  bd != nullptr:
 // the matching runs on min(iou, boundary iou).
-int mt_launch(hipStream_t s, const OvSet& D, int dcap, const MtHost& h, const void* gt_bits, int G, const double* iou_thrs, int T, const double* area_rngs,
+int mt_launch(hipStream_t s, const MaskSet& D, int dcap, const MtHost& h, int G, const double* iou_thrs, int T, const double* area_rngs,
               int A, int max_det, bool want_iou, const MtWs& w, const MtBd* bd = nullptr) {
   const size_t cells = (size_t)A * T;
-  MT_UP(w.ginfo, h.ginfo.data(), (size_t)G * sizeof(mnc_mask_info));
-  MT_UP(w.gbits, gt_bits, h.gused);
-  MT_UP(w.crowd, h.crowd.data(), (size_t)G);
-  MT_UP(w.ignore, h.ignore.data(), (size_t)G);
-  MT_UP(w.eval_area, h.eval_area.data(), (size_t)G * 8);
-  MT_UP(w.thrs, iou_thrs, (size_t)T * 8);
-  MT_UP(w.rngs, area_rngs, (size_t)A * 16);
+  auto up = [s](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  MNC_HIP_TRY(h.gt.upload(s));
+  MNC_HIP_TRY(up(w.crowd, h.crowd.data(), (size_t)G));
+  MNC_HIP_TRY(up(w.ignore, h.ignore.data(), (size_t)G));
+  MNC_HIP_TRY(up(w.eval_area, h.eval_area.data(), (size_t)G * 8));
+  MNC_HIP_TRY(up(w.thrs, iou_thrs, (size_t)T * 8));
+  MNC_HIP_TRY(up(w.rngs, area_rngs, (size_t)A * 16));
   if (cells * dcap) {
     MNC_HIP_TRY(hipMemsetAsync(w.dt_match, 0xff, cells * dcap * 4, s));
     MNC_HIP_TRY(hipMemsetAsync(w.dt_ignore, 0, cells * dcap, s));
   }
   if (cells * G) MNC_HIP_TRY(hipMemsetAsync(w.gt_match, 0xff, cells * G * 4, s));
-  const MtGt gt = {w.ginfo, w.crowd, w.ignore, w.eval_area, w.thrs, w.rngs, G, T, A, max_det};
+  const MtGt gt = {h.gt.d_info, w.crowd, w.ignore, w.eval_area, w.thrs, w.rngs, G, T, A, max_det};
   const int n = dcap > G ? dcap : G;
   if (n < 1) return MNC_OK;
   hipLaunchKernelGGL(match_lists_kernel, dim3(cdiv(n, kMtThreads)), dim3(kMtThreads), 0, s, D, dcap, gt, w.L);
   const long long pairs = (long long)dcap * G;
   if (pairs > 0) {
-    const OvSet B = {w.ginfo, w.gbits, nullptr, G};
+    const MaskSet B = h.gt.view();
     overlaps_launch(s, D, B, nullptr, 0, dcap, G, w.inter, nullptr);
     if (!bd) {
       hipLaunchKernelGGL(match_iou_kernel, dim3((unsigned)((pairs + kMtThreads - 1) / kMtThreads)), dim3(kMtThreads), 0, s, D, dcap, gt,
@@ -390,7 +374,7 @@ int mt_launch(hipStream_t s, const OvSet& D, int dcap, const MtHost& h, const vo
       // the two boundary sets, one after the other through the same scratch planes, then their counts
       boundary_launch(s, D, bd->H, bd->W, bd->d, bd->dplan, bd->dinfo, bd->dbits, bd->scratch);
       boundary_launch(s, B, bd->H, bd->W, bd->d, bd->gplan, bd->ginfo, bd->gbits, bd->scratch);
-      const OvSet Db = {bd->dinfo, bd->dbits, nullptr, dcap}, Gb = {bd->ginfo, bd->gbits, nullptr, G};
+      const MaskSet Db = {bd->dinfo, bd->dbits, nullptr, dcap}, Gb = {bd->ginfo, bd->gbits, nullptr, G};
       overlaps_launch(s, Db, Gb, nullptr, 0, dcap, G, bd->inter, nullptr);
       hipLaunchKernelGGL(match_iou_min_kernel, dim3((unsigned)((pairs + kMtThreads - 1) / kMtThreads)), dim3(kMtThreads), 0, s, D, Db,
                          dcap, gt, bd->ginfo, w.inter, bd->inter, w.L.dpos, w.L.gpos, want_iou ? w.iou : nullptr, bd->biou, w.siou);
@@ -429,6 +413,84 @@ void mt_nothing(const MtHost& h, int nd, const int* dt_classes, const float* dt_
   }
 }
 
+// mnc_mask_match (bd == nullptr) and mnc_mask_match_boundary (bd: H, W, d and biou_out filled in), which differ in the boundary
+// part alone.
+int mt_host(const char* who, const int* dt_bounds, const long long* dt_offsets, const long long* dt_areas, const void* dt_bits,
+            size_t dt_bytes, int nd, const int* dt_classes, const float* dt_scores, const int* gt_bounds, const long long* gt_offsets,
+            const long long* gt_areas, const void* gt_bits, size_t gt_bytes, int ng, const int* gt_classes,
+            const unsigned char* gt_crowd, const unsigned char* gt_ignore_in, const double* gt_eval_area, const double* iou_thrs, int T,
+            const double* area_rngs, int A, int max_det, MtBd* bd, int* rank, int* dt_match, unsigned char* dt_ignore, int* gt_match,
+            unsigned char* gt_ignore, double* iou, int device_id) {
+  MNC_REQUIRE(nd >= 0 && nd <= kMtMaxN, "%s: %d detections not in [0, %d]", who, nd, kMtMaxN);
+  MNC_REQUIRE(rank && dt_match && dt_ignore && gt_match && gt_ignore, "%s: null output pointer", who);
+  MNC_REQUIRE(nd == 0 || (dt_classes && dt_scores), "%s: null classes or scores of the detections", who);
+  for (int k = 0; k < nd; ++k) MNC_REQUIRE(!std::isnan(dt_scores[k]), "%s: score %d is NaN", who, k);
+  int rc = bd ? boundary_check_image(who, bd->H, bd->W, bd->d) : MNC_OK;
+  if (rc) return rc;
+  MtHost h;
+  rc = mt_check(who, gt_bounds, gt_offsets, gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area,
+                iou_thrs, T, area_rngs, A, max_det, &h);
+  if (rc) return rc;
+  HostMaskSet dt;
+  rc = dt.check(who, "dt", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores);
+  if (rc) return rc;
+  const size_t cells = (size_t)A * T, pairs = (size_t)nd * ng;
+  if (nd == 0 || ng == 0) {                              // (no pair: no IoU table has an entry)
+    mt_nothing(h, nd, dt_classes, dt_scores, dt_areas, ng, T, area_rngs, A, max_det, rank, dt_match, dt_ignore, gt_match, gt_ignore);
+    clear_error();
+    return MNC_OK;
+  }
+  // the boundary sets' instance tables follow from the bounds alone
+  std::vector<mnc_mask_info> dbinfo, gbinfo;
+  if (bd) {
+    boundary_plan(dt.info, bd->H, bd->W, bd->d, &dbinfo, &bd->dplan);
+    boundary_plan(h.gt.info, bd->H, bd->W, bd->d, &gbinfo, &bd->gplan);
+  }
+  MtWs w;
+  auto layout = [&](WsLayout l) {
+    dt.take(l);
+    w.layout(l, nd, h, ng, T, A, iou != nullptr);
+    if (bd) {
+      const size_t plane = bd->dplan.bytes > bd->gplan.bytes ? bd->dplan.bytes : bd->gplan.bytes;
+      bd->dinfo = l.take<mnc_mask_info>(nd);
+      bd->ginfo = l.take<mnc_mask_info>(ng);
+      bd->dbits = l.take<u64>(bd->dplan.bytes / 8);
+      bd->gbits = l.take<u64>(bd->gplan.bytes / 8);
+      bd->scratch = l.take<u64>(plane / 8 * bd->dplan.planes);
+      bd->inter = l.take<long long>(pairs);
+      bd->biou = l.take<double>(bd->biou_out ? pairs : 0);
+    }
+    return l.bytes();
+  };
+  HostScope hs;
+  rc = hs.open(device_id, layout(WsLayout()));
+  if (rc) return rc;
+  layout(WsLayout(hs.buf));
+  MNC_HIP_TRY(dt.upload(hs));
+  BdSpan span;                                           // (never begun without the boundary part)
+  if (bd) {
+    if (!bd->biou_out) bd->biou = nullptr;
+    MNC_HIP_TRY(hs.up(bd->dinfo, dbinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
+    MNC_HIP_TRY(hs.up(bd->ginfo, gbinfo.data(), (size_t)ng * sizeof(mnc_mask_info)));
+    span.begin(hs.stream);
+  }
+  rc = mt_launch(hs.stream, dt.view(), nd, h, ng, iou_thrs, T, area_rngs, A, max_det, iou != nullptr, w, bd);
+  if (rc) return rc;
+  span.end(hs.stream);
+  MNC_HIP_TRY(hipGetLastError());
+  MNC_HIP_TRY(hs.down(rank, w.L.rank, (size_t)nd * 4));
+  MNC_HIP_TRY(hs.down(dt_match, w.dt_match, cells * nd * 4));
+  MNC_HIP_TRY(hs.down(dt_ignore, w.dt_ignore, cells * nd));
+  MNC_HIP_TRY(hs.down(gt_match, w.gt_match, cells * ng * 4));
+  MNC_HIP_TRY(hs.down(gt_ignore, w.L.gig, (size_t)A * ng));
+  if (iou) MNC_HIP_TRY(hs.down(iou, w.iou, pairs * 8));
+  if (bd && bd->biou_out) MNC_HIP_TRY(hs.down(bd->biou_out, bd->biou, pairs * 8));
+  MNC_HIP_TRY(hs.sync());
+  span.keep();
+  clear_error();
+  return MNC_OK;
+}
+
 }  // namespace
 
 }  // namespace mnc
@@ -442,51 +504,9 @@ int mnc_mask_match(const int* dt_bounds, const long long* dt_offsets, const long
                    const unsigned char* gt_crowd, const unsigned char* gt_ignore_in, const double* gt_eval_area, const double* iou_thrs,
                    int T, const double* area_rngs, int A, int max_det, int* rank, int* dt_match, unsigned char* dt_ignore,
                    int* gt_match, unsigned char* gt_ignore, double* iou, int device_id) {
-  const char* who = "mnc_mask_match";
-  MNC_REQUIRE(nd >= 0 && nd <= kMtMaxN, "%s: %d detections not in [0, %d]", who, nd, kMtMaxN);
-  MNC_REQUIRE(rank && dt_match && dt_ignore && gt_match && gt_ignore, "%s: null output pointer", who);
-  MNC_REQUIRE(nd == 0 || (dt_classes && dt_scores), "%s: null classes or scores of the detections", who);
-  for (int d = 0; d < nd; ++d) MNC_REQUIRE(!std::isnan(dt_scores[d]), "%s: score %d is NaN", who, d);
-  MtHost h;
-  int rc = mt_check(who, gt_bounds, gt_offsets, gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area,
-                    iou_thrs, T, area_rngs, A, max_det, &h);
-  if (rc) return rc;
-  std::vector<mnc_mask_info> dinfo;
-  size_t dused = 0;
-  rc = ov_table(who, "dt", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores, &dinfo, &dused);
-  if (rc) return rc;
-  const size_t cells = (size_t)A * T;
-  if (nd == 0 || ng == 0) {
-    mt_nothing(h, nd, dt_classes, dt_scores, dt_areas, ng, T, area_rngs, A, max_det, rank, dt_match, dt_ignore, gt_match, gt_ignore);
-    clear_error();
-    return MNC_OK;
-  }
-  mnc_mask_info* d_dinfo; u64* d_dbits; MtWs w;
-  auto layout = [&](WsLayout l) {
-    d_dinfo = l.take<mnc_mask_info>(nd);
-    d_dbits = l.take<u64>(dused / 8);
-    w.layout(l, nd, h, ng, T, A, iou != nullptr);
-    return l.bytes();
-  };
-  HostScope hs;
-  rc = hs.open(device_id, layout(WsLayout()));
-  if (rc) return rc;
-  layout(WsLayout(hs.buf));
-  MNC_HIP_TRY(hs.up(d_dinfo, dinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_dbits, dt_bits, dused));
-  const OvSet D = {d_dinfo, d_dbits, nullptr, nd};
-  rc = mt_launch(hs.stream, D, nd, h, gt_bits, ng, iou_thrs, T, area_rngs, A, max_det, iou != nullptr, w);
-  if (rc) return rc;
-  MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hs.down(rank, w.L.rank, (size_t)nd * 4));
-  MNC_HIP_TRY(hs.down(dt_match, w.dt_match, cells * nd * 4));
-  MNC_HIP_TRY(hs.down(dt_ignore, w.dt_ignore, cells * nd));
-  MNC_HIP_TRY(hs.down(gt_match, w.gt_match, cells * ng * 4));
-  MNC_HIP_TRY(hs.down(gt_ignore, w.L.gig, (size_t)A * ng));
-  if (iou) MNC_HIP_TRY(hs.down(iou, w.iou, (size_t)nd * ng * 8));
-  MNC_HIP_TRY(hs.sync());
-  clear_error();
-  return MNC_OK;
+  return mt_host("mnc_mask_match", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores, gt_bounds, gt_offsets,
+                 gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area, iou_thrs, T, area_rngs, A, max_det,
+                 nullptr, rank, dt_match, dt_ignore, gt_match, gt_ignore, iou, device_id);
 }
 
 // see include/mnc_hip.h
@@ -497,75 +517,12 @@ int mnc_mask_match_boundary(const int* dt_bounds, const long long* dt_offsets, c
                             const double* gt_eval_area, const double* iou_thrs, int T, const double* area_rngs, int A, int max_det,
                             int H, int W, int d, int* rank, int* dt_match, unsigned char* dt_ignore, int* gt_match,
                             unsigned char* gt_ignore, double* iou, double* biou, int device_id) {
-  const char* who = "mnc_mask_match_boundary";
-  MNC_REQUIRE(nd >= 0 && nd <= kMtMaxN, "%s: %d detections not in [0, %d]", who, nd, kMtMaxN);
-  MNC_REQUIRE(rank && dt_match && dt_ignore && gt_match && gt_ignore, "%s: null output pointer", who);
-  MNC_REQUIRE(nd == 0 || (dt_classes && dt_scores), "%s: null classes or scores of the detections", who);
-  for (int k = 0; k < nd; ++k) MNC_REQUIRE(!std::isnan(dt_scores[k]), "%s: score %d is NaN", who, k);
-  int rc = boundary_check_image(who, H, W, d);
-  if (rc) return rc;
-  MtHost h;
-  rc = mt_check(who, gt_bounds, gt_offsets, gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area,
-                iou_thrs, T, area_rngs, A, max_det, &h);
-  if (rc) return rc;
-  std::vector<mnc_mask_info> dinfo;
-  size_t dused = 0;
-  rc = ov_table(who, "dt", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores, &dinfo, &dused);
-  if (rc) return rc;
-  const size_t cells = (size_t)A * T, pairs = (size_t)nd * ng;
-  if (nd == 0 || ng == 0) {                              // (no pair: neither IoU table has an entry)
-    mt_nothing(h, nd, dt_classes, dt_scores, dt_areas, ng, T, area_rngs, A, max_det, rank, dt_match, dt_ignore, gt_match, gt_ignore);
-    clear_error();
-    return MNC_OK;
-  }
-  // the boundary sets' instance tables follow from the bounds alone
-  std::vector<mnc_mask_info> dbinfo, gbinfo;
   MtBd bd;
   bd.H = H; bd.W = W; bd.d = d;
-  boundary_plan(dinfo, H, W, d, &dbinfo, &bd.dplan);
-  boundary_plan(h.ginfo, H, W, d, &gbinfo, &bd.gplan);
-  const size_t plane = bd.dplan.bytes > bd.gplan.bytes ? bd.dplan.bytes : bd.gplan.bytes;
-  mnc_mask_info* d_dinfo; u64* d_dbits; MtWs w;
-  auto layout = [&](WsLayout l) {
-    d_dinfo = l.take<mnc_mask_info>(nd);
-    d_dbits = l.take<u64>(dused / 8);
-    w.layout(l, nd, h, ng, T, A, iou != nullptr);
-    bd.dinfo = l.take<mnc_mask_info>(nd);
-    bd.ginfo = l.take<mnc_mask_info>(ng);
-    bd.dbits = l.take<u64>(bd.dplan.bytes / 8);
-    bd.gbits = l.take<u64>(bd.gplan.bytes / 8);
-    bd.scratch = l.take<u64>(plane / 8 * bd.dplan.planes);
-    bd.inter = l.take<long long>(pairs);
-    bd.biou = l.take<double>(biou ? pairs : 0);
-    return l.bytes();
-  };
-  HostScope hs;
-  rc = hs.open(device_id, layout(WsLayout()));
-  if (rc) return rc;
-  layout(WsLayout(hs.buf));
-  if (!biou) bd.biou = nullptr;
-  MNC_HIP_TRY(hs.up(d_dinfo, dinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_dbits, dt_bits, dused));
-  MNC_HIP_TRY(hs.up(bd.dinfo, dbinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(bd.ginfo, gbinfo.data(), (size_t)ng * sizeof(mnc_mask_info)));
-  const OvSet D = {d_dinfo, d_dbits, nullptr, nd};
-  BdSpan span;
-  span.begin(hs.stream);
-  rc = mt_launch(hs.stream, D, nd, h, gt_bits, ng, iou_thrs, T, area_rngs, A, max_det, iou != nullptr, w, &bd);
-  if (rc) return rc;
-  span.end(hs.stream);
-  MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hs.down(rank, w.L.rank, (size_t)nd * 4));
-  MNC_HIP_TRY(hs.down(dt_match, w.dt_match, cells * nd * 4));
-  MNC_HIP_TRY(hs.down(dt_ignore, w.dt_ignore, cells * nd));
-  MNC_HIP_TRY(hs.down(gt_match, w.gt_match, cells * ng * 4));
-  MNC_HIP_TRY(hs.down(gt_ignore, w.L.gig, (size_t)A * ng));
-  if (iou) MNC_HIP_TRY(hs.down(iou, w.iou, pairs * 8));
-  if (biou) MNC_HIP_TRY(hs.down(biou, bd.biou, pairs * 8));
-  MNC_HIP_TRY(hs.sync());
-  span.keep();
-  clear_error();
-  return MNC_OK;
+  bd.biou_out = biou;
+  return mt_host("mnc_mask_match_boundary", dt_bounds, dt_offsets, dt_areas, dt_bits, dt_bytes, nd, dt_classes, dt_scores, gt_bounds,
+                 gt_offsets, gt_areas, gt_bits, gt_bytes, ng, gt_classes, gt_crowd, gt_ignore_in, gt_eval_area, iou_thrs, T, area_rngs, A,
+                 max_det, &bd, rank, dt_match, dt_ignore, gt_match, gt_ignore, iou, device_id);
 }
 
 // see include/mnc_hip.h
@@ -597,9 +554,7 @@ int mnc_mask_match_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int
   layout(WsLayout(ctx->match_ws.p));
   LaunchScope ls(ctx, "mask_match");
   hipStream_t s = ctx->stream;
-  const mnc_mask_head* head = (const mnc_mask_head*)d_info;
-  const OvSet D = {rows_cap ? (const mnc_mask_info*)(head + 1) : nullptr, (const u64*)d_bits, rows_cap ? &head->kept : nullptr, 0};
-  rc = mt_launch(s, D, rows_cap, h, gt_bits, ng, iou_thrs, T, area_rngs, A, max_det, want_iou != 0, w);
+  rc = mt_launch(s, MaskSet::of_records(d_info, d_bits, rows_cap), rows_cap, h, ng, iou_thrs, T, area_rngs, A, max_det, want_iou != 0, w);
   if (rc) return rc;
   rc = ls.finish("mask_match");
   if (rc) return rc;

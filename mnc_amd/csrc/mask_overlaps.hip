@@ -22,18 +22,17 @@
 // The greedy scan is nms.hip's own (nms_scan_launch / _indirect), unchanged.
 //
 // Bound: L2 reads.  A pair reads the words of its intersection once from each operand (16 bytes per 64 pixels, B's words twice
-// from L1 for the funnel); the work of 100 x 100 instances is spread over 10 000 waves, most of which leave at once.  Staging A's rows through LDS for a tile of partners would cut the reads of a large instance; not built: measured at 100 x 100
-// instances of a 600 x 1000 image the kernel takes 8.5 us of a 56 us call that is launches and copies (profiles/mask_overlaps_bench.txt).
+// from L1 for the funnel); the work of 100 x 100 instances is spread over 10 000 waves, most of which leave at once.  Staging A's rows
+// through LDS for a tile of partners would cut the reads of a large instance.  Not built: measured at 100 x 100 instances of a
+// 600 x 1000 image the kernel takes 8.5 us of a 56 us call that is launches and copies (profiles/mask_overlaps_bench.txt).
 //
 // Compiled with -ffp-contract=off as its siblings are (the lone division has nothing to contract with).
 #include <cmath>
 #include <vector>
 
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
-
-typedef unsigned long long u64;
 
 constexpr int kOvThreads = 256;
 constexpr int kOvWaves = kOvThreads / 64;
@@ -42,29 +41,17 @@ constexpr int kOvMaxCoord = 1 << 24;           // |coordinate| limit: widths, he
 constexpr long long kOvMaxArea = 1LL << 26;    // pixels of one bound
 constexpr int kOvMaxNms = 2048;                // instances of one mask NMS
 
-// (OvSet, one set of packed masks on the device, is declared in mnc_internal.h: mask_match.hip launches the overlap kernel too.)
-__device__ __forceinline__ int ov_count(const OvSet& s, int cap) { return min(max(s.n_ptr ? *s.n_ptr : s.n, 0), cap); }
-
-// Word j of a row of `strips` words holding w columns: 0 outside the row, the padding of the last word cleared.
-__device__ __forceinline__ u64 ov_word(const u64* __restrict__ row, int j, int strips, int w) {
-  if (j < 0 || j >= strips) return 0ull;
-  u64 v = row[j];
-  const int valid = w - (j << 6);
-  if (valid < 64) v &= (1ull << valid) - 1ull;
-  return v;
-}
-
 // grid ceil(rows * cols / 4), block 256.  Pair p = (i, j) of the rows x cols output (row-major, leading dimension cols); rows /
 // cols are the capacities the buffers were sized with, pairs past the sets' counts store 0 / 0.0.  order != nullptr: the pair is
 // (order[i], order[j]) -- the set against itself in score order -- and with upper_only the pairs j <= i store 0 / 0.0 unread.
-__global__ __launch_bounds__(kOvThreads) void mask_overlaps_kernel(OvSet A, OvSet B, const int* __restrict__ order, int upper_only,
+__global__ __launch_bounds__(kOvThreads) void mask_overlaps_kernel(MaskSet A, MaskSet B, const int* __restrict__ order, int upper_only,
                                                                    int rows, int cols, long long* __restrict__ inter_out,
                                                                    double* __restrict__ iou_out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long p = (long long)blockIdx.x * kOvWaves + wave;
   if (p >= (long long)rows * cols) return;
   const int i = (int)(p / cols), j = (int)(p % cols);
-  const int na = ov_count(A, rows), nb = ov_count(B, cols);
+  const int na = mask_count(A, rows), nb = mask_count(B, cols);
   long long inter = 0;
   double iou = 0.0;
   if (i < na && j < nb && !(upper_only && j <= i)) {
@@ -73,7 +60,7 @@ __global__ __launch_bounds__(kOvThreads) void mask_overlaps_kernel(OvSet A, OvSe
     // (an instance without rows has x2 < x1 or y2 < y1: its intersection with anything is empty)
     if (ix1 <= ix2 && iy1 <= iy2) {
       const int wa = a.x2 - a.x1 + 1, wb = b.x2 - b.x1 + 1;
-      const int sa = (wa + 63) >> 6, sb = (wb + 63) >> 6;
+      const int sa = mask_strips(wa), sb = mask_strips(wb);
       const int k_lo = (ix1 - a.x1) >> 6, k_hi = (ix2 - a.x1) >> 6;
       const int nwords = k_hi - k_lo + 1, nrows = iy2 - iy1 + 1;
       const u64* rows_a = A.bits + a.offset / 8 + (long long)(iy1 - a.y1) * sa;
@@ -82,12 +69,9 @@ __global__ __launch_bounds__(kOvThreads) void mask_overlaps_kernel(OvSet A, OvSe
       long long cnt = 0;
       for (int t = lane; t < items; t += 64) {
         const int r = t / nwords, k = k_lo + (t - r * nwords);
-        const u64 wa_bits = ov_word(rows_a + (long long)r * sa, k, sa, wa);
+        const u64 wa_bits = mask_word(rows_a + (long long)r * sa, k, sa, wa);
         const int off = a.x1 + (k << 6) - b.x1;          // bit of B's row under bit 0 of this word, signed
-        const int q = off >> 6, s = off & 63;            // floor division, non-negative remainder
-        const u64* rb = rows_b + (long long)r * sb;
-        u64 wb_bits = ov_word(rb, q, sb, wb);
-        if (s) wb_bits = (wb_bits >> s) | (ov_word(rb, q + 1, sb, wb) << (64 - s));
+        const u64 wb_bits = mask_word_at(rows_b + (long long)r * sb, off, sb, wb);
         cnt += __popcll(wa_bits & wb_bits);
       }
 #pragma unroll
@@ -103,25 +87,16 @@ __global__ __launch_bounds__(kOvThreads) void mask_overlaps_kernel(OvSet A, OvSe
   }
 }
 
-// float32 -> an unsigned key with the floats' order (-0.0 counts as 0.0, as it does for numpy's comparison).  A NaN, which the
-// host entry refuses and a device table cannot be asked about without a read-back, gets the place of its bit pattern: the order
-// is a permutation whatever the scores hold.
-__device__ __forceinline__ unsigned ov_score_key(float s) {
-  if (s == 0.f) s = 0.f;
-  const unsigned u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // grid ceil(cap / 256), block 256.  order[rank of i] = i; *n_out = the count, clamped to cap (what the scan reads).
-__global__ __launch_bounds__(kOvThreads) void mask_order_kernel(OvSet A, int cap, int* __restrict__ order, int* __restrict__ n_out) {
-  const int n = ov_count(A, cap);
+__global__ __launch_bounds__(kOvThreads) void mask_order_kernel(MaskSet A, int cap, int* __restrict__ order, int* __restrict__ n_out) {
+  const int n = mask_count(A, cap);
   const int i = blockIdx.x * kOvThreads + threadIdx.x;
   if (i == 0) *n_out = n;
   if (i >= n) return;
-  const unsigned mine = ov_score_key(A.info[i].score);
+  const unsigned mine = mask_score_key(A.info[i].score);
   int rank = 0;
   for (int j = 0; j < n; ++j) {
-    const unsigned k = ov_score_key(A.info[j].score);
+    const unsigned k = mask_score_key(A.info[j].score);
     rank += (k > mine || (k == mine && j < i)) ? 1 : 0;
   }
   order[rank] = i;
@@ -129,13 +104,13 @@ __global__ __launch_bounds__(kOvThreads) void mask_order_kernel(OvSet A, int cap
 
 // grid ceil(cap * cb_cap / 4), block 256; cb_cap = ceil(cap / 64).  iou [cap][cap] in score order (pairs j > i valid).
 // mask[c * cap + i] = the word of row i in column tile c: nms_scan_kernel's layout with n_stride = cap.
-__global__ __launch_bounds__(kOvThreads) void mask_nms_words_kernel(OvSet A, const int* __restrict__ order, int cap, int cb_cap,
+__global__ __launch_bounds__(kOvThreads) void mask_nms_words_kernel(MaskSet A, const int* __restrict__ order, int cap, int cb_cap,
                                                                     const double* __restrict__ iou, double thresh, int class_aware,
                                                                     u64* __restrict__ mask) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long g = (long long)blockIdx.x * kOvWaves + wave;
   if (g >= (long long)cap * cb_cap) return;
-  const int n = ov_count(A, cap);
+  const int n = mask_count(A, cap);
   const int i = (int)(g / cb_cap), c = (int)(g % cb_cap);
   if (i >= n || c * 64 >= n) return;                     // (the scan reads neither)
   const int col = c * 64 + lane;
@@ -154,19 +129,14 @@ __global__ __launch_bounds__(kOvThreads) void mask_keep_kernel(const int* __rest
   if (r < min(out[0], cap)) out[64 + r] = order[keep[r]];
 }
 
-namespace {
-
-inline long long ov_bytes(int w, int h) { return w < 1 || h < 1 ? 0 : (long long)h * ((w + 63) >> 6) * 8; }
-
-}  // namespace
-
-// The instance table of a host set, checked: MNC_ERR_INVALID before anything is launched.  *used = the bytes of `bits` the rows reach.
-// (Shared with mask_rle.hip: mnc_internal.h.)
-int ov_table(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
-             size_t bytes, int n, const int* classes, const float* scores, std::vector<mnc_mask_info>* info, size_t* used) {
+// The instance table of a host set, checked: MNC_ERR_INVALID before anything is launched.  (Declared in mask_set.h: every host
+// entry of the mask files checks its sets here.)
+int HostMaskSet::check(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas,
+                       const void* bits_in, size_t bytes, int n, const int* classes, const float* scores) {
   MNC_REQUIRE(n == 0 || (bounds && offsets && areas), "%s: null pointer in set %s", who, set);
-  info->assign((size_t)n, mnc_mask_info());
-  *used = 0;
+  info.assign((size_t)n, mnc_mask_info());
+  bits = bits_in;
+  used = 0;
   for (int i = 0; i < n; ++i) {
     const int* q = bounds + 4 * (size_t)i;
     for (int k = 0; k < 4; ++k)
@@ -176,11 +146,11 @@ int ov_table(const char* who, const char* set, const int* bounds, const long lon
                 (long long)w * h, kOvMaxArea);
     MNC_REQUIRE(offsets[i] >= 0 && offsets[i] % 8 == 0, "%s: %s[%d] offset %lld is negative or not a multiple of 8", who, set, i,
                 offsets[i]);
-    const long long need = ov_bytes(w, h);
+    const long long need = mask_bytes(w, h);
     MNC_REQUIRE(need == 0 || ((unsigned long long)offsets[i] <= bytes && bytes - (size_t)offsets[i] >= (size_t)need), "%s: the rows of %s[%d] (%lld bytes at %lld) reach past the %zu bytes given",
                 who, set, i, need, offsets[i], bytes);
-    if (need && (size_t)(offsets[i] + need) > *used) *used = (size_t)(offsets[i] + need);
-    mnc_mask_info& d = (*info)[i];
+    if (need && (size_t)(offsets[i] + need) > used) used = (size_t)(offsets[i] + need);
+    mnc_mask_info& d = info[i];
     d.x1 = q[0]; d.y1 = q[1]; d.x2 = q[2]; d.y2 = q[3];
     d.cls = classes ? classes[i] : 0;
     d.score = scores ? scores[i] : 0.f;
@@ -188,12 +158,12 @@ int ov_table(const char* who, const char* set, const int* bounds, const long lon
     d.offset = offsets[i];
     d.area = areas[i];
   }
-  MNC_REQUIRE(*used == 0 || bits, "%s: null bits in set %s", who, set);
+  MNC_REQUIRE(used == 0 || bits, "%s: null bits in set %s", who, set);
   return MNC_OK;
 }
 
-// (Shared with mask_match.hip: mnc_internal.h.)
-void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
+// (Declared in mask_set.h: mask_match.hip launches the overlap kernel too.)
+void overlaps_launch(hipStream_t s, const MaskSet& A, const MaskSet& B, const int* d_order, int upper_only, int rows, int cols,
                      long long* d_inter, double* d_iou) {
   const long long pairs = (long long)rows * cols;
   if (pairs < 1) return;
@@ -218,7 +188,7 @@ struct NmsWs {
   }
 };
 
-void nms_launch(hipStream_t s, const OvSet& A, int cap, double thresh, int class_aware, const NmsWs& w) {
+void nms_launch(hipStream_t s, const MaskSet& A, int cap, double thresh, int class_aware, const NmsWs& w) {
   const int cb = cdiv(cap, 64);
   hipLaunchKernelGGL(mask_order_kernel, dim3(cdiv(cap, kOvThreads)), dim3(kOvThreads), 0, s, A, cap, w.order, w.out + 1);
   overlaps_launch(s, A, A, w.order, 1, cap, cap, nullptr, w.iou);
@@ -246,22 +216,19 @@ int mnc_mask_overlaps(const int* a_bounds, const long long* a_offsets, const lon
   MNC_REQUIRE(na >= 0 && nb >= 0, "mnc_mask_overlaps: na=%d, nb=%d must be >= 0", na, nb);
   MNC_REQUIRE((long long)na * nb <= kOvMaxPairs, "mnc_mask_overlaps: %d x %d pairs (limit %lld)", na, nb, kOvMaxPairs);
   MNC_REQUIRE(inter || iou, "mnc_mask_overlaps: both outputs are null");
-  std::vector<mnc_mask_info> ia, ib;
-  size_t ua = 0, ub = 0;
-  int rc = ov_table("mnc_mask_overlaps", "a", a_bounds, a_offsets, a_areas, a_bits, a_bytes, na, nullptr, nullptr, &ia, &ua);
+  HostMaskSet a, b;                                      // (b stays empty when the set meets itself)
+  int rc = a.check("mnc_mask_overlaps", "a", a_bounds, a_offsets, a_areas, a_bits, a_bytes, na, nullptr, nullptr);
   if (rc) return rc;
   if (!self) {
-    rc = ov_table("mnc_mask_overlaps", "b", b_bounds, b_offsets, b_areas, b_bits, b_bytes, nb, nullptr, nullptr, &ib, &ub);
+    rc = b.check("mnc_mask_overlaps", "b", b_bounds, b_offsets, b_areas, b_bits, b_bytes, nb, nullptr, nullptr);
     if (rc) return rc;
   }
   if (na == 0 || nb == 0) { clear_error(); return MNC_OK; }
   const size_t pairs = (size_t)na * nb;
-  mnc_mask_info *d_ia, *d_ib; u64 *d_ba, *d_bb; long long* d_inter; double* d_iou;
+  long long* d_inter; double* d_iou;
   auto layout = [&](WsLayout l) {
-    d_ia = l.take<mnc_mask_info>(na);
-    d_ba = l.take<u64>(ua / 8);
-    d_ib = l.take<mnc_mask_info>(self ? 0 : nb);
-    d_bb = l.take<u64>(ub / 8);
+    a.take(l);
+    b.take(l);
     d_inter = l.take<long long>(inter ? pairs : 0);
     d_iou = l.take<double>(iou ? pairs : 0);
     return l.bytes();
@@ -270,13 +237,9 @@ int mnc_mask_overlaps(const int* a_bounds, const long long* a_offsets, const lon
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  MNC_HIP_TRY(hs.up(d_ia, ia.data(), (size_t)na * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_ba, a_bits, ua));
-  if (!self) {
-    MNC_HIP_TRY(hs.up(d_ib, ib.data(), (size_t)nb * sizeof(mnc_mask_info)));
-    MNC_HIP_TRY(hs.up(d_bb, b_bits, ub));
-  }
-  const OvSet A = {d_ia, d_ba, nullptr, na}, B = self ? A : OvSet{d_ib, d_bb, nullptr, nb};
+  MNC_HIP_TRY(a.upload(hs));
+  MNC_HIP_TRY(b.upload(hs));
+  const MaskSet A = a.view(), B = self ? A : b.view();
   overlaps_launch(hs.stream, A, B, nullptr, 0, na, nb, inter ? d_inter : nullptr, iou ? d_iou : nullptr);
   MNC_HIP_TRY(hipGetLastError());
   if (inter) MNC_HIP_TRY(hs.down(inter, d_inter, pairs * 8));
@@ -295,11 +258,10 @@ int mnc_mask_overlaps_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, 
   if (self) nb = rows_cap;
   MNC_REQUIRE(rows_cap >= 0 && nb >= 0, "mnc_mask_overlaps_dev: rows_cap=%d, nb=%d must be >= 0", rows_cap, nb);
   MNC_REQUIRE((long long)rows_cap * nb <= kOvMaxPairs, "mnc_mask_overlaps_dev: %d x %d pairs (limit %lld)", rows_cap, nb, kOvMaxPairs);
-  std::vector<mnc_mask_info> ib;
-  size_t ub = 0;
+  HostMaskSet b;                                         // (stays empty when the set meets itself)
   int rc = MNC_OK;
   if (!self) {
-    rc = ov_table("mnc_mask_overlaps_dev", "b", b_bounds, b_offsets, b_areas, b_bits, b_bytes, nb, nullptr, nullptr, &ib, &ub);
+    rc = b.check("mnc_mask_overlaps_dev", "b", b_bounds, b_offsets, b_areas, b_bits, b_bytes, nb, nullptr, nullptr);
     if (rc) return rc;
   }
   *d_inter = nullptr;
@@ -308,10 +270,9 @@ int mnc_mask_overlaps_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, 
   MNC_REQUIRE(d_info && d_bits, "mnc_mask_overlaps_dev: null device pointer");
   MNC_NO_CAPTURE(ctx, "mnc_mask_overlaps_dev");
   const size_t pairs = (size_t)rows_cap * nb;
-  mnc_mask_info* d_ib; u64* d_bb; long long* inter; double* iou;
+  long long* inter; double* iou;
   auto layout = [&](WsLayout l) {
-    d_ib = l.take<mnc_mask_info>(self ? 0 : nb);
-    d_bb = l.take<u64>(ub / 8);
+    b.take(l);
     inter = l.take<long long>(pairs);
     iou = l.take<double>(pairs);
     return l.bytes();
@@ -322,13 +283,8 @@ int mnc_mask_overlaps_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, 
   layout(WsLayout(ctx->overlap_ws.p));
   LaunchScope ls(ctx, "mask_overlaps");
   hipStream_t s = ctx->stream;
-  if (!self) {
-    MNC_HIP_TRY(hipMemcpyAsync(d_ib, ib.data(), (size_t)nb * sizeof(mnc_mask_info), hipMemcpyHostToDevice, s));
-    if (ub) MNC_HIP_TRY(hipMemcpyAsync(d_bb, b_bits, ub, hipMemcpyHostToDevice, s));
-  }
-  const mnc_mask_head* head = (const mnc_mask_head*)d_info;
-  const OvSet A = {(const mnc_mask_info*)(head + 1), (const u64*)d_bits, &head->kept, 0};
-  const OvSet B = self ? A : OvSet{d_ib, d_bb, nullptr, nb};
+  MNC_HIP_TRY(b.upload(s));
+  const MaskSet A = MaskSet::of_records(d_info, d_bits, rows_cap), B = self ? A : b.view();
   overlaps_launch(s, A, B, nullptr, 0, rows_cap, nb, inter, iou);
   rc = ls.finish("mask_overlaps");
   if (rc) return rc;
@@ -348,16 +304,14 @@ int mnc_mask_nms(const int* bounds, const long long* offsets, const long long* a
   MNC_REQUIRE(!std::isnan(thresh), "mnc_mask_nms: thresh is NaN");
   MNC_REQUIRE(n == 0 || (scores && (classes || !class_aware)), "mnc_mask_nms: null scores or classes");
   for (int i = 0; i < n; ++i) MNC_REQUIRE(!std::isnan(scores[i]), "mnc_mask_nms: score %d is NaN", i);
-  std::vector<mnc_mask_info> info;
-  size_t used = 0;
-  int rc = ov_table("mnc_mask_nms", "masks", bounds, offsets, areas, bits, bytes, n, classes, scores, &info, &used);
+  HostMaskSet set;
+  int rc = set.check("mnc_mask_nms", "masks", bounds, offsets, areas, bits, bytes, n, classes, scores);
   if (rc) return rc;
   *num_out = 0;
   if (n == 0) { clear_error(); return MNC_OK; }
-  mnc_mask_info* d_info; u64* d_bits; NmsWs w;
+  NmsWs w;
   auto layout = [&](WsLayout l) {
-    d_info = l.take<mnc_mask_info>(n);
-    d_bits = l.take<u64>(used / 8);
+    set.take(l);
     w.layout(l, n);
     return l.bytes();
   };
@@ -365,10 +319,8 @@ int mnc_mask_nms(const int* bounds, const long long* offsets, const long long* a
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  MNC_HIP_TRY(hs.up(d_info, info.data(), (size_t)n * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_bits, bits, used));
-  const OvSet A = {d_info, d_bits, nullptr, n};
-  nms_launch(hs.stream, A, n, thresh, class_aware, w);
+  MNC_HIP_TRY(set.upload(hs));
+  nms_launch(hs.stream, set.view(), n, thresh, class_aware, w);
   MNC_HIP_TRY(hipGetLastError());
   std::vector<int> out(64 + (size_t)n);
   MNC_HIP_TRY(hs.down(out.data(), w.out, out.size() * 4));       // the count and the kept rows in one copy
@@ -401,9 +353,7 @@ int mnc_mask_nms_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int r
   if (rows_cap == 0) {
     MNC_HIP_TRY(hipMemsetAsync(w.out, 0, 256, s));
   } else {
-    const mnc_mask_head* head = (const mnc_mask_head*)d_info;
-    const OvSet A = {(const mnc_mask_info*)(head + 1), (const u64*)d_bits, &head->kept, 0};
-    nms_launch(s, A, rows_cap, thresh, class_aware, w);
+    nms_launch(s, MaskSet::of_records(d_info, d_bits, rows_cap), rows_cap, thresh, class_aware, w);
   }
   rc = ls.finish("mask_nms");
   if (rc) return rc;

@@ -34,11 +34,10 @@
 #include <exception>
 #include <vector>
 
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
 
-typedef unsigned long long u64;
 
 constexpr int kPolyThreads = 256;
 constexpr int kPolyMaxN = 2048;                  // annotations of one call
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(kPolyThreads) void poly_write_kernel(const mnc_mask
   const mnc_mask_info m = info[blockIdx.y];
   const int w = m.x2 - m.x1 + 1, h = m.y2 - m.y1 + 1;
   if (w < 1 || h < 1) return;
-  const int strips = (w + 63) >> 6;
+  const int strips = mask_strips(w);
   const long long k = (long long)blockIdx.x * kPolyThreads + threadIdx.x;
   if (k >= (long long)h * strips) return;
   const int r = (int)(k / strips), s = (int)(k - (long long)r * strips);
@@ -367,7 +366,7 @@ int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const lo
     words += (long long)anns[i].px.nr * anns[i].px.nw;
   }
   // no tight box is larger than the image: room beyond that is never used
-  const size_t image = (size_t)H * cdiv(W, 64) * 8, most = image * n;
+  const size_t image = (size_t)H * mask_strips(W) * 8, most = image * n;
   const size_t room = !bits ? 0 : (bits_cap < most ? bits_cap : most) & ~(size_t)7;
   PolyEdge* d_edges; PolyPlane* d_planes; PolyAnn* d_anns; PolyBox* d_boxes; mnc_mask_info* d_info; int* d_flag; u64* d_ws; u64* d_bits;
   auto layout = [&](WsLayout l) {
@@ -424,7 +423,7 @@ int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const lo
     offsets[i] = d.offset;
     areas[i] = b.area;
     if (w < 1 || h < 1) continue;
-    const long long count = (long long)h * cdiv(w, 64);
+    const long long count = (long long)h * mask_strips(w);
     need += (size_t)count * 8;
     if (count > most_words) most_words = count;
   }

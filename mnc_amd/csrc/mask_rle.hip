@@ -35,25 +35,14 @@
 #include <exception>
 #include <vector>
 
-#include "mnc_internal.h"
+#include "mask_set.h"
 
 namespace mnc {
-
-typedef unsigned long long u64;
 
 constexpr int kRleThreads = 256;
 constexpr int kRleWaves = kRleThreads / 64;
 constexpr int kRleMaxN = 2048;                 // instances of one call
 constexpr int kRleMaxSide = 32768;             // H, W limit: H * W <= 2^30, a position fits an unsigned
-
-struct RleSet {
-  const mnc_mask_info* info;
-  const u64* bits;
-  const int* n_ptr;
-  int n;
-};
-
-__device__ __forceinline__ int rle_count(const RleSet& s, int cap) { return min(max(s.n_ptr ? *s.n_ptr : s.n, 0), cap); }
 
 // An instance in an H x W image.
 struct RleGeom {
@@ -74,28 +63,16 @@ __device__ __forceinline__ RleGeom rle_geom(const mnc_mask_info& m, const u64* b
   RleGeom g;
   g.x1 = m.x1; g.y1 = m.y1;
   g.w = m.x2 - m.x1 + 1;
-  g.sw = (g.w + 63) >> 6;
+  g.sw = mask_strips(g.w);
   g.ax = max(m.x1, 0); g.ay = max(m.y1, 0); g.bx = min(m.x2, W - 1); g.by = min(m.y2, H - 1);
   rle_extent(m.x1, m.y1, m.x2, m.y2, H, W, &g.ncols, &g.nrows);
   g.rows = bits + m.offset / 8;
   return g;
 }
 
-// Word j of a row of `strips` words holding w columns: 0 outside the row, the padding of the last word cleared.
-__device__ __forceinline__ u64 rle_word(const u64* __restrict__ row, int j, int strips, int w) {
-  if (j < 0 || j >= strips) return 0ull;
-  u64 v = row[j];
-  const int valid = w - (j << 6);
-  if (valid < 64) v &= (1ull << valid) - 1ull;
-  return v;
-}
-
 // The 64 pixels (X0 .. X0 + 63, y) of the instance, ay <= y <= by and ax <= X0 <= bx + 1: bit k is column X0 + k; columns past bx read 0.
 __device__ __forceinline__ u64 rle_row_bits(const RleGeom& g, int y, int X0) {
-  const u64* row = g.rows + (long long)(y - g.y1) * g.sw;
-  const int off = X0 - g.x1, q = off >> 6, s = off & 63;
-  u64 v = rle_word(row, q, g.sw, g.w);
-  if (s) v = (v >> s) | (rle_word(row, q + 1, g.sw, g.w) << (64 - s));
+  u64 v = mask_word_at(g.rows + (long long)(y - g.y1) * g.sw, X0 - g.x1, g.sw, g.w);
   const int inside = g.bx - X0 + 1;
   if (inside < 64) v &= inside > 0 ? (1ull << inside) - 1ull : 0ull;
   return v;
@@ -120,12 +97,12 @@ __device__ __forceinline__ int rle_wave_incl_scan(int v, int lane) {
 // transitions of every column of the strip there; kEmit = 1 reads their exclusive prefix from it and stores the positions of the
 // transitions at pos[run_ptr[i] + ...], slots >= runs_cap dropped.
 template <bool kEmit>
-__global__ __launch_bounds__(kRleThreads) void rle_columns_kernel(RleSet A, int cap, int H, int W, int stride, int* __restrict__ cols,
+__global__ __launch_bounds__(kRleThreads) void rle_columns_kernel(MaskSet A, int cap, int H, int W, int stride, int* __restrict__ cols,
                                                                   const long long* __restrict__ run_ptr, unsigned* __restrict__ pos,
                                                                   long long runs_cap) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.y, strip = blockIdx.x * kRleWaves + wave;
-  if (i >= rle_count(A, cap)) return;
+  if (i >= mask_count(A, cap)) return;
   const RleGeom g = rle_geom(A.info[i], A.bits, H, W);
   if (strip * 64 >= g.ncols) return;                     // (uniform over the wave; an instance outside the image has no columns)
   const int X0 = g.ax + strip * 64;
@@ -164,10 +141,10 @@ __global__ __launch_bounds__(kRleThreads) void rle_columns_kernel(RleSet A, int 
 }
 
 // grid cap, block 64.  cols [cap][stride] -> the exclusive prefix over each instance's columns; sums [cap].
-__global__ __launch_bounds__(64) void rle_scan_columns_kernel(RleSet A, int cap, int H, int W, int stride, int* __restrict__ cols,
+__global__ __launch_bounds__(64) void rle_scan_columns_kernel(MaskSet A, int cap, int H, int W, int stride, int* __restrict__ cols,
                                                               int* __restrict__ sums) {
   const int i = blockIdx.x, lane = threadIdx.x;
-  if (i >= rle_count(A, cap)) return;
+  if (i >= mask_count(A, cap)) return;
   const mnc_mask_info m = A.info[i];
   int ncols, nrows;
   rle_extent(m.x1, m.y1, m.x2, m.y2, H, W, &ncols, &nrows);
@@ -193,10 +170,10 @@ struct RleHead {
 static_assert(sizeof(RleHead) == 256, "the layout include/mnc_hip.h documents");
 
 // grid 1, block 64.  run_ptr [cap + 1]: instance i has sums[i] + 1 runs; the entries past the count repeat the total.
-__global__ __launch_bounds__(64) void rle_scan_runs_kernel(RleSet A, int cap, const int* __restrict__ sums, RleHead* __restrict__ head,
+__global__ __launch_bounds__(64) void rle_scan_runs_kernel(MaskSet A, int cap, const int* __restrict__ sums, RleHead* __restrict__ head,
                                                            long long* __restrict__ run_ptr) {
   const int lane = threadIdx.x;
-  const int n = rle_count(A, cap);
+  const int n = mask_count(A, cap);
   long long base = 0;
   for (int i0 = 0; i0 <= cap; i0 += 64) {
     const int i = i0 + lane;
@@ -288,7 +265,7 @@ __global__ __launch_bounds__(kRleThreads) void rle_fill_kernel(const mnc_mask_in
   const mnc_mask_info m = info[i];
   const int w = m.x2 - m.x1 + 1, h = m.y2 - m.y1 + 1;
   if (w < 1 || h < 1) return;
-  const int strips = (w + 63) >> 6, tiles = (h + 63) >> 6;
+  const int strips = mask_strips(w), tiles = (h + 63) >> 6;
   const int strip = item % strips, tile = item / strips;
   if (tile >= tiles) return;                             // (uniform over the wave)
   const int rows = min(64, h - tile * 64);
@@ -341,9 +318,9 @@ struct RleWs {
 // out: [RleHead | run_ptr [cap + 1] | runs [runs_cap]].  The bytes of it in front of the runs:
 inline size_t rle_front(int cap) { return sizeof(RleHead) + ((size_t)cap + 1) * 8; }
 
-void rle_launch(hipStream_t s, const RleSet& A, int cap, int H, int W, const RleWs& w, void* out, size_t runs_cap) {
+void rle_launch(hipStream_t s, const MaskSet& A, int cap, int H, int W, const RleWs& w, void* out, size_t runs_cap) {
   RleHead* head = (RleHead*)out;
-  long long* run_ptr = (long long*)(head + 1);
+  long long* run_ptr = (long long*)((char*)out + sizeof(RleHead));
   unsigned* runs = (unsigned*)((char*)out + rle_front(cap));
   const dim3 grid(cdiv(w.stride / 64, kRleWaves), cap);
   hipLaunchKernelGGL(rle_columns_kernel<false>, grid, dim3(kRleThreads), 0, s, A, cap, H, W, w.stride, w.cols, nullptr, nullptr, 0LL);
@@ -368,10 +345,9 @@ int mnc_mask_rle(const int* bounds, const long long* offsets, const void* bits, 
   MNC_REQUIRE(n >= 0 && n <= kRleMaxN, "mnc_mask_rle: n=%d not in [0, %d]", n, kRleMaxN);
   MNC_REQUIRE(H >= 1 && W >= 1 && H <= kRleMaxSide && W <= kRleMaxSide, "mnc_mask_rle: image %d x %d not in [1, %d]", H, W, kRleMaxSide);
   MNC_REQUIRE(run_ptr && runs_total, "mnc_mask_rle: null output pointer");
-  std::vector<mnc_mask_info> info;
+  HostMaskSet set;
   std::vector<long long> areas((size_t)n, 0);
-  size_t used = 0;
-  int rc = ov_table("mnc_mask_rle", "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr, &info, &used);
+  int rc = set.check("mnc_mask_rle", "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   *runs_total = 0;
   run_ptr[0] = 0;
@@ -382,15 +358,15 @@ int mnc_mask_rle(const int* bounds, const long long* offsets, const void* bits, 
   int widest = 1;
   for (int i = 0; i < n; ++i) {
     int ncols, nrows;
-    rle_extent(info[i].x1, info[i].y1, info[i].x2, info[i].y2, H, W, &ncols, &nrows);
+    const mnc_mask_info& m = set.info[i];
+    rle_extent(m.x1, m.y1, m.x2, m.y2, H, W, &ncols, &nrows);
     most += (size_t)ncols * ((size_t)nrows + 1) + 1;
     if (ncols > widest) widest = ncols;
   }
   const size_t cap = !runs ? 0 : runs_cap < most ? runs_cap : most;
-  mnc_mask_info* d_info; u64* d_bits; RleWs w; char* d_out;
+  RleWs w; char* d_out;
   auto layout = [&](WsLayout l) {
-    d_info = l.take<mnc_mask_info>(n);
-    d_bits = l.take<u64>(used / 8);
+    set.take(l);
     w.layout(l, n, widest, cap);
     d_out = l.take<char>(rle_front(n) + cap * 4);
     return l.bytes();
@@ -399,10 +375,8 @@ int mnc_mask_rle(const int* bounds, const long long* offsets, const void* bits, 
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  MNC_HIP_TRY(hs.up(d_info, info.data(), (size_t)n * sizeof(mnc_mask_info)));
-  MNC_HIP_TRY(hs.up(d_bits, bits, used));
-  const RleSet A = {d_info, d_bits, nullptr, n};
-  rle_launch(hs.stream, A, n, H, W, w, d_out, cap);
+  MNC_HIP_TRY(set.upload(hs));
+  rle_launch(hs.stream, set.view(), n, H, W, w, d_out, cap);
   MNC_HIP_TRY(hipGetLastError());
   MNC_HIP_TRY(hs.down(run_ptr, d_out + sizeof(RleHead), ((size_t)n + 1) * 8));
   MNC_HIP_TRY(hs.sync());
@@ -440,9 +414,7 @@ int mnc_mask_rle_dev(mnc_ctx* ctx, const void* d_info, const void* d_bits, int r
   if (rows_cap == 0) {
     MNC_HIP_TRY(hipMemsetAsync(out, 0, rle_front(0), s));
   } else {
-    const mnc_mask_head* head = (const mnc_mask_head*)d_info;
-    const RleSet A = {(const mnc_mask_info*)(head + 1), (const u64*)d_bits, &head->kept, 0};
-    rle_launch(s, A, rows_cap, H, W, w, out, runs_cap);
+    rle_launch(s, MaskSet::of_records(d_info, d_bits, rows_cap), rows_cap, H, W, w, out, runs_cap);
   }
   rc = ls.finish("mask_rle");
   if (rc) return rc;
@@ -487,7 +459,7 @@ int mnc_mask_from_rle(const long long* run_ptr, const unsigned* runs, int n, int
     MNC_REQUIRE(at == HW, "mnc_mask_from_rle: the counts of mask %d sum to %llu, not %d x %d", i, at, H, W);
   }
   // no tight box is larger than the image: room beyond that is never used
-  const size_t image = (size_t)H * cdiv(W, 64) * 8, most = image * n;
+  const size_t image = (size_t)H * mask_strips(W) * 8, most = image * n;
   const size_t room = !bits ? 0 : (bits_cap < most ? bits_cap : most) & ~(size_t)7;
   long long* d_ptr; unsigned* d_starts; RleBox* d_boxes; mnc_mask_info* d_info; u64* d_bits;
   auto layout = [&](WsLayout l) {
@@ -525,7 +497,7 @@ int mnc_mask_from_rle(const long long* run_ptr, const unsigned* runs, int n, int
     offsets[i] = d.offset;
     areas[i] = b.area;
     if (w < 1 || h < 1) continue;
-    need += (size_t)h * cdiv(w, 64) * 8;
+    need += (size_t)h * mask_strips(w) * 8;
     if (cdiv(w, 64) * cdiv(h, 64) > items) items = cdiv(w, 64) * cdiv(h, 64);
   }
   *bits_bytes = need;

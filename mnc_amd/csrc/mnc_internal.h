@@ -229,8 +229,8 @@ struct CallBuf {
 };
 
 // Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances,
-// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle, mnc_mask_match): the
-// device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
+// mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle, mnc_mask_match, mnc_mask_match_boundary,
+// mnc_mask_boundary, mnc_mask_from_polygons, mnc_coco_accumulate): the device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
 // mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
 // ctypes releases the GIL, so two host threads may be inside such entry points on one device.
 struct HostScope {
@@ -259,46 +259,6 @@ int nms_mask_launch_indirect(hipStream_t stream, const float* d_boxes, const int
 int nms_scan_launch_indirect(hipStream_t stream, const unsigned long long* d_mask, const int* d_n, int n_cap, int max_keep,
                              int* d_keep, int* d_num, const float* d_gather_boxes = nullptr, const int* d_gather_order = nullptr,
                              float* d_rois = nullptr, int rois_cap = 0);   // d_rois: the ProposalLayer's RoI rows written by the same launch
-// mask_overlaps.hip: the instance table of a host set of packed masks (bounds, offsets, areas as include/mnc_hip.h n5 gives them),
-// checked against the coordinate, pixel and offset limits of mnc_mask_overlaps; *used = the bytes of `bits` the rows reach
-int ov_table(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
-             size_t bytes, int n, const int* classes, const float* scores, std::vector<mnc_mask_info>* info, size_t* used);
-// mask_overlaps.hip: one set of packed masks on the device -- the instance table, the words, and the count (read from *n_ptr when
-// that is set) -- and the launch of the overlap kernel over rows x cols pairs of two of them (pairs past the sets' counts store
-// 0 / 0.0; d_order != nullptr: the set against itself in that order; either output may be null)
-struct OvSet {
-  const mnc_mask_info* info;
-  const unsigned long long* bits;
-  const int* n_ptr;
-  int n;
-};
-void overlaps_launch(hipStream_t s, const OvSet& A, const OvSet& B, const int* d_order, int upper_only, int rows, int cols,
-                     long long* d_inter, double* d_iou);
-// mask_boundary.hip: the boundary bands (include/mnc_hip.h n11) of one set of packed masks on the device.  boundary_plan makes, on
-// the host, the instance table of the result from the input's (bounds clipped to the H x W image, not tightened; (0, 0, -1, -1)
-// for an instance without rows or outside the image; offsets in order without gaps; areas 0, which the launch adds to; class,
-// score and row carried over) and what the launch needs; boundary_launch writes every word of d_out_bits once and adds the bit
-// counts to d_out_info[i].area.  d_out_info holds the uploaded table of boundary_plan, d_scratch plan.planes * plan.bytes bytes.
-struct BdPlan {
-  int n;                  // instances
-  int planes;             // scratch planes of `bytes` each: the row-eroded words, and for a large d their block prefix ANDs
-  size_t bytes;           // of the clipped masks = of the result's bits
-  long long most_words;   // of one instance
-  long long most_scan;    // (word columns x blocks of 2d + 1 rows) of one instance
-};
-void boundary_plan(const std::vector<mnc_mask_info>& in, int H, int W, int d, std::vector<mnc_mask_info>* out, BdPlan* plan);
-void boundary_launch(hipStream_t s, const OvSet& in, int H, int W, int d, const BdPlan& plan, mnc_mask_info* d_out_info,
-                     unsigned long long* d_out_bits, unsigned long long* d_scratch);
-int boundary_check_image(const char* who, int H, int W, int d);   // MNC_ERR_INVALID: H or W outside [1, 32768], d outside [1, 1024]
-// mnc_mask_boundary_timing's event pair around the launches of one call; keep() after the stream was synchronised
-struct BdSpan {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  ~BdSpan();
-  void begin(hipStream_t s);
-  void end(hipStream_t s);
-  void keep();
-};
 void proposal_state_free(void* state);  // proposal.hip
 void comm_free(mnc_ctx* ctx);           // comm.hip
 void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,

@@ -456,10 +456,12 @@ def mask_nms_numpy(pm, thresh, class_aware=False):
     return np.array(keep, np.int32)
 
 
-def _set_args(pm):
-    """The six arguments of one host set.  (An empty bits array still has an address: NULL would mean "B is A".)"""
+def _set_args(pm, areas=True):
+    """The six arguments of one host set; five, without the areas, for the entries that take none (mnc_mask_rle).  (An empty bits
+    array still has an address: NULL would mean "B is A".)"""
     bits = pm.bits if pm.bits.size else np.zeros(1, np.uint64)
-    return (_lib.ptr(pm.bounds), _lib.ptr(pm.offsets), _lib.ptr(pm.areas), _lib.ptr(bits), int(pm.bits.nbytes), len(pm))
+    return ((_lib.ptr(pm.bounds), _lib.ptr(pm.offsets)) + ((_lib.ptr(pm.areas),) if areas else ()) +
+            (_lib.ptr(bits), int(pm.bits.nbytes), len(pm)))
 
 
 def _device_id(device_id):

@@ -18,7 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .masks import MAX_SIDE, PackedMasks, _device_id
+from .masks import MAX_SIDE, PackedMasks, _device_id, _set_args
 
 MAX_MASKS = 2048
 FIRST_RUNS = 1 << 16            # room of the first mnc_mask_rle_dev of a device-resident result; one retry at the true total
@@ -135,16 +135,11 @@ def string_to_counts(s):
     return out.astype(np.uint32)
 
 
-def _mask_set_args(pm):
-    bits = pm.bits if pm.bits.size else np.zeros(1, np.uint64)
-    return _lib.ptr(pm.bounds), _lib.ptr(pm.offsets), _lib.ptr(bits), int(pm.bits.nbytes), len(pm)
-
-
 def rle_counts_call(pm, H, W, runs=None, device_id=0):
     """mnc_mask_rle as it is: runs None asks for run_ptr and the total only.  -> (run_ptr, total)."""
     run_ptr, total = np.zeros(len(pm) + 1, np.int64), ctypes.c_size_t(0)
-    _lib.call("mnc_mask_rle", *(_mask_set_args(pm) + (int(H), int(W), _lib.ptr(run_ptr), _lib.ptr(runs),
-                                                      runs.size if runs is not None else 0, ctypes.addressof(total), int(device_id))))
+    _lib.call("mnc_mask_rle", *(_set_args(pm, areas=False) + (int(H), int(W), _lib.ptr(run_ptr), _lib.ptr(runs),
+                                                             runs.size if runs is not None else 0, ctypes.addressof(total), int(device_id))))
     return run_ptr, int(total.value)
 
 
