@@ -477,6 +477,67 @@ MNC_API int mnc_mask_match_boundary(const int* dt_bounds, const long long* dt_of
 MNC_API int mnc_mask_boundary_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n12 The masks as shapes: connected components of packed masks, and what is built on them -- the component table, the
+ *     selection by area, the filling of holes, one instance per region (csrc/mask_components.hip, csrc/mask_cc.h) -- on the
+ *     layout of n5.  The statements of the rule are mnc_amd/components.py:components_numpy, select_numpy, fill_holes_numpy
+ *     and split_numpy.
+ *     A component of instance i is a maximal set of its set pixels connected under `connectivity` 4 (edge neighbours) or 8
+ *     (edge and corner neighbours).  Padding bits are not trusted; pixels outside the instance's bounds are background; an
+ *     instance without rows has no components.  The components of an instance are numbered by their first pixel in row-major
+ *     order (lowest y, then lowest x: scipy.ndimage.label's numbering); the components of a set are those of instance 0, then
+ *     of instance 1, ...: comp_ptr [n + 1], comp_ptr[0] = 0, instance i has the components comp_ptr[i] .. comp_ptr[i + 1] - 1.
+ *     Runs are labelled, not pixels.  Per 64-bit word the run starts are v & ~((v << 1) | carry), a scan of their counts over
+ *     the words of the set numbers the runs in raster order; one thread per word unites its runs with the runs of the row
+ *     above that they touch, in a lock-free union-find whose smaller id always becomes the parent (parent[i] <= i at every
+ *     moment, so every find ends whatever the interleaving); a run is a root when it is its own parent, a scan of the root
+ *     flags numbers the components in first-pixel order.  Integer atomics only (min, max, add, compare-and-swap); no output
+ *     depends on the order in which they arrive: the same input gives the same bytes on every run.
+ *     Every entry takes the set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds
+ *     (the areas are not needed).  n == 0 and sets without a single row are answered on the host.  MNC_ERR_INVALID, checked on
+ *     the host before anything is launched, for every entry: connectivity not 4 or 8; everything mnc_mask_rle refuses about a
+ *     set (n outside [0, 2048], |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or not a
+ *     multiple of 8, rows that reach past bytes); more than 2^25 words (256 MiB) of rows in the set, for mnc_mask_fill_holes
+ *     counted on the boxes grown by one pixel on every side (a word holds at most 32 runs: run ids stay below 2^30); a null
+ *     pointer where one is needed.  (There are no forms that read a device-resident mnc_mask_records result: the PackedMasks
+ *     methods fetch such a result first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* The component table.  Outputs: comp_ptr [n + 1], *n_comp = C = comp_ptr[n]; per component area [C] (pixels), bbox [C][4]
+ * (x1, y1, x2, y2 in image coordinates, inclusive and tight), anchor [C][2] (x, y of its first pixel).  area == NULL: comp_ptr
+ * and *n_comp only (bbox and anchor are not looked at).  Otherwise comp_cap is the room of area, bbox and anchor in components;
+ * comp_cap < C is MNC_ERR_INVALID with comp_ptr and *n_comp set and nothing else written, so that the caller calls again with
+ * room.  Entries past C are never written. */
+MNC_API int mnc_mask_components(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int connectivity,
+                                long long* comp_ptr, long long* area, int* bbox, int* anchor, size_t comp_cap, size_t* n_comp,
+                                int device_id);
+/* The selection.  A component stays when its area is >= min_area and, with keep > 0, it is among the keep largest of its
+ * instance (larger area first, equal areas to the lower component number).  The result has the input's bounds and offsets:
+ * out_bits receives the words of every instance at the input's offsets (every word of every row once, padding bits 0; bytes
+ * between and behind the rows are not written), out_areas [n] the true bit counts.  bits_cap below the bytes the rows reach is
+ * MNC_ERR_INVALID.  min_area = 1, keep = 0 gives the input with its padding cleared.  MNC_ERR_INVALID as above, and: a negative
+ * min_area or keep; rows of two instances that overlap or stand out of order (offsets[i] below the end of the rows before). */
+MNC_API int mnc_mask_select(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int connectivity,
+                            int min_area, int keep, long long* out_areas, void* out_bits, size_t bits_cap, int device_id);
+/* The filling of holes.  `connectivity` is that of the background.  A hole of instance i is a component of the unset pixels of
+ * its box that is not connected to the outside of the box: the labelling above on the complement of the box grown by a frame of
+ * one background pixel, every component but the frame's.  The result is the mask OR its holes, in the layout and under the
+ * rules of mnc_mask_select (scipy.ndimage.binary_fill_holes with the 4- or 8-neighbour structure). */
+MNC_API int mnc_mask_fill_holes(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int connectivity,
+                                long long* out_areas, void* out_bits, size_t bits_cap, int device_id);
+/* One instance per component, in component order: out_bounds [C][4] the tight boxes, out_offsets [C] (multiples of 8, in order
+ * without gaps), out_areas [C], out_source [C] (the instance the component came from), the rows in out_bits (padding bits 0),
+ * *n_comp = C, *bits_bytes = the bytes of the rows.  out_bits == NULL: *n_comp and *bits_bytes only.  Otherwise comp_cap < C or
+ * bits_cap < *bits_bytes is MNC_ERR_INVALID with both sizes set and nothing else written.  Entries and bytes past the reported
+ * sizes are never written.  Also MNC_ERR_INVALID, after the table pass: more than 2^31 words of rows in the result. */
+MNC_API int mnc_mask_split(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int connectivity,
+                           int* out_bounds, long long* out_offsets, long long* out_areas, int* out_source, size_t comp_cap,
+                           size_t* n_comp, void* out_bits, size_t bits_cap, size_t* bits_bytes, int device_id);
+/* For tools/mask_components_bench.py.  on = 1: the following calls of the four entries above put a HIP event pair around their
+ * launches (with the read-back of the run total between them, without the copies of the set and of the results) and keep the
+ * last call's time in milliseconds; on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before
+ * this call, -1.0 when there is none; switching on forgets it. */
+MNC_API int mnc_mask_components_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -269,6 +269,29 @@ def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None,
     return dt.match_boundary(gt, H, W, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, d, ratio, return_iou, cfg.GPU_ID)
 
 
+def mask_components(pm, connectivity=8):
+    """The connected components of a PackedMasks on the GPU (mnc_mask_components, csrc/mask_components.hip) ->
+    mnc_amd.components.Components(comp_ptr, area, bbox, anchor)."""
+    return pm.components(connectivity, device_id=cfg.GPU_ID)
+
+
+def mask_select(pm, connectivity=8, min_area=1, keep=0):
+    """The components of area >= min_area, with keep > 0 the `keep` largest of each instance, on the GPU (mnc_mask_select) ->
+    mnc_amd.masks.PackedMasks in the input's layout."""
+    return pm.select(connectivity, min_area, keep, device_id=cfg.GPU_ID)
+
+
+def mask_fill_holes(pm, connectivity=4):
+    """The masks OR their holes (background of this connectivity that does not reach the box's outside) on the GPU
+    (mnc_mask_fill_holes) -> mnc_amd.masks.PackedMasks in the input's layout."""
+    return pm.fill_holes(connectivity, device_id=cfg.GPU_ID)
+
+
+def mask_split(pm, connectivity=8):
+    """One instance per connected component on the GPU (mnc_mask_split) -> (mnc_amd.masks.PackedMasks, source int32 [C])."""
+    return pm.split(connectivity, device_id=cfg.GPU_ID)
+
+
 def mask_rle(pm, H, W):
     """COCO RLEs of a PackedMasks in an H x W image on the GPU (mnc_mask_rle / mnc_mask_rle_dev): -> [{"size": [H, W], "counts":
     str}] per instance."""

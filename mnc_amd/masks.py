@@ -15,6 +15,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     PackedMasks.from_polygons / .from_segmentations   COCO polygon segmentations rasterised into the layout (mnc_amd/polygons.py, n9)
     PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
     PackedMasks.boundary / .match_boundary   the boundary bands and the matching on min(mask IoU, boundary IoU) (mnc_amd/boundary.py, n11)
+    PackedMasks.components / .select / .fill_holes / .split   connected components and what is built on them (mnc_amd/components.py, n12)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -159,6 +160,33 @@ class PackedMasks(object):
         from . import coco_eval
         return coco_eval.match_boundary(self, gt, H, W, iscrowd, ignore, eval_area, iou_thrs, area_rngs, max_det, d, ratio, return_iou,
                                         device_id)
+
+    def components(self, connectivity=8, device_id=None):
+        """The connected components of every instance under 4- or 8-connectivity -> mnc_amd.components.Components(comp_ptr, area,
+        bbox, anchor), numbered by first pixel in row-major order, by the rule of mnc_amd.components.components_numpy
+        (include/mnc_hip.h n12, csrc/mask_components.hip) on the GPU.  A device-resident result is fetched to the host first."""
+        from . import components
+        return components.components(self, connectivity, device_id)
+
+    def select(self, connectivity=8, min_area=1, keep=0, device_id=None):
+        """The components of area >= min_area and, with keep > 0, among the `keep` largest of their instance -> a host PackedMasks
+        with this one's bounds and offsets (mnc_amd.components.select_numpy's rule through mnc_mask_select).  A device-resident
+        result is fetched to the host first."""
+        from . import components
+        return components.select(self, connectivity, min_area, keep, device_id)
+
+    def fill_holes(self, connectivity=4, device_id=None):
+        """These masks OR their holes, `connectivity` being the background's -> a host PackedMasks with this one's bounds and
+        offsets (mnc_amd.components.fill_holes_numpy's rule through mnc_mask_fill_holes).  A device-resident result is fetched to
+        the host first."""
+        from . import components
+        return components.fill_holes(self, connectivity, device_id)
+
+    def split(self, connectivity=8, device_id=None):
+        """One instance per connected component, tight bounds, in component order -> (a host PackedMasks, source int32 [C])
+        (mnc_amd.components.split_numpy's rule through mnc_mask_split).  A device-resident result is fetched to the host first."""
+        from . import components
+        return components.split(self, connectivity, device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

@@ -4,13 +4,16 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR] [--save-coco FILE]
+                         [--save-masks DIR] [--save-coco FILE] [--min-component-area A [--largest-component]]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
 `--cpu` is accepted and ignored by the network, exactly as in the reference (demo.py:40-42 vs :126); with --save-masks it selects
 the numpy form of the per-instance masks (transform.mask_transform.instance_masks_numpy) instead of the GPU's, with --save-coco
-the numpy form of the run-length encoding as well (mnc_amd.rle.rle_counts_numpy)."""
+the numpy form of the run-length encoding as well (mnc_amd.rle.rle_counts_numpy).  --min-component-area A drops the 8-connected
+components of fewer than A pixels from every mask that --save-masks / --save-coco write, --largest-component keeps the largest of
+what is left (PackedMasks.select, csrc/mask_components.hip; with --cpu mnc_amd.components.select_numpy); without the two flags the
+output is what it was."""
 import argparse
 import os
 import time
@@ -47,6 +50,10 @@ def parse_args(argv=None):
     p.add_argument("--save-coco", dest="save_coco", default=None, metavar="FILE",
                    help="write the instances scoring >= --vis-thresh of all images as one JSON array of COCO results: "
                         "{image_id, category_id, segmentation: {size, counts}, bbox, score}, the masks run-length encoded")
+    p.add_argument("--min-component-area", dest="min_component_area", default=0, type=int, metavar="A",
+                   help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco write")
+    p.add_argument("--largest-component", dest="largest_component", action="store_true",
+                   help="keep only the largest 8-connected component of every written mask")
     return p.parse_args(argv)
 
 
@@ -158,6 +165,14 @@ def _packed_masks(im_shape, result_mask, result_box, view=None, score_thresh=0.5
     return (instance_masks_numpy if cpu else instance_masks)(bxs, mks, h, w, clip=True, classes=classes)
 
 
+def _select_components(packed, min_area, largest, cpu=False):
+    """The written masks without their components of fewer than min_area pixels and, with `largest`, without all but the largest
+    (on the GPU, csrc/mask_components.hip; cpu=True: the numpy statement).  A device-resident result is fetched first."""
+    from mnc_amd import components
+    args = (8, max(int(min_area), 1), 1 if largest else 0)
+    return components.select_numpy(packed.fetch(), *args) if cpu else packed.select(*args)
+
+
 def _coco_results(image_id, im_shape, packed, cpu=False):
     """-> COCO result entries of one image's PackedMasks: the mask run-length encoded in the image (on the GPU where the masks
     lie, csrc/mask_rle.hip; cpu=True: mnc_amd.rle's numpy statement), bbox = [x, y, w, h] of the tight box of its pixels."""
@@ -241,6 +256,8 @@ def main(argv=None):
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
             packed = _packed_masks(im.shape, result_mask, result_box, blk.view() if blk is not None else None, args.vis_thresh,
                                    args.cpu_mode)
+            if args.min_component_area > 0 or args.largest_component:
+                packed = _select_components(packed, args.min_component_area, args.largest_component, args.cpu_mode)
             if args.save_coco:                                    # (first: a device-resident result is encoded where it lies)
                 coco.extend(_coco_results(name, im.shape, packed, args.cpu_mode))
             if args.save_masks:
