@@ -104,3 +104,11 @@ def device_mem_info(device_id=0):
     fr, tot = ctypes.c_size_t(0), ctypes.c_size_t(0)
     call("mnc_device_mem_info", int(device_id), ctypes.addressof(fr), ctypes.addressof(tot))
     return fr.value, tot.value
+
+
+def timing(entry_name, on):
+    """One of the mnc_*_timing entries (boundary, polygons, accumulate, components): switch its event pair on or off -> the
+    kernels' milliseconds of the last timed call before the switch (-1.0: none)."""
+    last = ctypes.c_double(-1.0)
+    call(entry_name, int(bool(on)), ctypes.addressof(last))
+    return float(last.value)

@@ -20,9 +20,9 @@ import math
 import numpy as np
 
 from . import _lib
+from .masks import MAX_SIDE, PackedMasks, _device_id, _set_args, sized_then_filled
 
 MAX_N = 2048
-MAX_SIDE = 32768
 MAX_D = 1024
 
 
@@ -67,34 +67,23 @@ def erode_numpy(m, d):
 def boundary_numpy(pm, H, W, d):
     """The rule as a plain loop on the host -- the specification csrc/mask_boundary.hip is tested against.  -> PackedMasks.
     Raises ValueError where mnc_mask_boundary returns MNC_ERR_INVALID for H, W or d."""
-    from .masks import PackedMasks
     H, W, d = _distance("boundary_numpy", H, W, d, None)
     bounds = clipped_bounds(pm.bounds, H, W)
-    n = len(bounds)
-    offsets, areas, words, nbytes = np.zeros(n, np.int64), np.zeros(n, np.int64), [], 0
-    for i in range(n):
-        offsets[i] = nbytes
+    dense = [None] * len(bounds)
+    for i in range(len(bounds)):
         x1, y1, x2, y2 = (int(v) for v in bounds[i])
         if x2 < x1 or y2 < y1:
             continue
         ax, ay = int(pm.bounds[i][0]), int(pm.bounds[i][1])
         m = pm.dense(i)[y1 - ay:y2 - ay + 1, x1 - ax:x2 - ax + 1]
         # (the clipped box ends where the image does or where the mask's bounds do, and the mask is 0 beyond those: zeros all round)
-        b = m & ~erode_numpy(m, d)
-        h, w = b.shape
-        rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
-        rows[:, :(w + 7) // 8] = np.packbits(b, axis=1, bitorder="little")
-        areas[i] = int(b.sum())
-        words.append(rows.reshape(-1).view(np.uint64))
-        nbytes += rows.size
-    bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
-    return PackedMasks(bounds, offsets, areas, pm.classes, pm.scores, bits)
+        dense[i] = m & ~erode_numpy(m, d)
+    return PackedMasks.from_dense(bounds, dense, pm.classes, pm.scores)
 
 
 def boundary_call(pm, H, W, d, bits=None, device_id=0):
     """mnc_mask_boundary as it is: bits None asks for bounds, offsets and the size only (nothing is launched).  -> (bounds,
     offsets, areas, bytes needed)."""
-    from .masks import _set_args
     n = len(pm)
     bounds, offsets, areas = np.zeros((n, 4), np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
     need = ctypes.c_size_t(0)
@@ -108,10 +97,7 @@ def boundary(pm, H, W, d=None, ratio=0.02, device_id=None):
     """boundary_numpy on the GPU (mnc_mask_boundary, csrc/mask_boundary.hip): the same PackedMasks field by field.  d None: the
     distance of the image at `ratio`.  Invalid sets and sizes raise ValueError or _lib.MncError (MNC_ERR_INVALID) before anything
     is launched."""
-    from .masks import PackedMasks, _device_id
     H, W, d = _distance("boundary", H, W, d, ratio)
     dev = _device_id(device_id)
-    _, _, _, need = boundary_call(pm, H, W, d, None, dev)
-    bits = np.zeros(max(need // 8, 1), np.uint64)
-    bounds, offsets, areas, _ = boundary_call(pm, H, W, d, bits, dev)
-    return PackedMasks(bounds, offsets, areas, pm.classes, pm.scores, bits[:need // 8])
+    bounds, offsets, areas, bits = sized_then_filled(lambda bits: boundary_call(pm, H, W, d, bits, dev))
+    return PackedMasks(bounds, offsets, areas, pm.classes, pm.scores, bits)

@@ -37,6 +37,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .masks import PackedMasks, _device_id, _set_args, pack_rows, row_words
 
 MAX_N = 2048
 MAX_WORDS = 2 ** 25
@@ -64,14 +65,14 @@ def _check_set(who, pm, frame=0, ordered=False):
         h, w = pm.size(i)
         if h == 0 or w == 0:
             continue
-        words += (h + 2 * frame) * ((w + 2 * frame + 63) // 64)
+        words += row_words(h + 2 * frame, w + 2 * frame)
         if words > MAX_WORDS:
             raise ValueError("%s: more than %d words of rows in the set (at masks[%d])" % (who, MAX_WORDS, i))
         if ordered:
             if int(pm.offsets[i]) < end:
                 raise ValueError("%s: the rows of masks[%d] (offset %d) begin before the end of the rows before (%d)"
                                  % (who, i, int(pm.offsets[i]), end))
-            end = int(pm.offsets[i]) + h * ((w + 63) // 64) * 8
+            end = int(pm.offsets[i]) + row_words(h, w) * 8
 
 
 def _runs(m):
@@ -128,14 +129,6 @@ def label_numpy(m, connectivity=8):
     return np.cumsum(d, axis=1)[:, :w].astype(np.int32), count
 
 
-def _pack(b):
-    """bool [h, w] -> the uint64 words of its rows (n5's layout)."""
-    h, w = b.shape
-    rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
-    rows[:, :(w + 7) // 8] = np.packbits(b, axis=1, bitorder="little")
-    return rows.reshape(-1).view(np.uint64)
-
-
 def _table(m, connectivity, x1, y1):
     """One dense mask at (x1, y1) -> (area, bbox, anchor) of its components."""
     y, a, b = _runs(m)
@@ -172,14 +165,13 @@ def components_numpy(pm, connectivity=8):
 
 def _rewritten(pm, make):
     """The layout of select and fill_holes: make(dense mask) per instance with rows, written where the input's rows stand."""
-    from .masks import PackedMasks
     n = len(pm)
     bits, areas = np.zeros(pm.bits.size, np.uint64), np.zeros(n, np.int64)
     for i in range(n):
         h, w = pm.size(i)
         if h and w:
             b = make(pm.dense(i))
-            words = _pack(b)
+            words = pack_rows(b)
             lo = int(pm.offsets[i]) // 8
             bits[lo:lo + len(words)] = words
             areas[i] = int(b.sum())
@@ -223,10 +215,9 @@ def fill_holes_numpy(pm, connectivity=4):
 
 def split_numpy(pm, connectivity=8):
     """One instance per component as a plain loop on the host -> (PackedMasks, source int32 [C])."""
-    from .masks import PackedMasks
     connectivity = _check("split_numpy", connectivity)[0]
     _check_set("split_numpy", pm)
-    bounds, offsets, areas, source, words, nbytes = [], [], [], [], [], 0
+    bounds, dense, source = [], [], []
     for i in range(len(pm)):
         h, w = pm.size(i)
         if not (h and w):
@@ -237,17 +228,11 @@ def split_numpy(pm, connectivity=8):
         for c in range(1, count + 1):
             part = labels == c
             ys, xs = np.nonzero(part.any(axis=1))[0], np.nonzero(part.any(axis=0))[0]
-            part = part[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
+            dense.append(part[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1])
             bounds.append([ax + xs[0], ay + ys[0], ax + xs[-1], ay + ys[-1]])
-            offsets.append(nbytes)
-            areas.append(int(part.sum()))
             source.append(i)
-            words.append(_pack(part))
-            nbytes += words[-1].nbytes
     source = np.array(source, np.int32)
-    bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
-    return PackedMasks(np.array(bounds, np.int32).reshape(-1, 4), np.array(offsets, np.int64), np.array(areas, np.int64),
-                       pm.classes[source], pm.scores[source], bits), source
+    return PackedMasks.from_dense(np.array(bounds, np.int32).reshape(-1, 4), dense, pm.classes[source], pm.scores[source]), source
 
 
 # ---- the device ----
@@ -260,7 +245,6 @@ def _host(pm):
 def components_call(pm, connectivity, cap, device_id=0, sizes_only=False):
     """mnc_mask_components as it is, with room for `cap` components -> (Components with arrays of `cap` rows, C).  Too little room
     raises _lib.MncError (MNC_ERR_INVALID); sizes_only passes no table at all."""
-    from .masks import _set_args
     n = len(pm)
     comp_ptr = np.zeros(n + 1, np.int64)
     area, bbox, anchor = np.zeros(cap, np.int64), np.zeros((cap, 4), np.int32), np.zeros((cap, 2), np.int32)
@@ -279,7 +263,6 @@ def components(pm, connectivity=8, device_id=None):
     """components_numpy on the GPU (mnc_mask_components): the same Components field by field.  One call with room for 64 + 16 n
     components, a second one when the masks have more.  Invalid arguments raise ValueError, invalid sets _lib.MncError
     (MNC_ERR_INVALID), before anything is launched.  A device-resident PackedMasks is fetched to the host first."""
-    from .masks import _device_id
     connectivity = _check("components", connectivity)[0]
     pm = _host(pm)
     dev = _device_id(device_id)
@@ -294,7 +277,6 @@ def components(pm, connectivity=8, device_id=None):
 
 
 def _rewrite(name, pm, head, device_id):
-    from .masks import PackedMasks, _device_id, _set_args
     pm = _host(pm)
     bits, areas = np.zeros(max(pm.bits.size, 1), np.uint64), np.zeros(len(pm), np.int64)
     _lib.call(name, *(_set_args(pm, areas=False) + head + (_lib.ptr(areas), _lib.ptr(bits), int(pm.bits.nbytes), _device_id(device_id))))
@@ -315,7 +297,6 @@ def fill_holes(pm, connectivity=4, device_id=None):
 def split_call(pm, connectivity, cap, bits, device_id=0):
     """mnc_mask_split as it is, with room for `cap` components and the words `bits` (None: the sizes only) -> (bounds, offsets,
     areas, source, C, bytes).  Too little room raises _lib.MncError (MNC_ERR_INVALID) with .needed = (C, bytes)."""
-    from .masks import _set_args
     bounds, offsets = np.zeros((cap, 4), np.int32), np.zeros(cap, np.int64)
     areas, source = np.zeros(cap, np.int64), np.zeros(cap, np.int32)
     count, nbytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
@@ -333,7 +314,6 @@ def split(pm, connectivity=8, device_id=None):
     """split_numpy on the GPU (mnc_mask_split): the same (PackedMasks, source) field by field.  One call with room for 64 + 16 n
     components and twice the input's words, a second one when the result is larger.  Invalid arguments raise ValueError, invalid sets
     _lib.MncError (MNC_ERR_INVALID), before anything is launched.  A device-resident PackedMasks is fetched to the host first."""
-    from .masks import PackedMasks, _device_id
     connectivity = _check("split", connectivity)[0]
     pm = _host(pm)
     dev = _device_id(device_id)
@@ -353,6 +333,4 @@ def split(pm, connectivity=8, device_id=None):
 
 def timing(on):
     """mnc_mask_components_timing: switch the event pair on or off -> the kernels' milliseconds of the last timed call (-1.0: none)."""
-    last = ctypes.c_double(-1.0)
-    _lib.call("mnc_mask_components_timing", int(bool(on)), ctypes.addressof(last))
-    return float(last.value)
+    return _lib.timing("mnc_mask_components_timing", on)

@@ -384,23 +384,7 @@ __global__ __launch_bounds__(kAccumThreads) void accum_cells_kernel(const unsign
 namespace {
 
 // mnc_coco_accum_timing: a HIP event pair around the launches of the next calls (tools/coco_accum_bench.py)
-std::atomic<int> g_accum_timing{0};
-std::atomic<double> g_accum_last_ms{-1.0};
-
-struct AccumSpan {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  ~AccumSpan() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void begin(hipStream_t s) {
-    on = g_accum_timing.load() != 0 && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-    if (on) (void)hipEventRecord(a, s);
-  }
-  void end(hipStream_t s) { if (on) (void)hipEventRecord(b, s); }
-  double ms() const {                                   // after the stream was synchronised
-    float t = 0.f;
-    return on && hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0;
-  }
-};
+CallTimer g_accum_timer;
 
 }  // namespace
 
@@ -503,7 +487,7 @@ int mnc_coco_accumulate(const int* dt_class_idx, const float* dt_score, const in
   MNC_HIP_TRY(hs.up(d_gcls, gt_class_idx, (size_t)Gn * 4));
   MNC_HIP_TRY(hs.up(d_gig, gt_ignore, ngig));
   MNC_HIP_TRY(hs.up(d_thrs, rec_thrs, (size_t)R * 8));
-  AccumSpan span;
+  TimedSpan span(g_accum_timer);
   span.begin(s);
   MNC_HIP_TRY(hipMemsetAsync(d_npig, 0, (size_t)K * A * 8, s));
   const dim3 block(kAccumThreads);
@@ -528,16 +512,10 @@ int mnc_coco_accumulate(const int* dt_class_idx, const float* dt_score, const in
   MNC_HIP_TRY(hs.down(recall, d_rec, nrec * 8));
   if (npig) MNC_HIP_TRY(hs.down(npig, d_npig, (size_t)K * A * 8));
   MNC_HIP_TRY(hs.sync());
-  if (span.on) g_accum_last_ms.store(span.ms());
+  span.keep();
   clear_error();
   return MNC_OK;
 }
 
 // see include/mnc_hip.h
-int mnc_coco_accum_timing(int on, double* last_ms) {
-  if (last_ms) *last_ms = g_accum_last_ms.load();
-  g_accum_timing.store(on ? 1 : 0);
-  if (on) g_accum_last_ms.store(-1.0);
-  clear_error();
-  return MNC_OK;
-}
+int mnc_coco_accum_timing(int on, double* last_ms) { return g_accum_timer.set(on, last_ms); }

@@ -70,6 +70,14 @@ int CallBuf::alloc(const char* who, size_t bytes) {
   return MNC_ERR_NOMEM;
 }
 
+int CallTimer::set(int enable, double* out_last_ms) {
+  if (out_last_ms) *out_last_ms = last_ms.load();
+  on.store(enable ? 1 : 0);
+  if (enable) last_ms.store(-1.0);
+  clear_error();
+  return MNC_OK;
+}
+
 static hipEvent_t take_event(mnc_ctx* ctx) {
   if (!ctx->event_pool.empty()) {
     hipEvent_t e = ctx->event_pool.back();

@@ -222,29 +222,8 @@ int boundary_check_image(const char* who, int H, int W, int d) {
   return MNC_OK;
 }
 
-namespace {
-
 // mnc_mask_boundary_timing: a HIP event pair around the launches of the next calls, the last call's time kept
-std::atomic<int> g_bd_timing{0};
-std::atomic<double> g_bd_last_ms{-1.0};
-
-}  // namespace
-
-BdSpan::~BdSpan() {
-  if (a) (void)hipEventDestroy(a);
-  if (b) (void)hipEventDestroy(b);
-}
-void BdSpan::begin(hipStream_t s) {
-  on = g_bd_timing.load() != 0 && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-  if (on) (void)hipEventRecord(a, s);
-}
-void BdSpan::end(hipStream_t s) {
-  if (on) (void)hipEventRecord(b, s);
-}
-void BdSpan::keep() {
-  float t = 0.f;
-  if (on && hipEventElapsedTime(&t, a, b) == hipSuccess) g_bd_last_ms.store((double)t);
-}
+CallTimer g_bd_timer;
 
 }  // namespace mnc
 
@@ -294,7 +273,7 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
   layout(WsLayout(hs.buf));
   MNC_HIP_TRY(set.upload(hs));
   MNC_HIP_TRY(hs.up(d_out, out.data(), (size_t)n * sizeof(mnc_mask_info)));
-  BdSpan span;
+  TimedSpan span(g_bd_timer);
   span.begin(hs.stream);
   boundary_launch(hs.stream, set.view(), H, W, d, plan, d_out, d_obits, d_scratch);
   span.end(hs.stream);
@@ -309,10 +288,4 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
 }
 
 // see include/mnc_hip.h
-int mnc_mask_boundary_timing(int on, double* last_ms) {
-  if (last_ms) *last_ms = g_bd_last_ms.load();
-  g_bd_timing.store(on ? 1 : 0);
-  if (on) g_bd_last_ms.store(-1.0);
-  clear_error();
-  return MNC_OK;
-}
+int mnc_mask_boundary_timing(int on, double* last_ms) { return g_bd_timer.set(on, last_ms); }

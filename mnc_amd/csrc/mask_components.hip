@@ -425,27 +425,8 @@ namespace {
 // mutex, which the call holds to its end.
 DevArena g_cc_runs[16], g_cc_comps[16];
 
-std::atomic<int> g_cc_timing{0};
-std::atomic<double> g_cc_last_ms{-1.0};
-
-// mnc_mask_components_timing's event pair around the launches of one call; keep() after the stream was synchronised.
-struct CcSpan {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  ~CcSpan() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void begin(hipStream_t s) {
-    if (!g_cc_timing.load()) return;
-    on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, s) == hipSuccess;
-  }
-  void end(hipStream_t s) { if (on) on = hipEventRecord(b, s) == hipSuccess; }
-  void keep() {
-    float ms = 0.f;
-    if (on && hipEventElapsedTime(&ms, a, b) == hipSuccess) g_cc_last_ms.store((double)ms);
-  }
-};
+// mnc_mask_components_timing: a HIP event pair around the launches of the next calls, the last call's time kept
+CallTimer g_cc_timer;
 
 inline int cc_blocks(long long items) { return (int)((items + kCcThreads - 1) / kCcThreads); }
 inline int cc_tiles(long long items) { return (int)((items + kCcTile - 1) / kCcTile); }
@@ -620,7 +601,7 @@ int cc_rewrite(CcJob& job, const int* bounds, const long long* offsets, const vo
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  CcSpan span;
+  TimedSpan span(g_cc_timer);
   span.begin(hs.stream);
   rc = job.label(hs, !fill);
   if (rc) return rc;
@@ -677,7 +658,7 @@ int mnc_mask_components(const int* bounds, const long long* offsets, const void*
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  CcSpan span;
+  TimedSpan span(g_cc_timer);
   span.begin(hs.stream);
   rc = job.label(hs, true);
   if (rc) return rc;
@@ -741,7 +722,7 @@ int mnc_mask_split(const int* bounds, const long long* offsets, const void* bits
   rc = hs.open(device_id, layout(WsLayout()));
   if (rc) return rc;
   layout(WsLayout(hs.buf));
-  CcSpan span;
+  TimedSpan span(g_cc_timer);
   span.begin(hs.stream);
   rc = job.label(hs, true);
   if (rc) return rc;
@@ -792,10 +773,4 @@ int mnc_mask_split(const int* bounds, const long long* offsets, const void* bits
 }
 
 // see include/mnc_hip.h
-int mnc_mask_components_timing(int on, double* last_ms) {
-  if (last_ms) *last_ms = g_cc_last_ms.load();
-  g_cc_timing.store(on ? 1 : 0);
-  if (on) g_cc_last_ms.store(-1.0);
-  clear_error();
-  return MNC_OK;
-}
+int mnc_mask_components_timing(int on, double* last_ms) { return g_cc_timer.set(on, last_ms); }

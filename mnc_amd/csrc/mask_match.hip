@@ -467,7 +467,7 @@ int mt_host(const char* who, const int* dt_bounds, const long long* dt_offsets, 
   if (rc) return rc;
   layout(WsLayout(hs.buf));
   MNC_HIP_TRY(dt.upload(hs));
-  BdSpan span;                                           // (never begun without the boundary part)
+  TimedSpan span(g_bd_timer);                            // (never begun without the boundary part)
   if (bd) {
     if (!bd->biou_out) bd->biou = nullptr;
     MNC_HIP_TRY(hs.up(bd->dinfo, dbinfo.data(), (size_t)nd * sizeof(mnc_mask_info)));

@@ -242,23 +242,7 @@ __global__ __launch_bounds__(kPolyThreads) void poly_write_kernel(const mnc_mask
 namespace {
 
 // mnc_mask_poly_timing: a HIP event pair around each group of launches of the next calls, their sum kept (tools/mask_poly_bench.py)
-std::atomic<int> g_poly_timing{0};
-std::atomic<double> g_poly_last_ms{-1.0};
-
-struct PolySpan {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  ~PolySpan() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void begin(hipStream_t s) {
-    on = g_poly_timing.load() != 0 && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-    if (on) (void)hipEventRecord(a, s);
-  }
-  void end(hipStream_t s) { if (on) (void)hipEventRecord(b, s); }
-  double ms() const {                                   // after the stream was synchronised
-    float t = 0.f;
-    return on && hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0;
-  }
-};
+CallTimer g_poly_timer;
 
 inline int floordiv5(int a) { return a >= 0 ? a / 5 : -((4 - a) / 5); }
 inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
@@ -387,7 +371,7 @@ int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const lo
   MNC_HIP_TRY(hs.up(d_edges, edges.data(), edges.size() * sizeof(PolyEdge)));
   MNC_HIP_TRY(hs.up(d_planes, planes.data(), planes.size() * sizeof(PolyPlane)));
   MNC_HIP_TRY(hs.up(d_anns, anns.data(), (size_t)n * sizeof(PolyAnn)));
-  PolySpan rasterise, write;
+  TimedSpan rasterise(g_poly_timer), write(g_poly_timer);
   rasterise.begin(hs.stream);
   MNC_HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), hs.stream));
   if (words) MNC_HIP_TRY(hipMemsetAsync(d_ws, 0, (size_t)words * 8, hs.stream));
@@ -402,7 +386,7 @@ int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const lo
   MNC_HIP_TRY(hs.down(boxes.data(), d_boxes, (size_t)n * sizeof(PolyBox)));
   MNC_HIP_TRY(hs.down(&flag, d_flag, sizeof(int)));
   MNC_HIP_TRY(hs.sync());
-  if (rasterise.on) g_poly_last_ms.store(rasterise.ms());
+  rasterise.keep();                    // what a sizes-only call leaves
   if (flag) {
     set_error("mnc_mask_from_polygons: a crossing fell outside the rectangle the host made for its polygon (a bug)");
     return MNC_ERR_STATE;
@@ -439,17 +423,11 @@ int mnc_mask_from_polygons(const double* xy, const long long* vert_ptr, const lo
     MNC_HIP_TRY(hipGetLastError());
     MNC_HIP_TRY(hs.down(bits, d_bits, need));
     MNC_HIP_TRY(hs.sync());
-    if (write.on) g_poly_last_ms.store(rasterise.ms() + write.ms());
+    write.keep_sum(rasterise);
   }
   clear_error();
   return MNC_OK;
 }
 
 // see include/mnc_hip.h
-int mnc_mask_poly_timing(int on, double* last_ms) {
-  if (last_ms) *last_ms = g_poly_last_ms.load();
-  g_poly_timing.store(on ? 1 : 0);
-  if (on) g_poly_last_ms.store(-1.0);
-  clear_error();
-  return MNC_OK;
-}
+int mnc_mask_poly_timing(int on, double* last_ms) { return g_poly_timer.set(on, last_ms); }

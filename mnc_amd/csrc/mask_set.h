@@ -104,15 +104,8 @@ void boundary_plan(const std::vector<mnc_mask_info>& in, int H, int W, int d, st
 void boundary_launch(hipStream_t s, const MaskSet& in, int H, int W, int d, const BdPlan& plan, mnc_mask_info* d_out_info,
                      u64* d_out_bits, u64* d_scratch);
 int boundary_check_image(const char* who, int H, int W, int d);   // MNC_ERR_INVALID: H or W outside [1, 32768], d outside [1, 1024]
-// mnc_mask_boundary_timing's event pair around the launches of one call; keep() after the stream was synchronised.  A span that
-// was never begun records and keeps nothing.
-struct BdSpan {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  ~BdSpan();
-  void begin(hipStream_t s);
-  void end(hipStream_t s);
-  void keep();
-};
+// mnc_mask_boundary_timing's timer (mask_boundary.hip): mnc_mask_boundary and the boundary part of mnc_mask_match_boundary keep
+// the time of their launches in it
+extern CallTimer g_bd_timer;
 
 }  // namespace mnc

@@ -248,6 +248,49 @@ struct HostScope {
   hipError_t sync() const { return hipStreamSynchronize(stream); }
 };
 
+// The switch and the kept figure behind one mnc_*_timing entry (boundary, polygons, accumulate, components): off and -1.0 until
+// the entry is called.
+struct CallTimer {
+  std::atomic<int> on{0};
+  std::atomic<double> last_ms{-1.0};
+  int set(int enable, double* out_last_ms);   // ctx.hip: the whole of an mnc_*_timing entry
+};
+
+// A HIP event pair around one group of launches of a call, for its timer.  The events exist only while the timer is on; with it off
+// begin() is one relaxed load and end() / keep() one bool test.  A span that was never begun, or one of whose event calls failed,
+// keeps nothing.
+struct TimedSpan {
+  CallTimer& timer;
+  hipEvent_t a = nullptr, b = nullptr;
+  bool on = false;
+  explicit TimedSpan(CallTimer& t) : timer(t) {}
+  TimedSpan(const TimedSpan&) = delete;
+  ~TimedSpan() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void begin(hipStream_t s) {
+    if (!timer.on.load(std::memory_order_relaxed)) return;
+    on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, s) == hipSuccess;
+  }
+  void end(hipStream_t s) { if (on) on = hipEventRecord(b, s) == hipSuccess; }
+  // All three after the stream was synchronised.  ms() is not const: a failed hipEventElapsedTime switches the span off.
+  double ms() {
+    float t = 0.f;
+    if (on) on = hipEventElapsedTime(&t, a, b) == hipSuccess;
+    return on ? (double)t : 0.0;
+  }
+  void keep() {
+    const double t = ms();
+    if (on) timer.last_ms.store(t);
+  }
+  // the sum of an earlier span of the same call and this one; nothing when either is off or failed
+  void keep_sum(TimedSpan& earlier) {
+    const double t = earlier.ms() + ms();
+    if (on && earlier.on) timer.last_ms.store(t);
+  }
+};
+
 // launchers shared between translation units (all asynchronous on `stream`, pointers are device pointers)
 int nms_mask_launch(hipStream_t stream, const float* d_boxes, const int* d_order, int n, int dim, float thr,
                     unsigned long long* d_mask, int batch);

@@ -37,6 +37,46 @@ MAX_AREA = 2 ** 26
 MAX_SIDE = 32768
 
 
+def row_words(h, w):
+    """The uint64 words of one instance of h rows and w columns; 0 when either side is 0."""
+    return h * ((w + 63) // 64) if h and w else 0
+
+
+def pack_rows(m):
+    """bool [h, w] -> the uint64 words of its rows: the bit layout above, padding bits 0."""
+    h, w = m.shape
+    rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
+    rows[:, :(w + 7) // 8] = np.packbits(m, axis=1, bitorder="little")
+    return rows.reshape(-1).view(np.uint64)
+
+
+def merge_sets(parts, order):
+    """Host PackedMasks `parts` and for every output row the (part, row) it comes from -> (bounds, offsets, areas, bits) of one set
+    in that order: the offsets repacked without gaps, the bits copied.  The one gather: PackedMasks.take is it over one set."""
+    words, at = [], 0
+    bounds, offsets, areas = np.zeros((len(order), 4), np.int32), np.zeros(len(order), np.int64), np.zeros(len(order), np.int64)
+    for k, (p, i) in enumerate(order):
+        pm = parts[p]
+        count = row_words(*pm.size(i))
+        lo = int(pm.offsets[i]) // 8
+        words.append(pm.bits[lo:lo + count])
+        bounds[k], offsets[k], areas[k] = pm.bounds[i], at, pm.areas[i]
+        at += count * 8
+    return bounds, offsets, areas, (np.concatenate(words) if words else np.zeros(0, np.uint64))
+
+
+def sized_then_filled(call):
+    """The two calls of an entry point that reports the bytes of its bits: call(None) for the size, then call(bits) with room.
+    call(bits_or_None) -> (bounds, offsets, areas, need); -> (bounds, offsets, areas, bits) with bits.size == need // 8.  A result
+    of zero bytes makes the second call with a one-word buffer that is not returned: every entry point takes a non-null pointer
+    as "the call with room" and none writes past `need`, whereas null would ask for the sizes again and an empty array's address
+    is whatever numpy makes it."""
+    need = call(None)[3]
+    bits = np.zeros(need // 8, np.uint64)
+    bounds, offsets, areas, _ = call(bits if bits.size else np.zeros(1, np.uint64))
+    return bounds, offsets, areas, bits
+
+
 class PackedMasks(object):
     """The packed masks of one image.  Made from host arrays, or from a device result whose arrays are copied on first access
     (the instance table in one copy, the bits in a second) and kept; a device result that was never read refuses a later image's."""
@@ -79,9 +119,8 @@ class PackedMasks(object):
         h, w = self.size(i)
         if h == 0 or w == 0:
             return np.zeros((h, 0), np.uint8), w
-        strips = (w + 63) // 64
         lo = int(self.offsets[i]) // 8
-        return self.bits[lo:lo + h * strips].view(np.uint8).reshape(h, strips * 8), w
+        return self.bits[lo:lo + row_words(h, w)].view(np.uint8).reshape(h, row_words(1, w) * 8), w
 
     def dense(self, i):
         """bool [h, w]: the mask of instance i inside its bounds."""
@@ -226,19 +265,27 @@ class PackedMasks(object):
         from . import polygons
         return polygons.masks_from_segmentations(segs, H, W, classes, scores)
 
+    @classmethod
+    def from_dense(cls, bounds, dense, classes=None, scores=None):
+        """Per-instance bool [h, w] arrays (None, or one with a zero side: no rows) -> a host PackedMasks: offsets in order without
+        gaps, areas the true counts, the given bounds [n, 4] stored as they are."""
+        n = len(dense)
+        offsets, areas, words, nbytes = np.zeros(n, np.int64), np.zeros(n, np.int64), [], 0
+        for i, m in enumerate(dense):
+            offsets[i] = nbytes
+            if m is None or 0 in np.shape(m):
+                continue
+            m = np.asarray(m, bool)
+            areas[i] = int(m.sum())
+            words.append(pack_rows(m))
+            nbytes += words[-1].nbytes
+        return cls(bounds, offsets, areas, classes, scores, np.concatenate(words) if words else np.zeros(0, np.uint64))
+
     def take(self, indices):
         """-> a host PackedMasks of these instances, in this order: offsets repacked without gaps, the bits copied."""
         idx = np.asarray(indices, np.int64).reshape(-1)
-        words, offsets, at = [], np.zeros(len(idx), np.int64), 0
-        for k, i in enumerate(idx):
-            h, w = self.size(i)
-            count = h * ((w + 63) // 64) if h and w else 0
-            lo = int(self.offsets[i]) // 8
-            words.append(self.bits[lo:lo + count])
-            offsets[k] = at
-            at += count * 8
-        bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
-        return PackedMasks(self.bounds[idx], offsets, self.areas[idx], self.classes[idx], self.scores[idx], bits)
+        bounds, offsets, areas, bits = merge_sets((self,), [(0, i) for i in idx])
+        return PackedMasks(bounds, offsets, areas, self.classes[idx], self.scores[idx], bits)
 
     def arrays(self):
         """{name: array} of the six fields (what tools/demo.py --save-masks writes with np.savez)."""
@@ -294,8 +341,7 @@ def instance_masks_numpy(boxes, masks, im_h, im_w, clip=True, binarize_thresh=No
         raise ValueError("instance_masks_numpy: mask_size %d not in [1, %d]" % (S, MAX_MASK))
     if clip and not (1 <= im_h <= MAX_SIDE and 1 <= im_w <= MAX_SIDE):
         raise ValueError("instance_masks_numpy: image %d x %d not in [1, %d]" % (im_h, im_w, MAX_SIDE))
-    bounds = np.zeros((n, 4), np.int32)
-    offsets, areas, words, nbytes = np.zeros(n, np.int64), np.zeros(n, np.int64), [], 0
+    bounds, dense = np.zeros((n, 4), np.int32), []
     for i in range(n):
         r = np.round(boxes[i, :4])
         if not (np.abs(r) < MAX_COORD).all():
@@ -309,14 +355,9 @@ def instance_masks_numpy(boxes, masks, im_h, im_w, clip=True, binarize_thresh=No
             raise ValueError("instance_masks_numpy: box %d %s is empty once rounded (cv2.resize would raise)" % (i, boxes[i, :4]))
         if w * h > MAX_AREA:
             raise ValueError("instance_masks_numpy: box %d covers %d pixels (limit %d)" % (i, w * h, MAX_AREA))
-        m = resize_to(masks[i].reshape(S, S), w, h) >= thr
-        rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
-        rows[:, :(w + 7) // 8] = np.packbits(m, axis=1, bitorder="little")
-        bounds[i], offsets[i], areas[i] = b, nbytes, int(m.sum())
-        words.append(rows.reshape(-1).view(np.uint64))
-        nbytes += rows.size
-    bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
-    return PackedMasks(bounds, offsets, areas, classes, _scores_of(boxes, scores), bits)
+        bounds[i] = b
+        dense.append(resize_to(masks[i].reshape(S, S), w, h) >= thr)
+    return PackedMasks.from_dense(bounds, dense, classes, _scores_of(boxes, scores))
 
 
 def instance_masks_call(boxes, masks, n, S, im_h, im_w, clip, binarize_thresh, bits=None, device_id=0):
@@ -335,14 +376,12 @@ def instance_masks(boxes, masks, im_h, im_w, clip=True, binarize_thresh=None, cl
     Invalid boxes and sizes raise _lib.MncError (MNC_ERR_INVALID) before anything is launched."""
     from mnc_config import cfg
     thr = cfg.BINARIZE_THRESH if binarize_thresh is None else binarize_thresh
-    if device_id is None:
-        device_id = int(cfg.get("GPU_ID", 0))
+    device_id = _device_id(device_id)
     boxes, masks, n, S = _flat(boxes, masks)
     b4 = np.ascontiguousarray(boxes[:, :4])
     S = S if n else int(cfg.MASK_SIZE)
-    _, _, _, need = instance_masks_call(b4, masks, n, S, im_h, im_w, clip, thr, None, device_id)
-    bits = np.zeros(need // 8, np.uint64)
-    bounds, offsets, areas, _ = instance_masks_call(b4, masks, n, S, im_h, im_w, clip, thr, bits, device_id)
+    bounds, offsets, areas, bits = sized_then_filled(
+        lambda bits: instance_masks_call(b4, masks, n, S, im_h, im_w, clip, thr, bits, device_id))
     return PackedMasks(bounds, offsets, areas, classes, _scores_of(boxes, scores), bits)
 
 

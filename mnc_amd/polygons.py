@@ -20,7 +20,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .masks import PackedMasks, _device_id
+from .masks import PackedMasks, _device_id, merge_sets, sized_then_filled  # noqa: F401 (merge_sets: its public name here)
 from .rle import MAX_MASKS, _check_image, counts_of_rles, masks_from_counts, masks_from_counts_numpy
 
 MAX_COORD = 2.0 ** 20
@@ -183,30 +183,13 @@ def masks_from_polygons(segs, H, W, classes=None, scores=None, device_id=None):
     segs, H, W = _check_segs("masks_from_polygons", segs, H, W)
     device_id = _device_id(device_id)
     xy, vert_ptr, poly_ptr = _flatten(segs)
-    _, _, _, need = masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W, None, device_id)
-    bits = np.zeros(need // 8, np.uint64)
-    bounds, offsets, areas, _ = masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W, bits if need else None, device_id)
+    bounds, offsets, areas, bits = sized_then_filled(
+        lambda bits: masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W, bits, device_id))
     return PackedMasks(bounds, offsets, areas, classes, scores, bits)
 
 
 def _is_rle(seg):
     return isinstance(seg, dict) and "counts" in seg and "size" in seg
-
-
-def merge_sets(parts, order):
-    """Host PackedMasks `parts` and for every output row the (part, row) it comes from -> one host PackedMasks in that order: the
-    offsets repacked without gaps, the bits copied (PackedMasks.take's packing across sets)."""
-    words, at = [], 0
-    bounds, offsets, areas = np.zeros((len(order), 4), np.int32), np.zeros(len(order), np.int64), np.zeros(len(order), np.int64)
-    for k, (p, i) in enumerate(order):
-        pm = parts[p]
-        h, w = pm.size(i)
-        count = h * ((w + 63) // 64) if h and w else 0
-        lo = int(pm.offsets[i]) // 8
-        words.append(pm.bits[lo:lo + count])
-        bounds[k], offsets[k], areas[k] = pm.bounds[i], at, pm.areas[i]
-        at += count * 8
-    return bounds, offsets, areas, (np.concatenate(words) if words else np.zeros(0, np.uint64))
 
 
 def masks_from_segmentations(segs, H, W, classes=None, scores=None, device_id=None, cpu=False):

@@ -18,7 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .masks import MAX_SIDE, PackedMasks, _device_id, _set_args
+from .masks import MAX_SIDE, PackedMasks, _device_id, _set_args, sized_then_filled
 
 MAX_MASKS = 2048
 FIRST_RUNS = 1 << 16            # room of the first mnc_mask_rle_dev of a device-resident result; one retry at the true total
@@ -62,27 +62,20 @@ def masks_from_counts_numpy(run_ptr, runs, H, W, classes=None, scores=None):
     Raises ValueError where mnc_mask_from_rle returns MNC_ERR_INVALID."""
     H, W = int(H), int(W)
     run_ptr, runs, n = _check_counts("masks_from_counts_numpy", run_ptr, runs, H, W)
-    bounds = np.zeros((n, 4), np.int32)
-    offsets, areas, words, nbytes = np.zeros(n, np.int64), np.zeros(n, np.int64), [], 0
+    bounds, dense = np.zeros((n, 4), np.int32), [None] * n
     for i in range(n):
         c = runs[run_ptr[i]:run_ptr[i + 1]].astype(np.int64)
         if c.sum() != H * W:
             raise ValueError("masks_from_counts_numpy: the counts of mask %d sum to %d, not %d x %d" % (i, c.sum(), H, W))
         m = np.repeat(np.arange(len(c)) & 1, c).astype(bool).reshape(W, H).T
-        offsets[i], areas[i] = nbytes, int(m.sum())
-        if not areas[i]:
+        if not m.any():
             bounds[i] = (0, 0, -1, -1)
             continue
         xs, ys = np.flatnonzero(m.any(axis=0)), np.flatnonzero(m.any(axis=1))
         x1, y1, x2, y2 = int(xs[0]), int(ys[0]), int(xs[-1]), int(ys[-1])
-        w, h = x2 - x1 + 1, y2 - y1 + 1
-        rows = np.zeros((h, (w + 63) // 64 * 8), np.uint8)
-        rows[:, :(w + 7) // 8] = np.packbits(m[y1:y2 + 1, x1:x2 + 1], axis=1, bitorder="little")
         bounds[i] = (x1, y1, x2, y2)
-        words.append(rows.reshape(-1).view(np.uint64))
-        nbytes += rows.size
-    bits = np.concatenate(words) if words else np.zeros(0, np.uint64)
-    return PackedMasks(bounds, offsets, areas, classes, scores, bits)
+        dense[i] = m[y1:y2 + 1, x1:x2 + 1]
+    return PackedMasks.from_dense(bounds, dense, classes, scores)
 
 
 def _chars(counts):
@@ -194,9 +187,7 @@ def masks_from_counts(run_ptr, runs, H, W, classes=None, scores=None, device_id=
     runs = np.ascontiguousarray(runs, np.uint32).reshape(-1)
     if len(run_ptr) < 1 or (len(run_ptr) > 1 and run_ptr.max() > len(runs)):
         raise ValueError("masks_from_counts: run_ptr is empty or reaches past the runs")
-    _, _, _, need = masks_from_counts_call(run_ptr, runs, H, W, None, device_id)
-    bits = np.zeros(need // 8, np.uint64)
-    bounds, offsets, areas, _ = masks_from_counts_call(run_ptr, runs, H, W, bits if need else None, device_id)
+    bounds, offsets, areas, bits = sized_then_filled(lambda bits: masks_from_counts_call(run_ptr, runs, H, W, bits, device_id))
     return PackedMasks(bounds, offsets, areas, classes, scores, bits)
 
 

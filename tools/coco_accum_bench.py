@@ -15,13 +15,11 @@ one JSON line.
     python tools/coco_accum_bench.py [--images 5000] [--dets 100] [--host-images 200] [--iters 5]
 """
 import argparse
-import ctypes
-import json
 import time
 
 import numpy as np
 
-import _init_paths  # noqa: F401
+from _task_harness import emit, kernels_us, median_ms
 
 CLASSES = 80
 GTS = 7
@@ -44,27 +42,6 @@ def records(n_images, dets, seed=0):
     return images
 
 
-def _times_ms(fn, rounds):
-    times = []
-    for _ in range(max(rounds, 1)):
-        t0 = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return round(sorted(times)[len(times) // 2], 3), round(min(times), 3)
-
-
-def _kernels_ms(fn, rounds):
-    from mnc_amd import _lib
-    times, last = [], ctypes.c_double(-1.0)
-    for _ in range(max(rounds, 1)):
-        _lib.call("mnc_coco_accum_timing", 1, None)
-        fn()
-        _lib.call("mnc_coco_accum_timing", 0, ctypes.addressof(last))
-        if last.value >= 0:
-            times.append(last.value)
-    return round(sorted(times)[len(times) // 2], 3) if times else None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=5000)
@@ -83,18 +60,18 @@ def main():
     same = bool(np.array_equal(got["precision"], want["precision"]) and np.array_equal(got["recall"], want["recall"]))
     coco_eval.accumulate_device(images, classes=classes)                      # (the workspace grows to the full size)
     uniq = np.asarray(classes, np.int64)
-    flatten = _times_ms(lambda: coco_eval.flatten_records(images, uniq, coco_eval.MAX_DETS), args.iters)
-    device = _times_ms(lambda: coco_eval.accumulate_device(images, classes=classes), args.iters)
-    kernels = _kernels_ms(lambda: coco_eval.accumulate_device(images, classes=classes), args.iters)
+    flatten = median_ms(lambda: coco_eval.flatten_records(images, uniq, coco_eval.MAX_DETS), args.iters)
+    device = median_ms(lambda: coco_eval.accumulate_device(images, classes=classes), args.iters)
+    kernels = kernels_us("mnc_coco_accum_timing", lambda: coco_eval.accumulate_device(images, classes=classes), args.iters)
     scale = len(images) / float(len(part))
-    print(json.dumps({"workload": "COCO accumulate: per-image match tables -> precision [T, R, K, A, M] and recall [T, K, A, M]",
-                      "images": len(images), "detections": len(images) * args.dets, "ground_truths": len(images) * GTS,
-                      "classes": CLASSES, "T": 10, "A": 4, "M": 3, "R": 101,
-                      "host": "accumulate", "host_images": len(part), "host_ms": round(host_ms, 1), "host_scaled": len(part) != len(images),
-                      "host_ms_scaled": round(host_ms * scale, 1),
-                      "device": "accumulate_device: flatten_records on the host, one mnc_coco_accumulate call, host arrays in and out",
-                      "device_rounds": max(args.iters, 1), "device_equals_host": same, "flatten_ms_median": flatten[0],
-                      "device_ms_median": device[0], "device_ms_min": device[1], "kernels_ms_median": kernels}))
+    emit({"workload": "COCO accumulate: per-image match tables -> precision [T, R, K, A, M] and recall [T, K, A, M]",
+          "images": len(images), "detections": len(images) * args.dets, "ground_truths": len(images) * GTS,
+          "classes": CLASSES, "T": 10, "A": 4, "M": 3, "R": 101,
+          "host": "accumulate", "host_images": len(part), "host_ms": round(host_ms, 1), "host_scaled": len(part) != len(images),
+          "host_ms_scaled": round(host_ms * scale, 1),
+          "device": "accumulate_device: flatten_records on the host, one mnc_coco_accumulate call, host arrays in and out",
+          "device_rounds": max(args.iters, 1), "device_equals_host": same, "flatten_ms_median": flatten[0],
+          "device_ms_median": device[0], "device_ms_min": device[1], "kernels_ms_median": None if kernels is None else round(kernels / 1e3, 3)})
 
 
 if __name__ == "__main__":

@@ -13,18 +13,12 @@ a heading, to --profile (default profiles/mask_boundary_bench.txt; "" writes not
 
     python tools/mask_boundary_bench.py [--iters 20] [--host-iters 3] [--keep 100] [--gts 20] [--profile FILE]
 """
-import argparse
-import ctypes
-import json
 import os
-import sys
-import tempfile
-import time
 
 import numpy as np
 
-import _init_paths  # noqa: F401
-from mnc_amd import models, synth
+from _task_harness import emit, kernels_us, median_ms, parser, voted_instances
+
 
 HEADING = """tools/mask_boundary_bench.py --iters %d --host-iters %d on one MI355X: per image, mnc_amd.boundary.boundary_numpy of the %d
 best instances against PackedMasks.boundary (mnc_mask_boundary, csrc/mask_boundary.hip: host arrays in and out, the sizes-only call
@@ -36,103 +30,46 @@ call's launches between a HIP event pair (mnc_mask_boundary_timing).  Host and d
 """
 
 
-def _median_ms(fn, rounds):
-    times = []
-    for _ in range(max(rounds, 1)):
-        t0 = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return round(sorted(times)[len(times) // 2], 3), round(min(times), 3)
-
-
-def _kernels_us(fn, rounds):
-    """Median device time of the launches of one fn() -- a single call of one of the two entries -- in microseconds."""
-    from mnc_amd import _lib
-    times, last = [], ctypes.c_double(-1.0)
-    for _ in range(max(rounds, 1)):
-        _lib.call("mnc_mask_boundary_timing", 1, None)
-        fn()
-        _lib.call("mnc_mask_boundary_timing", 0, ctypes.addressof(last))
-        if last.value >= 0:
-            times.append(last.value * 1e3)
-    return round(sorted(times)[len(times) // 2], 2) if times else None
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--host-iters", type=int, default=3)
-    ap.add_argument("--keep", type=int, default=100)
+    ap = parser()
     ap.add_argument("--gts", type=int, default=20)
     ap.add_argument("--profile", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "mask_boundary_bench.txt"))
-    ap.add_argument("--math", default=os.environ.get("MNC_MATH", "fp32"))
     args = ap.parse_args()
-    os.environ["MNC_MATH"] = args.math
-    from caffeWrapper.TesterWrapper import TesterWrapper
-    from mnc_config import cfg
     from mnc_amd import boundary
     from mnc_amd.coco_eval import match_boundary_numpy
     from mnc_amd.masks import PackedMasks
-    from transform.mask_transform import gpu_mask_voting
-    from utils.image_io import imread
-    cfg.TEST.DEVICE_PREP = True
-    with tempfile.TemporaryDirectory() as root:
-        cfg.ROOT_DIR = root
-        image_path = os.path.join(root, "im0.npy")
-
-        class Imdb(object):
-            name, image_index, _image_index, num_classes = "mask_boundary_bench", ["im0"], ["im0"], 21
-
-            def image_path_at(self, i):
-                return image_path
-
-        path = models.write_mnc_5stage_test_prototxt()
-        t0 = time.time()
-        t = TesterWrapper(path, Imdb(), synth.synthetic_weights(path, seed=0), "seg")
-        print("net ready in %.1f s" % (time.time() - t0), file=sys.stderr)
-        sizes = []
-        for H, W in ((600, 1000), (375, 500)):
-            np.save(image_path, np.random.default_rng(H).integers(0, 256, (H, W, 3), dtype=np.uint8))
-            im = imread(image_path)
-            masks, bxs, scores = t._segmentation_forward(im)
-            _, result_box = gpu_mask_voting(masks, bxs, scores, 21, 100, im.shape[1], im.shape[0])
-            ranked = np.sort(np.concatenate([b[:, 4] for b in result_box]))[::-1]
-            thr = float(ranked[min(args.keep, len(ranked)) - 1])
-            dt = PackedMasks(**t.net._inst.view().masks(H, W, score_thresh=thr).fetch().arrays())       # host arrays alone
-            t.net.sync()
-            n, d = len(dt), boundary.boundary_distance(H, W)
-            gt = dt.take(np.linspace(0, n - 1, min(args.gts, n)).astype(int))
-            crowd = (np.arange(len(gt)) % 10 == 9).astype(np.uint8)
-            want_b, got_b = boundary.boundary_numpy(dt, H, W, d), dt.boundary(H, W)                     # (the warm-ups)
-            same_b = all(np.array_equal(getattr(want_b, f), getattr(got_b, f)) for f in PackedMasks.FIELDS)
-            want_m, got_m = match_boundary_numpy(dt, gt, H, W, crowd, return_iou=True), dt.match_boundary(gt, H, W, crowd, return_iou=True)
-            same_m = all(np.array_equal(a, b) for a, b in zip(want_m[0], got_m[0])) and np.array_equal(want_m[1], got_m[1])
-            b_host = _median_ms(lambda: boundary.boundary_numpy(dt, H, W, d), args.host_iters)
-            b_dev = _median_ms(lambda: dt.boundary(H, W), args.iters)
-            m_host = _median_ms(lambda: match_boundary_numpy(dt, gt, H, W, crowd), args.host_iters)
-            m_dev = _median_ms(lambda: dt.match_boundary(gt, H, W, crowd), args.iters)
-            room = np.zeros(max(want_b.bits.size, 1), np.uint64)
-            sizes.append({"image": "%dx%d" % (H, W), "d": d, "detections": n, "ground_truths": len(gt), "bits_bytes": int(dt.bits.nbytes),
-                          "boundary_bits_bytes": int(want_b.bits.nbytes), "pixels_set": int(dt.areas.sum()),
-                          "boundary_pixels": int(want_b.areas.sum()), "matches_at_iou50": int((want_m[0].dt_match[0, 0] >= 0).sum()),
-                          "boundary_equals_host": bool(same_b), "match_equals_host": bool(same_m),
-                          "boundary_host_ms_median": b_host[0], "boundary_host_ms_min": b_host[1],
-                          "boundary_device_ms_median": b_dev[0], "boundary_device_ms_min": b_dev[1],
-                          "boundary_kernels_us_median": _kernels_us(lambda: boundary.boundary_call(dt, H, W, d, room), args.iters),
-                          "match_host_ms_median": m_host[0], "match_host_ms_min": m_host[1],
-                          "match_device_ms_median": m_dev[0], "match_device_ms_min": m_dev[1],
-                          "match_kernels_us_median": _kernels_us(lambda: dt.match_boundary(gt, H, W, crowd), args.iters)})
-        line = json.dumps({"workload": "boundary bands (2 % of the diagonal) of mnc 5-stage vgg16's voted instances at image resolution, "
-                                       "and COCO matching on min(mask IoU, boundary IoU) against synthetic ground truths",
-                           "host": "boundary_numpy / match_boundary_numpy on a host PackedMasks",
-                           "device": "PackedMasks.boundary (two mnc_mask_boundary calls) / PackedMasks.match_boundary (one "
-                                     "mnc_mask_match_boundary call), host arrays in and out",
-                           "device_rounds": max(args.iters, 1), "host_rounds": max(args.host_iters, 1), "sizes": sizes})
-        print(line)
-        if args.profile:
-            with open(args.profile, "w") as f:
-                f.write(HEADING % (max(args.iters, 1), max(args.host_iters, 1), args.keep, args.gts) + line + "\n")
-        t.net.close()
+    timed = lambda fn: kernels_us("mnc_mask_boundary_timing", fn, args.iters)        # noqa: E731 (fn: a single call of one of the two entries)
+    sizes = []
+    for H, W, _, dt, _ in voted_instances("mask_boundary_bench", args.keep, args.math):
+        n, d = len(dt), boundary.boundary_distance(H, W)
+        gt = dt.take(np.linspace(0, n - 1, min(args.gts, n)).astype(int))
+        crowd = (np.arange(len(gt)) % 10 == 9).astype(np.uint8)
+        want_b, got_b = boundary.boundary_numpy(dt, H, W, d), dt.boundary(H, W)                     # (the warm-ups)
+        same_b = all(np.array_equal(getattr(want_b, f), getattr(got_b, f)) for f in PackedMasks.FIELDS)
+        want_m, got_m = match_boundary_numpy(dt, gt, H, W, crowd, return_iou=True), dt.match_boundary(gt, H, W, crowd, return_iou=True)
+        same_m = all(np.array_equal(a, b) for a, b in zip(want_m[0], got_m[0])) and np.array_equal(want_m[1], got_m[1])
+        b_host = median_ms(lambda: boundary.boundary_numpy(dt, H, W, d), args.host_iters)
+        b_dev = median_ms(lambda: dt.boundary(H, W), args.iters)
+        m_host = median_ms(lambda: match_boundary_numpy(dt, gt, H, W, crowd), args.host_iters)
+        m_dev = median_ms(lambda: dt.match_boundary(gt, H, W, crowd), args.iters)
+        room = np.zeros(max(want_b.bits.size, 1), np.uint64)
+        sizes.append({"image": "%dx%d" % (H, W), "d": d, "detections": n, "ground_truths": len(gt), "bits_bytes": int(dt.bits.nbytes),
+                      "boundary_bits_bytes": int(want_b.bits.nbytes), "pixels_set": int(dt.areas.sum()),
+                      "boundary_pixels": int(want_b.areas.sum()), "matches_at_iou50": int((want_m[0].dt_match[0, 0] >= 0).sum()),
+                      "boundary_equals_host": bool(same_b), "match_equals_host": bool(same_m),
+                      "boundary_host_ms_median": b_host[0], "boundary_host_ms_min": b_host[1],
+                      "boundary_device_ms_median": b_dev[0], "boundary_device_ms_min": b_dev[1],
+                      "boundary_kernels_us_median": timed(lambda: boundary.boundary_call(dt, H, W, d, room)),
+                      "match_host_ms_median": m_host[0], "match_host_ms_min": m_host[1],
+                      "match_device_ms_median": m_dev[0], "match_device_ms_min": m_dev[1],
+                      "match_kernels_us_median": timed(lambda: dt.match_boundary(gt, H, W, crowd))})
+    emit({"workload": "boundary bands (2 % of the diagonal) of mnc 5-stage vgg16's voted instances at image resolution, "
+                      "and COCO matching on min(mask IoU, boundary IoU) against synthetic ground truths",
+          "host": "boundary_numpy / match_boundary_numpy on a host PackedMasks",
+          "device": "PackedMasks.boundary (two mnc_mask_boundary calls) / PackedMasks.match_boundary (one "
+                    "mnc_mask_match_boundary call), host arrays in and out",
+          "device_rounds": max(args.iters, 1), "host_rounds": max(args.host_iters, 1), "sizes": sizes},
+         HEADING % (max(args.iters, 1), max(args.host_iters, 1), args.keep, args.gts), args.profile)
 
 
 if __name__ == "__main__":

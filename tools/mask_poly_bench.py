@@ -11,36 +11,11 @@ Medians over --iters device rounds and --host-iters host rounds after one warm-u
     python tools/mask_poly_bench.py [--iters 20] [--host-iters 3]
 """
 import argparse
-import json
 import math
-import time
 
 import numpy as np
 
-import _init_paths  # noqa: F401
-
-
-def _median_ms(fn, rounds):
-    times = []
-    for _ in range(max(rounds, 1)):
-        t0 = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return round(sorted(times)[len(times) // 2], 3), round(min(times), 3)
-
-
-def _kernels_us(fn, rounds):
-    """Median device time of the launches of one fn() -- a single mnc_mask_from_polygons call -- in microseconds."""
-    import ctypes
-    from mnc_amd import _lib
-    times, last = [], ctypes.c_double(-1.0)
-    for _ in range(max(rounds, 1)):
-        _lib.call("mnc_mask_poly_timing", 1, None)
-        fn()
-        _lib.call("mnc_mask_poly_timing", 0, ctypes.addressof(last))
-        if last.value >= 0:
-            times.append(last.value * 1e3)
-    return round(sorted(times)[len(times) // 2], 2) if times else None
+from _task_harness import emit, kernels_us, median_ms
 
 
 def annotations(H, W, n=20, seed=0):
@@ -74,21 +49,21 @@ def main():
         same = all(np.array_equal(getattr(want, f), getattr(got, f)) for f in ("bounds", "offsets", "areas", "bits"))
         checked, _, _ = polygons._check_segs("mask_poly_bench", segs, H, W)
         xy, vert_ptr, poly_ptr = polygons._flatten(checked)
-        host = _median_ms(lambda: polygons.masks_from_polygons_numpy(segs, H, W), args.host_iters)
-        dev = _median_ms(lambda: PackedMasks.from_polygons(segs, H, W), args.iters)
-        first = _median_ms(lambda: polygons.masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W), args.iters)
+        host = median_ms(lambda: polygons.masks_from_polygons_numpy(segs, H, W), args.host_iters)
+        dev = median_ms(lambda: PackedMasks.from_polygons(segs, H, W), args.iters)
+        first = median_ms(lambda: polygons.masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W), args.iters)
         room = np.zeros(max(want.bits.size, 1), np.uint64)
-        kernels = _kernels_us(lambda: polygons.masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W, room), args.iters)
+        kernels = kernels_us("mnc_mask_poly_timing", lambda: polygons.masks_from_polygons_call(xy, vert_ptr, poly_ptr, H, W, room), args.iters)
         walk = sum(len(polygons.polygon_walk_numpy(p)[0]) for polys in segs for p in polys)
         sizes.append({"image": "%dx%d" % (H, W), "annotations": len(segs), "polygons": int(poly_ptr[-1]), "vertices": int(vert_ptr[-1]),
                       "walk_points": int(walk), "pixels_set": int(want.areas.sum()), "bits_bytes": int(want.bits.nbytes),
                       "device_equals_host": bool(same), "host_ms_median": host[0], "host_ms_min": host[1],
                       "device_ms_median": dev[0], "device_ms_min": dev[1], "device_sizes_only_ms_median": first[0],
                       "device_sizes_only_ms_min": first[1], "kernels_us_median": kernels})
-    print(json.dumps({"workload": "COCO polygon segmentations of one image rasterised into packed masks (maskApi.c's rleFrPoly + merge)",
-                      "host": "masks_from_polygons_numpy", "device": "PackedMasks.from_polygons: two mnc_mask_from_polygons calls, "
-                      "host lists in, host arrays out", "device_rounds": max(args.iters, 1), "host_rounds": max(args.host_iters, 1),
-                      "sizes": sizes}))
+    emit({"workload": "COCO polygon segmentations of one image rasterised into packed masks (maskApi.c's rleFrPoly + merge)",
+          "host": "masks_from_polygons_numpy", "device": "PackedMasks.from_polygons: two mnc_mask_from_polygons calls, "
+          "host lists in, host arrays out", "device_rounds": max(args.iters, 1), "host_rounds": max(args.host_iters, 1),
+          "sizes": sizes})
 
 
 if __name__ == "__main__":
