@@ -538,6 +538,57 @@ MNC_API int mnc_mask_split(const int* bounds, const long long* offsets, const vo
 MNC_API int mnc_mask_components_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n13 The masks as outlines: the boundary of every instance of a packed set as closed rectilinear polygons
+ *     (csrc/mask_contours.hip, csrc/mask_contour.h) -- on the layout of n5.  The statement of the rule is
+ *     mnc_amd/contours.py:contours_numpy.
+ *     Pixel (x, y) of the image is the unit square [x, x + 1] x [y, y + 1]; vertices are lattice points in image coordinates
+ *     (the instance's bounds added in), int32.  A boundary edge is a unit side between a set pixel of instance i and an unset
+ *     one; pixels outside the instance's bounds are unset, padding bits are not trusted.  An edge is directed so that the set
+ *     pixel is on its right, y pointing down: the top side runs +x, the right side +y, the bottom side -x, the left side -y.
+ *     Outer boundaries then run clockwise on screen and holes the other way.  The successor of an edge is the boundary edge
+ *     that leaves its head vertex.  Two leave only where two set pixels touch at a corner alone: there connectivity = 8 takes
+ *     the left turn, so that the two pixels share one loop, and connectivity = 4 the right turn, so that each keeps its own.
+ *     The successor relation is a permutation of the edges; its cycles are the loops.
+ *     The vertices of a loop are the tails of those of its edges whose predecessor has another direction: consecutive
+ *     vertices differ in exactly one coordinate, horizontal and vertical sides alternate, no three consecutive vertices are
+ *     collinear.  The list starts at the loop's smallest vertex in (y, x) order and follows the direction of travel; the
+ *     first vertex is not repeated at the end.  A loop passes through that start vertex once, and it is the start of at most
+ *     one loop.  A loop is a hole exactly when its first side runs +y.  The loops of an instance are ordered by their start
+ *     vertex (y, x); the loops of a set are those of instance 0, then of instance 1, ...: loop_ptr [n + 1], loop_ptr[0] = 0,
+ *     instance i has the loops loop_ptr[i] .. loop_ptr[i + 1] - 1; loop l has the vertices vert_ptr[l] .. vert_ptr[l + 1] - 1
+ *     of xy.  An instance without rows or without a set pixel has no loops.  area[l] is the signed shoelace area of loop l,
+ *     exact: positive for an outer loop, negative for a hole; the areas of an instance's loops sum to its pixel count.
+ *     (A rectilinear polygon on lattice points is rasterised exactly by n10's rule: the XOR of the loops of an instance,
+ *     rasterised one by one, is the instance.)
+ *     Edges are numbered, not pixels.  The four masks of the edges that leave the 64 lattice points of a word are bit
+ *     expressions of the pixel words above and below and their carries; a scan of their counts numbers the edges in the order
+ *     instance, tail y, tail x, direction, so the smallest id of a cycle is the edge that leaves the loop's start vertex and a
+ *     scan of the leader flags numbers the loops in the order above.  The leaders are found by pointer jumping with a running
+ *     minimum and the vertex slots by Wyllie's list ranking of the cycles cut in front of their leaders, ceil(log2(E)) rounds
+ *     each for E edges, every round a launch of its own from one pair of buffers into the other.  Integer atomics only (the
+ *     64-bit adds of the areas); every other slot is written once: the same input gives the same bytes on every run.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* The set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds.  Outputs: loop_ptr
+ * [n + 1], *n_loops = L = loop_ptr[n], *n_verts = V; vert_ptr [L + 1] (vert_ptr[L] = V), area [L], xy [V][2] (x, y).
+ * xy == NULL: loop_ptr and the two sizes only (vert_ptr and area are not looked at).  Otherwise loop_cap is the room of area
+ * in loops (vert_ptr has room for loop_cap + 1 entries) and vert_cap the room of xy in vertices; loop_cap < L or vert_cap < V
+ * is MNC_ERR_INVALID with loop_ptr and the two sizes set and nothing else written, so that the caller calls again with room.
+ * Entries past the reported sizes are never written.  n == 0 and sets without a single row are answered on the host.
+ * MNC_ERR_INVALID, checked on the host before anything is launched: connectivity not 4 or 8; everything mnc_mask_rle refuses
+ * about a set; more than 2^25 words of rows in the set, counted on the lattice points ((h + 1) rows of ceil((w + 1) / 64)
+ * words per instance); a null pointer where one is needed.  MNC_ERR_INVALID after the counting pass: more than 2^30 boundary
+ * edges in the set.  (There is no form that reads a device-resident mnc_mask_records result: the PackedMasks method fetches
+ * such a result first.) */
+MNC_API int mnc_mask_contours(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int connectivity,
+                              long long* loop_ptr, long long* vert_ptr, long long* area, int* xy, size_t loop_cap, size_t vert_cap,
+                              size_t* n_loops, size_t* n_verts, int device_id);
+/* For tools/mask_contours_bench.py.  on = 1: the following calls of mnc_mask_contours put a HIP event pair around their launches
+ * (with the read-backs of the totals between them, without the copies of the results) and keep the last call's time in
+ * milliseconds; on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when
+ * there is none; switching on forgets it. */
+MNC_API int mnc_mask_contours_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

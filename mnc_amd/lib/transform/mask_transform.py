@@ -292,6 +292,18 @@ def mask_split(pm, connectivity=8):
     return pm.split(connectivity, device_id=cfg.GPU_ID)
 
 
+def mask_contours(pm, connectivity=8):
+    """The outlines of a PackedMasks as closed rectilinear loops on the GPU (mnc_mask_contours, csrc/mask_contours.hip) ->
+    mnc_amd.contours.Contours(loop_ptr, vert_ptr, area, xy)."""
+    return pm.contours(connectivity, device_id=cfg.GPU_ID)
+
+
+def mask_polygons(pm, connectivity=8):
+    """One COCO `segmentation` (a list of flat [x0, y0, x1, y1, ...] lists) per instance of a PackedMasks on the GPU: its outer
+    loops, the holes dropped."""
+    return pm.polygons(connectivity, device_id=cfg.GPU_ID)
+
+
 def mask_rle(pm, H, W):
     """COCO RLEs of a PackedMasks in an H x W image on the GPU (mnc_mask_rle / mnc_mask_rle_dev): -> [{"size": [H, W], "counts":
     str}] per instance."""

@@ -16,6 +16,7 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
     PackedMasks.boundary / .match_boundary   the boundary bands and the matching on min(mask IoU, boundary IoU) (mnc_amd/boundary.py, n11)
     PackedMasks.components / .select / .fill_holes / .split   connected components and what is built on them (mnc_amd/components.py, n12)
+    PackedMasks.contours / .polygons   the outlines as closed loops of lattice points, and as COCO polygons (mnc_amd/contours.py, n13)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -226,6 +227,22 @@ class PackedMasks(object):
         (mnc_amd.components.split_numpy's rule through mnc_mask_split).  A device-resident result is fetched to the host first."""
         from . import components
         return components.split(self, connectivity, device_id)
+
+    def contours(self, connectivity=8, device_id=None):
+        """The outline of every instance as closed rectilinear loops on lattice points, outer loops clockwise on screen and holes
+        the other way -> mnc_amd.contours.Contours(loop_ptr, vert_ptr, area, xy), by the rule of mnc_amd.contours.contours_numpy
+        (include/mnc_hip.h n13, csrc/mask_contours.hip) on the GPU.  A device-resident result is fetched to the host first."""
+        from . import contours
+        return contours.contours(self, connectivity, device_id)
+
+    def polygons(self, connectivity=8, device_id=None):
+        """One COCO `segmentation` per instance: the outer loops of contours(connectivity) as flat [x0, y0, x1, y1, ...] float
+        lists, the holes dropped.  COCO's polygons of one annotation are OR-ed, so they cannot say a hole: for masks inside the
+        H x W image, from_polygons(pm.polygons(c), H, W) is pm.fill_holes(4 if c == 8 else 8) -- the holes of the background of the
+        complementary connectivity filled -- with tight bounds.  Contours.polygons(i, holes=True) keeps the holes for a reader that
+        XORs."""
+        from . import contours
+        return contours.polygons(self, connectivity, device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

@@ -1,4 +1,4 @@
-"""What the bench tools of the packed-mask tasks share (mask_overlap / mask_rle / mask_match / mask_boundary / mask_components
+"""What the bench tools of the packed-mask tasks share (mask_overlap / mask_rle / mask_match / mask_boundary / mask_components / mask_contours
 _bench.py; mask_poly_bench.py and coco_accum_bench.py take the timers and emit alone): the timers, the instances of the two
 synthetic images, the output line."""
 import argparse
@@ -16,7 +16,7 @@ SIZES = ((600, 1000), (375, 500))
 
 
 def parser():
-    """The flags the five instance tools share."""
+    """The flags the instance tools share."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--host-iters", type=int, default=3)

@@ -4,7 +4,8 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR] [--save-coco FILE] [--min-component-area A [--largest-component]]
+                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE]
+                         [--min-component-area A [--largest-component]]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -13,7 +14,10 @@ the numpy form of the per-instance masks (transform.mask_transform.instance_mask
 the numpy form of the run-length encoding as well (mnc_amd.rle.rle_counts_numpy).  --min-component-area A drops the 8-connected
 components of fewer than A pixels from every mask that --save-masks / --save-coco write, --largest-component keeps the largest of
 what is left (PackedMasks.select, csrc/mask_components.hip; with --cpu mnc_amd.components.select_numpy); without the two flags the
-output is what it was."""
+output is what it was.  --save-annotations FILE writes the same instances as a COCO annotation-format file (images, categories,
+annotations) whose segmentations are polygons: the outer loops of the masks' outlines (PackedMasks.contours, csrc/mask_contours.hip;
+with --cpu mnc_amd.contours.contours_numpy).  Polygons belong in annotation files; COCO results files carry RLE, which is what
+--save-coco writes.  tools/eval_coco.py --gt FILE --polygons reads the file."""
 import argparse
 import os
 import time
@@ -50,8 +54,13 @@ def parse_args(argv=None):
     p.add_argument("--save-coco", dest="save_coco", default=None, metavar="FILE",
                    help="write the instances scoring >= --vis-thresh of all images as one JSON array of COCO results: "
                         "{image_id, category_id, segmentation: {size, counts}, bbox, score}, the masks run-length encoded")
+    p.add_argument("--save-annotations", dest="save_annotations", default=None, metavar="FILE",
+                   help="write the instances scoring >= --vis-thresh of all images as one COCO annotation-format file: images, "
+                        "categories and annotations {id, image_id, category_id, segmentation: [polygons], bbox, area, iscrowd: 0, "
+                        "score}, the polygons being the outer outlines of the masks (holes are filled: COCO ORs the polygons)")
     p.add_argument("--min-component-area", dest="min_component_area", default=0, type=int, metavar="A",
-                   help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco write")
+                   help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco / "
+                        "--save-annotations write")
     p.add_argument("--largest-component", dest="largest_component", action="store_true",
                    help="keep only the largest 8-connected component of every written mask")
     return p.parse_args(argv)
@@ -197,6 +206,27 @@ def _coco_results(image_id, im_shape, packed, cpu=False):
     return out
 
 
+def _coco_annotations(image_id, packed, first_id=1, cpu=False):
+    """-> COCO annotation entries of one image's PackedMasks: segmentation = the outer loops of the 8-connected outline as polygons
+    (on the GPU, csrc/mask_contours.hip; cpu=True: the numpy statement), bbox = [x, y, w, h] of the polygons' extent (the tight box
+    of the mask's pixels), area = the mask's pixel count, iscrowd 0.  An instance without a set pixel has no polygons.  A
+    device-resident result is fetched first."""
+    from mnc_amd import contours
+    packed = packed.fetch()
+    c = contours.contours_numpy(packed, 8) if cpu else packed.contours(8)
+    out = []
+    for i in range(len(packed)):
+        outer = [xy for xy, area in c.loops(i) if area > 0]
+        if outer:
+            lo, hi = np.min([xy.min(axis=0) for xy in outer], axis=0), np.max([xy.max(axis=0) for xy in outer], axis=0)
+            bbox = [float(lo[0]), float(lo[1]), float(hi[0] - lo[0]), float(hi[1] - lo[1])]
+        else:
+            bbox = [0.0, 0.0, 0.0, 0.0]
+        out.append({"id": first_id + i, "image_id": image_id, "category_id": int(packed.classes[i]), "segmentation": c.polygons(i),
+                    "bbox": bbox, "area": float(packed.areas[i]), "iscrowd": 0, "score": float(packed.scores[i])})
+    return out
+
+
 def _save_masks(out_dir, name, im_shape, result_mask, result_box, view=None, score_thresh=0.5, cpu=False, packed=None):
     """The instances scoring >= score_thresh (_packed_masks) -> <out_dir>/<name>_masks.npz (mnc_amd.masks.PackedMasks.load reads
     it back)."""
@@ -237,7 +267,7 @@ def main(argv=None):
     if not images:
         print("no images given; running one synthetic 600x1000 image")
         images = [None]
-    coco = []
+    coco, annotations, image_entries = [], [], []
     for path in images:
         print("~" * 35)
         print("Demo for {}".format(path or "<synthetic 600x1000>"))
@@ -250,7 +280,7 @@ def main(argv=None):
         print("mask voting time %f" % (time.time() - start))
         pred = get_vis_dict(result_box, result_mask, path or "synthetic", CLASSES, args.vis_thresh)
         print("%d instances with score >= %g" % (len(pred["boxes"]), args.vis_thresh))
-        if args.save_masks or args.save_coco:
+        if args.save_masks or args.save_coco or args.save_annotations:
             from mnc_amd.devarray import DeviceArray
             blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
@@ -260,6 +290,10 @@ def main(argv=None):
                 packed = _select_components(packed, args.min_component_area, args.largest_component, args.cpu_mode)
             if args.save_coco:                                    # (first: a device-resident result is encoded where it lies)
                 coco.extend(_coco_results(name, im.shape, packed, args.cpu_mode))
+            if args.save_annotations:
+                image_entries.append({"id": name, "file_name": os.path.basename(path) if path else name, "height": int(im.shape[0]),
+                                      "width": int(im.shape[1])})
+                annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode))
             if args.save_masks:
                 out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, packed=packed)
                 print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
@@ -280,6 +314,12 @@ def main(argv=None):
         with open(args.save_coco, "w") as f:
             json.dump(coco, f)
         print("wrote %s (%d instances)" % (args.save_coco, len(coco)))
+    if args.save_annotations:
+        import json
+        with open(args.save_annotations, "w") as f:
+            json.dump({"images": image_entries, "categories": [{"id": k + 1, "name": c} for k, c in enumerate(CLASSES)],
+                       "annotations": annotations}, f)
+        print("wrote %s (%d annotations of %d images)" % (args.save_annotations, len(annotations), len(image_entries)))
     net.close()
 
 
