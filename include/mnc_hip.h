@@ -589,6 +589,46 @@ MNC_API int mnc_mask_contours(const int* bounds, const long long* offsets, const
 MNC_API int mnc_mask_contours_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n14 Outlines simplified to a pixel tolerance: Douglas-Peucker on closed loops in exact integer arithmetic
+ *     (csrc/contour_simplify.hip), so that the parallel form equals a sequential one bit for bit.  The statement of the rule
+ *     is mnc_amd/contours.py:simplify_numpy.
+ *     Input: loops as n13 gives them (vert_ptr, xy int32) -- any closed integer loops, not only rectilinear ones; the first
+ *     vertex is not repeated.  The tolerance is q sixteenths of a pixel (the host quantises: q = round-half-even(16 epsilon)).
+ *     A loop v_0 .. v_(k-1), v_k = v_0, of k <= 3 vertices is unchanged.  Otherwise the anchors are index 0 and B, the index in
+ *     1 .. k - 1 with the largest |v_B - v_0|^2 (the lowest on ties), and the two chains are (0, B) and (B, k).
+ *     The deviation of m in the segment (i, j), i < m < j, with a = v_i, b = v_(j mod k), p = v_m, ab = b - a, ap = p - a,
+ *     L = ab.ab and t = ap.ab, is the pair (N, D): L == 0 gives (|ap|^2, 1); t <= 0 gives (|ap|^2 L, L); t >= L gives
+ *     (|p - b|^2 L, L); otherwise ((ab x ap)^2, L).  N / D is the squared distance of p from the segment; D is common to the
+ *     segment.  split(i, j) does nothing when j - i < 2; else m* is the m with the largest N (the lowest on ties), and if
+ *     256 N > q^2 D, m* is kept and split(i, m*) and split(m*, j) follow.  Both chains are split.  If neither keeps a vertex
+ *     (only 0 and B are kept), the third anchor applies: the m with the largest N over both chains -- they share L -- is kept
+ *     whatever q is (the lowest index on ties), and the two halves of its chain are split.  So a closed loop never comes out
+ *     with fewer than three vertices.  The output is the kept vertices in index order; v_0 is always first; loops are never
+ *     dropped.  Like every plain Douglas-Peucker the rule does not preserve topology: a simplified loop may touch or cross
+ *     itself or another one.
+ *     Coordinates are accepted in [-2^24, 2^24]: ab x ap is below 2^51 in size, N below 2^102, 256 N and q^2 D below 2^110.
+ *     The device works in 128-bit integers; there is no floating point.  A decision is a pure function of its segment's
+ *     vertices, so the segments may be taken in any order: loops of at most 64 vertices go one per wave, longer ones one per
+ *     workgroup (staged in LDS up to 4096 vertices) whose rounds over a double-buffered list of open segments run inside the
+ *     one launch; only the kept flags leave those kernels, a scan in index order places the vertices.  One memset and five
+ *     launches whatever the data, one read-back of V': the same input gives the same bytes on every run.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers.  vert_ptr [n_loops + 1], xy [n_verts][2] (x, y).  Outputs: out_vert_ptr [n_loops + 1], *out_verts = V' =
+ * out_vert_ptr[n_loops]; out_xy [V'][2] the kept vertices, out_index [V'] their positions in xy.  out_xy and out_index have room
+ * for n_verts vertices (V' <= n_verts): there is no second call.  Entries past n_loops + 1 of out_vert_ptr and past V' of out_xy and
+ * out_index are never written.  n_loops == 0 or n_verts == 0 is answered on the host.  MNC_ERR_INVALID, checked on the host before
+ * anything is launched and with nothing written: q outside [0, 2^20]; n_loops > 2^24 or n_verts > 2^27; a null pointer where one
+ * is needed (xy, out_xy and out_index may be null when n_verts == 0); a vert_ptr that does not start at 0, decreases, or does not
+ * end at n_verts; a coordinate outside [-2^24, 2^24]. */
+MNC_API int mnc_contours_simplify(const long long* vert_ptr, const int* xy, size_t n_loops, size_t n_verts, int q,
+                                  long long* out_vert_ptr, int* out_xy, long long* out_index, size_t* out_verts, int device_id);
+/* For tools/contours_simplify_bench.py.  on = 1: the following calls of mnc_contours_simplify put a HIP event pair around their
+ * launches (without the copies of the loops and of the result and without the read-back of V') and keep the last call's time in
+ * milliseconds; on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when
+ * there is none; switching on forgets it. */
+MNC_API int mnc_contours_simplify_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

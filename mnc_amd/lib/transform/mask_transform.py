@@ -298,10 +298,10 @@ def mask_contours(pm, connectivity=8):
     return pm.contours(connectivity, device_id=cfg.GPU_ID)
 
 
-def mask_polygons(pm, connectivity=8):
+def mask_polygons(pm, connectivity=8, epsilon=0.0):
     """One COCO `segmentation` (a list of flat [x0, y0, x1, y1, ...] lists) per instance of a PackedMasks on the GPU: its outer
-    loops, the holes dropped."""
-    return pm.polygons(connectivity, device_id=cfg.GPU_ID)
+    loops, the holes dropped; with epsilon > 0 simplified to that many pixels (mnc_contours_simplify, csrc/contour_simplify.hip)."""
+    return pm.polygons(connectivity, device_id=cfg.GPU_ID, epsilon=epsilon)
 
 
 def mask_rle(pm, H, W):

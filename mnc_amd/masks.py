@@ -16,7 +16,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     PackedMasks.match(gt, iscrowd)  COCO's matching of detections to ground truths (mnc_amd/coco_eval.py, n8)
     PackedMasks.boundary / .match_boundary   the boundary bands and the matching on min(mask IoU, boundary IoU) (mnc_amd/boundary.py, n11)
     PackedMasks.components / .select / .fill_holes / .split   connected components and what is built on them (mnc_amd/components.py, n12)
-    PackedMasks.contours / .polygons   the outlines as closed loops of lattice points, and as COCO polygons (mnc_amd/contours.py, n13)
+    PackedMasks.contours / .polygons   the outlines as closed loops of lattice points, and as COCO polygons (mnc_amd/contours.py, n13),
+                                       simplified to a tolerance with polygons(epsilon=) (n14)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -235,14 +236,15 @@ class PackedMasks(object):
         from . import contours
         return contours.contours(self, connectivity, device_id)
 
-    def polygons(self, connectivity=8, device_id=None):
+    def polygons(self, connectivity=8, device_id=None, epsilon=0.0):
         """One COCO `segmentation` per instance: the outer loops of contours(connectivity) as flat [x0, y0, x1, y1, ...] float
         lists, the holes dropped.  COCO's polygons of one annotation are OR-ed, so they cannot say a hole: for masks inside the
         H x W image, from_polygons(pm.polygons(c), H, W) is pm.fill_holes(4 if c == 8 else 8) -- the holes of the background of the
         complementary connectivity filled -- with tight bounds.  Contours.polygons(i, holes=True) keeps the holes for a reader that
-        XORs."""
+        XORs.  epsilon > 0: the loops simplified to that many pixels on the GPU (Contours.simplify, include/mnc_hip.h n14: what
+        cv2.approxPolyDP does after findContours); epsilon == 0, the default, is the exact pixel staircase."""
         from . import contours
-        return contours.polygons(self, connectivity, device_id)
+        return contours.polygons(self, connectivity, device_id, epsilon)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

@@ -4,7 +4,7 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE]
+                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E]]
                          [--min-component-area A [--largest-component]]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
@@ -17,7 +17,9 @@ what is left (PackedMasks.select, csrc/mask_components.hip; with --cpu mnc_amd.c
 output is what it was.  --save-annotations FILE writes the same instances as a COCO annotation-format file (images, categories,
 annotations) whose segmentations are polygons: the outer loops of the masks' outlines (PackedMasks.contours, csrc/mask_contours.hip;
 with --cpu mnc_amd.contours.contours_numpy).  Polygons belong in annotation files; COCO results files carry RLE, which is what
---save-coco writes.  tools/eval_coco.py --gt FILE --polygons reads the file."""
+--save-coco writes.  tools/eval_coco.py --gt FILE --polygons reads the file.  --polygon-epsilon E simplifies those polygons to E
+pixels (Contours.simplify, csrc/contour_simplify.hip; with --cpu mnc_amd.contours.simplify_numpy); 0, the default, writes the exact
+pixel staircase."""
 import argparse
 import os
 import time
@@ -58,6 +60,9 @@ def parse_args(argv=None):
                    help="write the instances scoring >= --vis-thresh of all images as one COCO annotation-format file: images, "
                         "categories and annotations {id, image_id, category_id, segmentation: [polygons], bbox, area, iscrowd: 0, "
                         "score}, the polygons being the outer outlines of the masks (holes are filled: COCO ORs the polygons)")
+    p.add_argument("--polygon-epsilon", dest="polygon_epsilon", default=0.0, type=float, metavar="E",
+                   help="simplify the polygons --save-annotations writes to E pixels (Douglas-Peucker on the closed loops) [0: the "
+                        "exact outline]")
     p.add_argument("--min-component-area", dest="min_component_area", default=0, type=int, metavar="A",
                    help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco / "
                         "--save-annotations write")
@@ -206,14 +211,17 @@ def _coco_results(image_id, im_shape, packed, cpu=False):
     return out
 
 
-def _coco_annotations(image_id, packed, first_id=1, cpu=False):
+def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0):
     """-> COCO annotation entries of one image's PackedMasks: segmentation = the outer loops of the 8-connected outline as polygons
     (on the GPU, csrc/mask_contours.hip; cpu=True: the numpy statement), bbox = [x, y, w, h] of the polygons' extent (the tight box
-    of the mask's pixels), area = the mask's pixel count, iscrowd 0.  An instance without a set pixel has no polygons.  A
-    device-resident result is fetched first."""
+    of the mask's pixels; with epsilon > 0 the extent of the polygons written), area = the mask's pixel count, iscrowd 0.  An
+    instance without a set pixel has no polygons.  epsilon > 0 simplifies the loops to that many pixels (csrc/contour_simplify.hip;
+    cpu=True: simplify_numpy).  A device-resident result is fetched first."""
     from mnc_amd import contours
     packed = packed.fetch()
     c = contours.contours_numpy(packed, 8) if cpu else packed.contours(8)
+    if epsilon != 0:
+        c = contours.simplify_numpy(c, epsilon) if cpu else c.simplify(epsilon)
     out = []
     for i in range(len(packed)):
         outer = [xy for xy, area in c.loops(i) if area > 0]
@@ -293,7 +301,7 @@ def main(argv=None):
             if args.save_annotations:
                 image_entries.append({"id": name, "file_name": os.path.basename(path) if path else name, "height": int(im.shape[0]),
                                       "width": int(im.shape[1])})
-                annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode))
+                annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode, args.polygon_epsilon))
             if args.save_masks:
                 out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, packed=packed)
                 print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
