@@ -22,6 +22,17 @@ class Dev(object):
         self._ptrs.append(p.value)
         return p.value
 
+    def mark(self):
+        """-> a mark for free_since: the allocations made so far."""
+        return len(self._ptrs)
+
+    def free_since(self, mark):
+        """Frees every allocation made after mark() (waits for the context's stream first)."""
+        self.sync()
+        for p in self._ptrs[mark:]:
+            _lib.call("mnc_dev_free", self.h, p)
+        del self._ptrs[mark:]
+
     def put(self, arr, dtype=np.float32):
         arr = np.ascontiguousarray(arr, dtype=dtype)
         p = self.alloc(max(arr.nbytes, 16))

@@ -207,7 +207,8 @@ def test_conv3x3_winograd_f4_is_bit_reproducible(dev, H, W, Cin, Cout):
     runs, not necessarily as an error against the reference.  A weak guard on its own: round 4's race (a fast wave refilled halo
     buffer 0 while a slow one was still reading it in its prologue) passed this test and every unit test -- back-to-back launches
     of one kernel keep the waves in step -- and failed tests/test_gpu_pipeline.py::test_image_stream_returns_results_in_order six
-    times out of six, where other streams' kernels share the CUs.  That test is the guard; this one covers the shapes it runs."""
+    times out of six, where other streams' kernels share the CUs.  tests/test_gpu_contention.py runs the F(4x4) plans (and the other
+    LDS-DMA and split-K kernels) under that condition, against the exact reference."""
     rng = np.random.default_rng(H + W + Cin + Cout)
     x = rng.normal(0, 1, (Cin, H, W)).astype(np.float32)
     w = (rng.normal(0, 1, (Cout, Cin, 3, 3)) * np.sqrt(2.0 / (9 * Cin))).astype(np.float32)
