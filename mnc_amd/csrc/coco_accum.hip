@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "mnc_internal.h"
+#include "scan.h"
 
 namespace mnc {
 
@@ -94,19 +95,10 @@ __global__ __launch_bounds__(kAccumThreads) void accum_hist_kernel(const u64* __
   hist[(size_t)threadIdx.x * tiles + blockIdx.x] = s_hist[threadIdx.x];
 }
 
-__device__ __forceinline__ unsigned accum_wave_incl_scan(unsigned v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned up = __shfl_up(v, o);
-    if (lane >= o) v += up;
-  }
-  return v;
-}
-
 // The exclusive scan of one value a thread over the workgroup's 256 threads; *total = the sum.  s_w: kAccumWaves words of LDS.
 __device__ __forceinline__ unsigned accum_block_excl_scan(unsigned v, unsigned* s_w, unsigned* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned incl = accum_wave_incl_scan(v, lane);
+  const unsigned incl = wave_incl_scan(v, lane);
   __syncthreads();                                                 // s_w may still be read from the call before
   if (lane == 63) s_w[wave] = incl;
   __syncthreads();

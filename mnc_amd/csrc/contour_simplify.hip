@@ -16,7 +16,7 @@
 //                     varies from run to run, no flag does).  The rounds end when a list stays empty: as many as the recursion is
 //                     deep, k / 2 at the most, all inside the one launch, a barrier each.  Up to kCsLdsVerts vertices a loop's
 //                     vertices and lists are staged in LDS; a longer loop is read from global memory and has its lists there.
-//   cs_scan_tiles_kernel, cs_scan_top_kernel   the exclusive prefix of the kept flags: in tiles of 1024, then over the tiles.
+//   scan_launch       (scan.hip: two launches) the exclusive prefix of the kept flags: in tiles of 1024, then over the tiles.
 //   cs_write_kernel   one thread per vertex: a kept vertex and its index into the slot the prefix names; one per loop: the prefix
 //                     at its first vertex is its new vert_ptr.
 // One memset (the flags) and five launches whatever the data; V' is read back once, to size the copies of the result.
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "mnc_internal.h"
+#include "scan.h"
 
 namespace mnc {
 
@@ -36,7 +37,6 @@ constexpr int kCsWaveVerts = 64;                  // loops up to here: one wave
 constexpr int kCsBlockThreads = 512;              // cs_block_kernel: 8 waves, a segment each
 constexpr int kCsBlockWaves = kCsBlockThreads / 64;
 constexpr int kCsLdsVerts = 4096;                 // loops up to here: vertices and segment lists in LDS (32 KiB each)
-constexpr int kCsTile = 1024;                     // entries of one scan tile: 4 per thread
 constexpr int kCsMaxBlocks = 2048;                // workgroups of cs_block_kernel (two of them fit a CU)
 constexpr int kCsMaxQ = 1 << 20;
 constexpr int kCsMaxCoord = 1 << 24;
@@ -268,80 +268,15 @@ __global__ __launch_bounds__(kCsBlockThreads) void cs_block_kernel(const long lo
   }
 }
 
-// The two-level scan of mask_components.hip and mask_contours.hip, whose kernels are local to those translation units, on byte
-// flags.  The exclusive prefix of the flags, as the two levels left it.
-struct CsScan {
-  const int* in_tile;
-  const int* tile;
-  int count, tiles;
-  __device__ __forceinline__ int at(long long v) const { return v < count ? in_tile[v] + tile[v / kCsTile] : tile[tiles]; }
-};
-
-__device__ __forceinline__ int cs_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// grid ceil(count / 1024), block 256.  in_tile [count] = the kept flags before this one inside its tile; tile[blockIdx.x] = the
-// tile's sum.
-__global__ __launch_bounds__(kCsThreads) void cs_scan_tiles_kernel(const unsigned char* __restrict__ keep, int count,
-                                                                   int* __restrict__ in_tile, int* __restrict__ tile) {
-  __shared__ int s_wave[kCsWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long k0 = (long long)blockIdx.x * kCsTile + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = k0 + e < count ? keep[k0 + e] : 0;
-  const int sum = v[0] + v[1] + v[2] + v[3];
-  const int incl = cs_wave_incl_scan(sum, lane);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - sum;
-  for (int k = 0; k < wave; ++k) before += s_wave[k];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (k0 + e < count) in_tile[k0 + e] = before;
-    before += v[e];
-  }
-  if (threadIdx.x == kCsThreads - 1) tile[blockIdx.x] = before;
-}
-
-// grid 1, block 256.  tile [tiles] -> its exclusive prefix; tile[tiles] = the total.
-__global__ __launch_bounds__(kCsThreads) void cs_scan_top_kernel(int* __restrict__ tile, int tiles) {
-  __shared__ int s_wave[kCsWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int t0 = 0; t0 < tiles; t0 += kCsThreads) {
-    const int t = t0 + threadIdx.x;
-    const int v = t < tiles ? tile[t] : 0;
-    const int incl = cs_wave_incl_scan(v, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = incl - v, all = 0;
-    for (int k = 0; k < kCsWaves; ++k) {
-      if (k < wave) before += s_wave[k];
-      all += s_wave[k];
-    }
-    if (t < tiles) tile[t] = base + before;
-    base += all;
-    __syncthreads();                                         // s_wave is written again
-  }
-  if (threadIdx.x == 0) tile[tiles] = base;
-}
-
 // grid ceil(max(V, n_loops + 1) / 256), block 256.
 __global__ __launch_bounds__(kCsThreads) void cs_write_kernel(const long long* __restrict__ vert_ptr, const int2* __restrict__ xy,
-                                                              int n_loops, const unsigned char* __restrict__ keep, CsScan pre,
+                                                              int n_loops, const unsigned char* __restrict__ keep, Scanned pre,
                                                               long long* __restrict__ out_vert_ptr, int2* __restrict__ out_xy,
                                                               long long* __restrict__ out_index) {
   const long long g = (long long)blockIdx.x * kCsThreads + threadIdx.x;
-  if (g <= n_loops) out_vert_ptr[g] = pre.at(vert_ptr[g]);
+  if (g <= n_loops) out_vert_ptr[g] = pre.upto((int)vert_ptr[g]);
   if (g < pre.count && keep[g]) {
-    const int slot = pre.at(g);
+    const int slot = pre.at((int)g);
     out_xy[slot] = xy[g];
     out_index[slot] = g;
   }
@@ -355,14 +290,11 @@ struct CsWork {
   int2* lists;           // [V]
 };
 
-inline int cs_tiles(size_t n_verts) { return (int)((n_verts + kCsTile - 1) / kCsTile); }
-
 // The whole rule on device pointers, asynchronous on `s`: vert_ptr [L + 1] and xy [V][2] checked by the caller (1 <= L <= 2^24,
 // 1 <= V <= 2^27, the pointers run from 0 to V without decreasing, |coordinate| <= 2^24, 0 <= q <= 2^20) -> out_vert_ptr [L + 1],
-// out_xy [V'][2], out_index [V'] and w.tile[cs_tiles(V)] = V'.  The same launches whatever the data.
+// out_xy [V'][2], out_index [V'] and w.tile[scan_tiles(V)] = V'.  The same launches whatever the data.
 hipError_t cs_launch(hipStream_t s, const long long* vert_ptr, const int* xy, int n_loops, int n_verts, int q, const CsWork& w,
                      long long* out_vert_ptr, int* out_xy, long long* out_index) {
-  const int tiles = cs_tiles((size_t)n_verts);
   const int2* p = (const int2*)xy;
   const dim3 block(kCsThreads);
   const hipError_t e = hipMemsetAsync(w.keep, 0, (size_t)n_verts, s);
@@ -370,11 +302,10 @@ hipError_t cs_launch(hipStream_t s, const long long* vert_ptr, const int* xy, in
   hipLaunchKernelGGL(cs_wave_kernel, dim3((n_loops + kCsWaves - 1) / kCsWaves), block, 0, s, vert_ptr, p, n_loops, q, w.keep);
   hipLaunchKernelGGL(cs_block_kernel, dim3(n_loops < kCsMaxBlocks ? n_loops : kCsMaxBlocks), dim3(kCsBlockThreads), 0, s, vert_ptr, p, n_loops, q,
                      w.keep, w.lists);
-  hipLaunchKernelGGL(cs_scan_tiles_kernel, dim3(tiles), block, 0, s, w.keep, n_verts, w.in_tile, w.tile);
-  hipLaunchKernelGGL(cs_scan_top_kernel, dim3(1), block, 0, s, w.tile, tiles);
+  const Scanned pre = scan_launch(s, w.keep, n_verts, w.in_tile, w.tile);
   const long long items = n_verts > n_loops + 1 ? n_verts : n_loops + 1;
   hipLaunchKernelGGL(cs_write_kernel, dim3((unsigned)((items + kCsThreads - 1) / kCsThreads)), block, 0, s, vert_ptr, p, n_loops,
-                     w.keep, CsScan{w.in_tile, w.tile, n_verts, tiles}, out_vert_ptr, (int2*)out_xy, out_index);
+                     w.keep, pre, out_vert_ptr, (int2*)out_xy, out_index);
   return hipGetLastError();
 }
 
@@ -414,7 +345,7 @@ int mnc_contours_simplify(const long long* vert_ptr, const int* xy, size_t n_loo
     return MNC_OK;
   }
 
-  const int L = (int)n_loops, V = (int)n_verts, tiles = cs_tiles(n_verts);
+  const int L = (int)n_loops, V = (int)n_verts, tiles = scan_tiles(V);
   long long *d_vert_ptr, *d_out_vert_ptr, *d_out_index; int *d_xy, *d_out_xy; CsWork w;
   auto layout = [&](WsLayout l) {
     d_vert_ptr = l.take<long long>(n_loops + 1);

@@ -28,6 +28,7 @@
 
 #include "cv_resize.h"
 #include "mask_set.h"
+#include "scan.h"
 
 namespace mnc {
 
@@ -57,15 +58,6 @@ __host__ __device__ inline long long mask_items(int w, int h) {
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-__device__ __forceinline__ long long wave_incl_scan(long long v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 // block 256.  d_records [record_cap][6 + S*S], rows [0, min(d_counts[0], record_cap)); info [record_cap]; head: kept rows, total
 // bytes and work items.  A rounded, clipped box with x2 < x1 or y2 < y1 keeps its place and has no bytes and no items.

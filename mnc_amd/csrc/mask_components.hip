@@ -6,8 +6,8 @@
 // of one pixel (frame = 1: (w + 2) x (h + 2), the frame set).  The words of all views of a set are numbered in raster order, instance
 // after instance (at most 2^25 of them); one thread works on one word.
 //   cc_count_kernel     the run starts of a word, v & ~((v << 1) | carry), counted.
-//   cc_scan_*_kernel    the exclusive prefix of the counts: in tiles of 1024, then over the tiles; a run's id is the prefix at its
-//                       word + the starts below it in the word (cc_run_at).  The total is read back: it sizes parent[].
+//   scan_launch         (scan.hip) the exclusive prefix of the counts: in tiles of 1024, then over the tiles; a run's id is the prefix
+//                       at its word + the starts below it in the word (cc_run_at).  The total is read back: it sizes parent[].
 //   cc_union_kernel     the runs of a word united with the runs of the row above that they touch (cc_link_word): lock-free, the
 //                       smaller id always becomes the parent.
 //   cc_flatten_kernel   parent[r] = the root of r; flag[r] = r is a root.  The scan of the flags numbers the components: roots are
@@ -27,13 +27,13 @@
 
 #include "mask_cc.h"
 #include "mask_set.h"
+#include "scan.h"
 
 namespace mnc {
 
 constexpr int kCcThreads = 256;
 constexpr int kCcMaxN = 2048;                   // instances of one call
 constexpr long long kCcMaxWords = 1ll << 25;    // words of all views of one call: 32 runs a word, run ids < 2^30
-constexpr int kCcTile = 1024;                   // entries of one scan tile: 4 per thread
 
 // The view of one instance: what the host adds to the set's own table (MaskSet::info).
 struct CcInst {
@@ -78,31 +78,10 @@ struct CcAt {
 // The instance, row and word of word g: the last instance that begins at or before g (one without words begins where the next does).
 template <bool kReal>
 __device__ __forceinline__ CcAt cc_decode(const CcInst* __restrict__ insts, int n, int g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((kReal ? insts[mid].real0 : insts[mid].word0) <= g) lo = mid; else hi = mid - 1;
-  }
+  const int lo = kReal ? mask_owner<&CcInst::real0>(insts, n, g) : mask_owner<&CcInst::word0>(insts, n, g);
   const int local = g - (kReal ? insts[lo].real0 : insts[lo].word0);
   const int per = kReal ? insts[lo].rs : insts[lo].vs;
   return {lo, local / per, local % per};
-}
-
-// A scanned array: the exclusive prefix inside tiles of kCcTile entries, and the exclusive prefix of the tiles' sums (tile[tiles] =
-// the total).
-struct CcScan {
-  const int* in_tile;
-  const int* tile;
-  __device__ __forceinline__ int at(int k) const { return in_tile[k] + tile[k / kCcTile]; }
-};
-
-__device__ __forceinline__ int cc_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // dst[key] += v for the live lanes of a wave, every lane of which comes here: one atomic per wave where its live lanes share the
@@ -134,49 +113,6 @@ __global__ __launch_bounds__(kCcThreads) void cc_count_kernel(MaskSet A, const C
   cnt[g] = v ? __popcll(cc_view_starts(m, at.y, at.j, frame, v)) : 0;
 }
 
-// grid ceil(count / 1024), block 256.  a [count] -> its exclusive prefix inside the tile; tile[blockIdx.x] = the tile's sum.
-__global__ __launch_bounds__(kCcThreads) void cc_scan_tiles_kernel(int* __restrict__ a, int count, int* __restrict__ tile) {
-  __shared__ int s_wave[kCcThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k0 = blockIdx.x * kCcTile + threadIdx.x * 4;
-  const int v0 = k0 < count ? a[k0] : 0, v1 = k0 + 1 < count ? a[k0 + 1] : 0;
-  const int v2 = k0 + 2 < count ? a[k0 + 2] : 0, v3 = k0 + 3 < count ? a[k0 + 3] : 0;
-  const int sum = v0 + v1 + v2 + v3;
-  const int incl = cc_wave_incl_scan(sum, lane);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - sum;
-  for (int k = 0; k < wave; ++k) before += s_wave[k];
-  if (k0 < count) a[k0] = before;
-  if (k0 + 1 < count) a[k0 + 1] = before + v0;
-  if (k0 + 2 < count) a[k0 + 2] = before + v0 + v1;
-  if (k0 + 3 < count) a[k0 + 3] = before + v0 + v1 + v2;
-  if (threadIdx.x == kCcThreads - 1) tile[blockIdx.x] = before + sum;
-}
-
-// grid 1, block 256.  tile [tiles] -> its exclusive prefix; tile[tiles] = the total.
-__global__ __launch_bounds__(kCcThreads) void cc_scan_top_kernel(int* __restrict__ tile, int tiles) {
-  __shared__ int s_wave[kCcThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int t0 = 0; t0 < tiles; t0 += kCcThreads) {
-    const int t = t0 + threadIdx.x;
-    const int v = t < tiles ? tile[t] : 0;
-    const int incl = cc_wave_incl_scan(v, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = incl - v, all = 0;
-    for (int k = 0; k < kCcThreads / 64; ++k) {
-      if (k < wave) before += s_wave[k];
-      all += s_wave[k];
-    }
-    if (t < tiles) tile[t] = base + before;
-    base += all;
-    __syncthreads();                                     // s_wave is written again
-  }
-  if (threadIdx.x == 0) tile[tiles] = base;
-}
-
 // grid ceil(runs / 256), block 256.
 __global__ __launch_bounds__(kCcThreads) void cc_init_kernel(int* __restrict__ parent, int runs) {
   const int r = blockIdx.x * kCcThreads + threadIdx.x;
@@ -185,7 +121,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_init_kernel(int* __restrict__ p
 
 // grid ceil(words / 256), block 256.  e = 1: 8-connectivity.
 __global__ __launch_bounds__(kCcThreads) void cc_union_kernel(MaskSet A, const CcInst* __restrict__ insts, int n, int frame, int words,
-                                                              CcScan base, int* parent, int e) {
+                                                              Scanned base, int* parent, int e) {
   const int g = blockIdx.x * kCcThreads + threadIdx.x;
   if (g >= words) return;
   const CcAt at = cc_decode<false>(insts, n, g);
@@ -220,13 +156,12 @@ __global__ __launch_bounds__(kCcThreads) void cc_flatten_kernel(int* parent, int
 }
 
 // grid ceil((n + 1) / 256), block 256.  comp_ptr [n + 1]: the components before the first run of instance i.
-__global__ __launch_bounds__(kCcThreads) void cc_comp_ptr_kernel(const CcInst* __restrict__ insts, int n, int words, CcScan base, int runs,
-                                                                 CcScan number, int comps_at, long long* __restrict__ comp_ptr) {
+__global__ __launch_bounds__(kCcThreads) void cc_comp_ptr_kernel(const CcInst* __restrict__ insts, int n, int words, Scanned base, Scanned number,
+                                                                 long long* __restrict__ comp_ptr) {
   const int i = blockIdx.x * kCcThreads + threadIdx.x;
   if (i > n) return;
   const int w0 = i < n ? insts[i].word0 : words;
-  const int run0 = w0 < words ? base.at(w0) : runs;
-  comp_ptr[i] = run0 < runs ? number.at(run0) : number.tile[comps_at];
+  comp_ptr[i] = number.upto(base.upto(w0));
 }
 
 // The table of the components on the device.
@@ -249,7 +184,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_table_init_kernel(CcTable t, lo
 // grid ceil(words / 256), block 256 (frame = 0 views: the masks themselves).  One thread per word takes the runs that START in it
 // and walks each to its end through the words that follow: four atomics per run, not per word of it.
 __global__ __launch_bounds__(kCcThreads) void cc_table_kernel(MaskSet A, const CcInst* __restrict__ insts, int n, int words,
-                                                              CcScan base, const int* __restrict__ parent, CcScan number, CcTable t) {
+                                                              Scanned base, const int* __restrict__ parent, Scanned number, CcTable t) {
   const int g = blockIdx.x * kCcThreads + threadIdx.x;
   if (g >= words) return;
   const CcAt at = cc_decode<false>(insts, n, g);
@@ -318,7 +253,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_rank_kernel(const long long* __
 
 // grid ceil(words / 256), block 256.  out: the words at the input's places; areas [n] are added to.
 __global__ __launch_bounds__(kCcThreads) void cc_select_kernel(MaskSet A, const CcInst* __restrict__ insts, int n, int words,
-                                                               CcScan base, const int* __restrict__ parent, CcScan number,
+                                                               Scanned base, const int* __restrict__ parent, Scanned number,
                                                                const long long* __restrict__ comp_ptr,
                                                                const unsigned long long* __restrict__ area, const u64* __restrict__ thr,
                                                                long long min_area, u64* __restrict__ out,
@@ -352,7 +287,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_select_kernel(MaskSet A, const 
 // grid ceil(real words / 256), block 256.  The labelling ran on the frame = 1 views; the frame's component is the one of the
 // instance's first run.  out as cc_select_kernel's.
 __global__ __launch_bounds__(kCcThreads) void cc_fill_kernel(MaskSet A, const CcInst* __restrict__ insts, int n, int real_words,
-                                                             CcScan base, const int* __restrict__ parent, u64* __restrict__ out,
+                                                             Scanned base, const int* __restrict__ parent, u64* __restrict__ out,
                                                              unsigned long long* __restrict__ out_area) {
   const int g = blockIdx.x * kCcThreads + threadIdx.x;
   const bool live = g < real_words;
@@ -384,7 +319,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_fill_kernel(MaskSet A, const Cc
 
 // grid ceil(out words / 256), block 256.  One instance per component: oword [C + 1] the first word of each in `out`, source [C]
 // its instance; box and root from the table.
-__global__ __launch_bounds__(kCcThreads) void cc_split_kernel(MaskSet A, const CcInst* __restrict__ insts, CcScan base,
+__global__ __launch_bounds__(kCcThreads) void cc_split_kernel(MaskSet A, const CcInst* __restrict__ insts, Scanned base,
                                                               const int* __restrict__ parent, CcTable t, long long comps,
                                                               const long long* __restrict__ oword, const int* __restrict__ source,
                                                               long long out_words, u64* __restrict__ out) {
@@ -429,7 +364,6 @@ DevArena g_cc_runs[16], g_cc_comps[16];
 CallTimer g_cc_timer;
 
 inline int cc_blocks(long long items) { return (int)((items + kCcThreads - 1) / kCcThreads); }
-inline int cc_tiles(long long items) { return (int)((items + kCcTile - 1) / kCcTile); }
 
 // The labelling of one set: what the host knows before the first launch, the buffers, the launch sequence.
 struct CcJob {
@@ -453,8 +387,7 @@ struct CcJob {
   long long* d_oword = nullptr;
   int* d_source = nullptr;
 
-  CcScan base() const { return {d_cnt, d_tile}; }
-  CcScan number() const { return {d_flag, d_tile2}; }
+  Scanned base = {}, number = {};     // the scans of d_cnt over the words and of d_flag over the runs, once launched
 
   // The checks of every entry, before anything is launched.  ordered: the rows must stand in order without overlap.
   int prepare(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n_in, int connectivity, int frame_in,
@@ -494,7 +427,7 @@ struct CcJob {
     set.take(l);
     d_insts = l.take<CcInst>((size_t)n + 1);
     d_cnt = l.take<int>(words);
-    d_tile = l.take<int>((size_t)cc_tiles(words) + 1);
+    d_tile = l.take<int>((size_t)scan_tiles(words) + 1);
     d_comp_ptr = l.take<long long>((size_t)n + 1);
   }
 
@@ -505,17 +438,16 @@ struct CcJob {
     MNC_HIP_TRY(set.upload(hs));
     MNC_HIP_TRY(hs.up(d_insts, insts.data(), insts.size() * sizeof(CcInst)));
     hipLaunchKernelGGL(cc_count_kernel, dim3(cc_blocks(words)), dim3(kCcThreads), 0, s, set.view(), d_insts, n, frame, words, d_cnt);
-    hipLaunchKernelGGL(cc_scan_tiles_kernel, dim3(cc_tiles(words)), dim3(kCcThreads), 0, s, d_cnt, words, d_tile);
-    hipLaunchKernelGGL(cc_scan_top_kernel, dim3(1), dim3(kCcThreads), 0, s, d_tile, cc_tiles(words));
+    base = scan_launch(s, d_cnt, words, d_tile);
     MNC_HIP_TRY(hipGetLastError());
-    MNC_HIP_TRY(hs.down(&runs, d_tile + cc_tiles(words), sizeof(int)));
+    MNC_HIP_TRY(hs.down(&runs, d_tile + base.tiles, sizeof(int)));
     MNC_HIP_TRY(hs.sync());
     comps = 0;
     if (runs <= 0) return MNC_OK;                        // every mask is empty: comp_ptr stays 0
     auto layout = [&](WsLayout l) {
       d_parent = l.take<int>(runs);
       d_flag = l.take<int>(runs);
-      d_tile2 = l.take<int>((size_t)cc_tiles(runs) + 1);
+      d_tile2 = l.take<int>((size_t)scan_tiles(runs) + 1);
       return l.bytes();
     };
     const size_t need = layout(WsLayout());
@@ -523,13 +455,11 @@ struct CcJob {
     if (rc) return rc;
     layout(WsLayout(g_cc_runs[device].p));
     hipLaunchKernelGGL(cc_init_kernel, dim3(cc_blocks(runs)), dim3(kCcThreads), 0, s, d_parent, runs);
-    hipLaunchKernelGGL(cc_union_kernel, dim3(cc_blocks(words)), dim3(kCcThreads), 0, s, set.view(), d_insts, n, frame, words, base(), d_parent, e);
+    hipLaunchKernelGGL(cc_union_kernel, dim3(cc_blocks(words)), dim3(kCcThreads), 0, s, set.view(), d_insts, n, frame, words, base, d_parent, e);
     hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_blocks(runs)), dim3(kCcThreads), 0, s, d_parent, runs, d_flag);
     if (want_comps) {
-      hipLaunchKernelGGL(cc_scan_tiles_kernel, dim3(cc_tiles(runs)), dim3(kCcThreads), 0, s, d_flag, runs, d_tile2);
-      hipLaunchKernelGGL(cc_scan_top_kernel, dim3(1), dim3(kCcThreads), 0, s, d_tile2, cc_tiles(runs));
-      hipLaunchKernelGGL(cc_comp_ptr_kernel, dim3(cc_blocks(n + 1)), dim3(kCcThreads), 0, s, d_insts, n, words, base(), runs, number(),
-                         cc_tiles(runs), d_comp_ptr);
+      number = scan_launch(s, d_flag, runs, d_tile2);
+      hipLaunchKernelGGL(cc_comp_ptr_kernel, dim3(cc_blocks(n + 1)), dim3(kCcThreads), 0, s, d_insts, n, words, base, number, d_comp_ptr);
     }
     MNC_HIP_TRY(hipGetLastError());
     if (want_comps) {
@@ -557,8 +487,8 @@ struct CcJob {
     if (rc) return rc;
     layout(WsLayout(g_cc_comps[device].p));
     hipLaunchKernelGGL(cc_table_init_kernel, dim3(cc_blocks(comps)), dim3(kCcThreads), 0, hs.stream, table, comps);
-    hipLaunchKernelGGL(cc_table_kernel, dim3(cc_blocks(words)), dim3(kCcThreads), 0, hs.stream, set.view(), d_insts, n, words, base(),
-                       d_parent, number(), table);
+    hipLaunchKernelGGL(cc_table_kernel, dim3(cc_blocks(words)), dim3(kCcThreads), 0, hs.stream, set.view(), d_insts, n, words, base,
+                       d_parent, number, table);
     MNC_HIP_TRY(hipGetLastError());
     return MNC_OK;
   }
@@ -612,13 +542,13 @@ int cc_rewrite(CcJob& job, const int* bounds, const long long* offsets, const vo
     MNC_HIP_TRY(hipMemsetAsync(d_out, 0, job.set.used, s));
   } else if (fill) {
     hipLaunchKernelGGL(cc_fill_kernel, dim3(cc_blocks(job.real_words)), dim3(kCcThreads), 0, s, job.set.view(), job.d_insts, n,
-                       job.real_words, job.base(), job.d_parent, d_out, d_area);
+                       job.real_words, job.base, job.d_parent, d_out, d_area);
   } else {
     rc = job.make_table(hs, false);
     if (rc) return rc;
     hipLaunchKernelGGL(cc_rank_kernel, dim3(n), dim3(kCcThreads), 0, s, job.d_comp_ptr, job.table.area, keep, job.d_thr);
     hipLaunchKernelGGL(cc_select_kernel, dim3(cc_blocks(job.words)), dim3(kCcThreads), 0, s, job.set.view(), job.d_insts, n, job.words,
-                       job.base(), job.d_parent, job.number(), job.d_comp_ptr, job.table.area, job.d_thr, (long long)min_area, d_out,
+                       job.base, job.d_parent, job.number, job.d_comp_ptr, job.table.area, job.d_thr, (long long)min_area, d_out,
                        d_area);
   }
   span.end(s);
@@ -755,7 +685,7 @@ int mnc_mask_split(const int* bounds, const long long* offsets, const void* bits
   if (rc) return rc;
   MNC_HIP_TRY(hs.up(job.d_oword, oword.data(), (C + 1) * 8));
   MNC_HIP_TRY(hs.up(job.d_source, source.data(), C * 4));
-  hipLaunchKernelGGL(cc_split_kernel, dim3(cc_blocks(at)), dim3(kCcThreads), 0, hs.stream, job.set.view(), job.d_insts, job.base(),
+  hipLaunchKernelGGL(cc_split_kernel, dim3(cc_blocks(at)), dim3(kCcThreads), 0, hs.stream, job.set.view(), job.d_insts, job.base,
                      job.d_parent, job.table, (long long)C, job.d_oword, job.d_source, at, (u64*)d_out.p);
   span.end(hs.stream);
   MNC_HIP_TRY(hipGetLastError());

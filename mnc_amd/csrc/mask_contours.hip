@@ -5,8 +5,8 @@
 // point.  The point words of a set are numbered in raster order, instance after instance (at most 2^25 of them).
 //   ct_count_kernel   one thread per point word: the edges that leave its points (ct_edges: four bit expressions of the pixel words
 //                     above and below and their carries), counted; the total of the set as a 64-bit sum.
-//   ct_scan_*_kernel  the exclusive prefix of the counts: in tiles of 1024, then over the tiles.  An edge's id is the prefix at its
-//                     word + the edges below it in the word (ct_edge_id): ids are in the order instance, tail y, tail x, direction.
+//   scan_launch       (scan.hip) the exclusive prefix of the counts: in tiles of 1024, then over the tiles.  An edge's id is the prefix at
+//                     its word + the edges below it in the word (ct_edge_id): ids are in the order instance, tail y, tail x, direction.
 //                     The total E is read back: it sizes the edge buffers and the number of rounds, ceil(log2(E)).
 //   ct_succ_kernel    one thread per point word: succ[e] of its edges (ct_successor), their tail and direction, and at the
 //                     successor whether it turns (= its tail is a vertex).  succ is a permutation: every slot is written once.
@@ -31,6 +31,7 @@
 
 #include "mask_contour.h"
 #include "mask_set.h"
+#include "scan.h"
 
 namespace mnc {
 
@@ -38,7 +39,6 @@ constexpr int kCtThreads = 256;
 constexpr int kCtMaxN = 2048;                   // instances of one call
 constexpr long long kCtMaxWords = 1ll << 25;    // point words of one call
 constexpr long long kCtMaxEdges = 1ll << 30;    // edges of one call: ids, ranks and vertex slots are ints
-constexpr int kCtTile = 1024;                   // entries of one scan tile: 4 per thread
 
 // The point rows of one instance: what the host adds to the set's own table (MaskSet::info).
 struct CtInst {
@@ -47,16 +47,10 @@ struct CtInst {
 };
 
 // One instance as a thread sees it; the G of mask_contour.h:ct_successor.
-struct CtScan {
-  const int* in_tile;
-  const int* tile;
-  __device__ __forceinline__ int at(int k) const { return in_tile[k] + tile[k / kCtTile]; }
-};
-
 struct CtGrid {
   int w, h, rs, vs, word0;
   const u64* rows;
-  CtScan ids;
+  Scanned ids;
   // pixel word j of pixel row y and the pixel before it; 0 outside
   __device__ __forceinline__ void row(int y, int j, u64* v, u64* carry) const {
     *v = 0ull; *carry = 0ull;
@@ -79,30 +73,17 @@ struct CtAt {
 };
 
 // The instance, point row and word of point word g: the last instance that begins at or before g (one without words begins where
-// the next does).  At most 11 turns: n <= 2048.
+// the next does).
 __device__ __forceinline__ CtAt ct_decode(const CtInst* __restrict__ insts, int n, int g) {
-  int lo = 0, hi = n - 1;
-  for (int turn = 0; turn < 12 && lo < hi; ++turn) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (insts[mid].word0 <= g) lo = mid; else hi = mid - 1;
-  }
+  const int lo = mask_owner<&CtInst::word0>(insts, n, g);
   const int local = g - insts[lo].word0;
   return {lo, local / insts[lo].vs, local % insts[lo].vs};
 }
 
-__device__ __forceinline__ CtGrid ct_grid(const MaskSet& A, const CtInst* __restrict__ insts, int i, CtScan ids) {
+__device__ __forceinline__ CtGrid ct_grid(const MaskSet& A, const CtInst* __restrict__ insts, int i, Scanned ids) {
   const mnc_mask_info s = A.info[i];
   const int w = s.x2 - s.x1 + 1;
   return {w, s.y2 - s.y1 + 1, mask_strips(w), insts[i].vs, insts[i].word0, A.bits + s.offset / 8, ids};
-}
-
-__device__ __forceinline__ int ct_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // grid ceil(words / 256), block 256.  cnt [words]; *total += the edges of the set, one atomic per wave.
@@ -112,57 +93,13 @@ __global__ __launch_bounds__(kCtThreads) void ct_count_kernel(MaskSet A, const C
   int c = 0;
   if (g < words) {
     const CtAt at = ct_decode(insts, n, g);
-    c = ct_count(ct_grid(A, insts, at.i, {nullptr, nullptr}).edges(at.y, at.j));
+    c = ct_count(ct_grid(A, insts, at.i, Scanned{}).edges(at.y, at.j));
     cnt[g] = c;
   }
   int sum = c;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
   if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, (unsigned long long)sum);
-}
-
-// The two-level scan of mask_components.hip, whose kernels are local to that translation unit.
-// grid ceil(count / 1024), block 256.  a [count] -> its exclusive prefix inside the tile; tile[blockIdx.x] = the tile's sum.
-__global__ __launch_bounds__(kCtThreads) void ct_scan_tiles_kernel(int* __restrict__ a, int count, int* __restrict__ tile) {
-  __shared__ int s_wave[kCtThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long k0 = (long long)blockIdx.x * kCtTile + threadIdx.x * 4;
-  const int v0 = k0 < count ? a[k0] : 0, v1 = k0 + 1 < count ? a[k0 + 1] : 0;
-  const int v2 = k0 + 2 < count ? a[k0 + 2] : 0, v3 = k0 + 3 < count ? a[k0 + 3] : 0;
-  const int sum = v0 + v1 + v2 + v3;
-  const int incl = ct_wave_incl_scan(sum, lane);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - sum;
-  for (int k = 0; k < wave; ++k) before += s_wave[k];
-  if (k0 < count) a[k0] = before;
-  if (k0 + 1 < count) a[k0 + 1] = before + v0;
-  if (k0 + 2 < count) a[k0 + 2] = before + v0 + v1;
-  if (k0 + 3 < count) a[k0 + 3] = before + v0 + v1 + v2;
-  if (threadIdx.x == kCtThreads - 1) tile[blockIdx.x] = before + sum;
-}
-
-// grid 1, block 256.  tile [tiles] -> its exclusive prefix; tile[tiles] = the total.
-__global__ __launch_bounds__(kCtThreads) void ct_scan_top_kernel(int* __restrict__ tile, int tiles) {
-  __shared__ int s_wave[kCtThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int t0 = 0; t0 < tiles; t0 += kCtThreads) {
-    const int t = t0 + threadIdx.x;
-    const int v = t < tiles ? tile[t] : 0;
-    const int incl = ct_wave_incl_scan(v, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = incl - v, all = 0;
-    for (int k = 0; k < kCtThreads / 64; ++k) {
-      if (k < wave) before += s_wave[k];
-      all += s_wave[k];
-    }
-    if (t < tiles) tile[t] = base + before;
-    base += all;
-    __syncthreads();                                     // s_wave is written again
-  }
-  if (threadIdx.x == 0) tile[tiles] = base;
 }
 
 // What is known of every edge once its word has been visited.
@@ -175,7 +112,7 @@ struct CtEdgeInfo {
 };
 
 // grid ceil(words / 256), block 256.  lead0[e] = e and next0[e] = succ[e]: the state before the first round of ct_min_kernel.
-__global__ __launch_bounds__(kCtThreads) void ct_succ_kernel(MaskSet A, const CtInst* __restrict__ insts, int n, int words, CtScan ids,
+__global__ __launch_bounds__(kCtThreads) void ct_succ_kernel(MaskSet A, const CtInst* __restrict__ insts, int n, int words, Scanned ids,
                                                              int eight, int edges, CtEdgeInfo info, int* __restrict__ lead0,
                                                              int* __restrict__ next0) {
   const int g = blockIdx.x * kCtThreads + threadIdx.x;
@@ -250,18 +187,17 @@ __global__ __launch_bounds__(kCtThreads) void ct_heads_kernel(const int* __restr
 }
 
 // grid ceil((n + 1) / 256), block 256.  loop_ptr [n + 1]: the loops before the first edge of instance i.
-__global__ __launch_bounds__(kCtThreads) void ct_loop_ptr_kernel(const CtInst* __restrict__ insts, int n, int words, CtScan ids, int edges,
-                                                                 CtScan number, int loops_at, long long* __restrict__ loop_ptr) {
+__global__ __launch_bounds__(kCtThreads) void ct_loop_ptr_kernel(const CtInst* __restrict__ insts, int n, int words, Scanned ids,
+                                                                 Scanned number, long long* __restrict__ loop_ptr) {
   const int i = blockIdx.x * kCtThreads + threadIdx.x;
   if (i > n) return;
   const int w0 = i < n ? insts[i].word0 : words;
-  const int e0 = w0 < words ? ids.at(w0) : edges;
-  loop_ptr[i] = e0 < edges ? number.at(e0) : number.tile[loops_at];
+  loop_ptr[i] = number.upto(ids.upto(w0));
 }
 
 // grid ceil(E / 256), block 256.  area [L] is zero before.
 __global__ __launch_bounds__(kCtThreads) void ct_write_kernel(CtEdgeInfo info, const int* __restrict__ lead, const int* __restrict__ rank,
-                                                              int edges, CtScan number, CtScan vbase, int verts,
+                                                              int edges, Scanned number, Scanned vbase, int verts,
                                                               long long* __restrict__ vert_ptr, unsigned long long* __restrict__ area,
                                                               int* __restrict__ xy) {
   const int e = blockIdx.x * kCtThreads + threadIdx.x;
@@ -291,7 +227,6 @@ DevArena g_ct_edges[16], g_ct_out[16];
 CallTimer g_ct_timer;
 
 inline int ct_blocks(long long items) { return (int)((items + kCtThreads - 1) / kCtThreads); }
-inline int ct_tiles(long long items) { return (int)((items + kCtTile - 1) / kCtTile); }
 
 }  // namespace
 
@@ -335,7 +270,7 @@ int mnc_mask_contours(const int* bounds, const long long* offsets, const void* b
     set.take(l);
     d_insts = l.take<CtInst>((size_t)n + 1);
     d_cnt = l.take<int>(words);
-    d_tile = l.take<int>((size_t)ct_tiles(words) + 1);
+    d_tile = l.take<int>((size_t)scan_tiles(words) + 1);
     d_total = l.take<unsigned long long>(1);
     d_loop_ptr = l.take<long long>((size_t)n + 1);
     return l.bytes();
@@ -352,8 +287,7 @@ int mnc_mask_contours(const int* bounds, const long long* offsets, const void* b
   MNC_HIP_TRY(hipMemsetAsync(d_total, 0, 8, s));
   const MaskSet A = set.view();
   hipLaunchKernelGGL(ct_count_kernel, dim3(ct_blocks(words)), dim3(kCtThreads), 0, s, A, d_insts, n, words, d_cnt, d_total);
-  hipLaunchKernelGGL(ct_scan_tiles_kernel, dim3(ct_tiles(words)), dim3(kCtThreads), 0, s, d_cnt, words, d_tile);
-  hipLaunchKernelGGL(ct_scan_top_kernel, dim3(1), dim3(kCtThreads), 0, s, d_tile, ct_tiles(words));
+  const Scanned ids = scan_launch(s, d_cnt, words, d_tile);
   MNC_HIP_TRY(hipGetLastError());
   unsigned long long total = 0;
   MNC_HIP_TRY(hs.down(&total, d_total, 8));
@@ -385,15 +319,14 @@ int mnc_mask_contours(const int* bounds, const long long* offsets, const void* b
     }
     d_flag = l.take<int>(E);
     d_vcnt = l.take<int>(E);
-    d_tile2 = l.take<int>((size_t)ct_tiles(E) + 1);
-    d_tile3 = l.take<int>((size_t)ct_tiles(E) + 1);
+    d_tile2 = l.take<int>((size_t)scan_tiles(E) + 1);
+    d_tile3 = l.take<int>((size_t)scan_tiles(E) + 1);
     return l.bytes();
   };
   size_t need = edge_layout(WsLayout());
   rc = arena_ensure(&g_ct_edges[device_id], need, (need >> 1) + 4096, "contour edge buffers", s);
   if (rc) return rc;
   edge_layout(WsLayout(g_ct_edges[device_id].p));
-  const CtScan ids = {d_cnt, d_tile}, number = {d_flag, d_tile2}, vbase = {d_vcnt, d_tile3};
   const dim3 per_edge(ct_blocks(E)), block(kCtThreads);
   hipLaunchKernelGGL(ct_succ_kernel, dim3(ct_blocks(words)), block, 0, s, A, d_insts, n, words, ids, eight, E, info, d_lead[0], d_next[0]);
   for (int k = 0; k < rounds; ++k)
@@ -404,15 +337,12 @@ int mnc_mask_contours(const int* bounds, const long long* offsets, const void* b
     hipLaunchKernelGGL(ct_rank_kernel, per_edge, block, 0, s, d_rank[k & 1], d_next[k & 1], E, d_rank[~k & 1], d_next[~k & 1]);
   const int* rank = d_rank[rounds & 1];
   hipLaunchKernelGGL(ct_heads_kernel, per_edge, block, 0, s, lead, rank, E, d_flag, d_vcnt);
-  hipLaunchKernelGGL(ct_scan_tiles_kernel, dim3(ct_tiles(E)), block, 0, s, d_flag, E, d_tile2);
-  hipLaunchKernelGGL(ct_scan_top_kernel, dim3(1), block, 0, s, d_tile2, ct_tiles(E));
-  hipLaunchKernelGGL(ct_scan_tiles_kernel, dim3(ct_tiles(E)), block, 0, s, d_vcnt, E, d_tile3);
-  hipLaunchKernelGGL(ct_scan_top_kernel, dim3(1), block, 0, s, d_tile3, ct_tiles(E));
-  hipLaunchKernelGGL(ct_loop_ptr_kernel, dim3(ct_blocks(n + 1)), block, 0, s, d_insts, n, words, ids, E, number, ct_tiles(E), d_loop_ptr);
+  const Scanned number = scan_launch(s, d_flag, E, d_tile2), vbase = scan_launch(s, d_vcnt, E, d_tile3);
+  hipLaunchKernelGGL(ct_loop_ptr_kernel, dim3(ct_blocks(n + 1)), block, 0, s, d_insts, n, words, ids, number, d_loop_ptr);
   MNC_HIP_TRY(hipGetLastError());
   int V = 0;
   MNC_HIP_TRY(hs.down(loop_ptr, d_loop_ptr, ((size_t)n + 1) * 8));
-  MNC_HIP_TRY(hs.down(&V, d_tile3 + ct_tiles(E), sizeof(int)));
+  MNC_HIP_TRY(hs.down(&V, d_tile3 + vbase.tiles, sizeof(int)));
   MNC_HIP_TRY(hs.sync());
   const size_t L = (size_t)loop_ptr[n];
   *n_loops = L;

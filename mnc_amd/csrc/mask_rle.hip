@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "mask_set.h"
+#include "scan.h"
 
 namespace mnc {
 
@@ -82,15 +83,6 @@ __device__ __forceinline__ bool rle_pixel(const RleGeom& g, int x, int y) {
   if (x < g.ax || x > g.bx || y < g.ay || y > g.by) return false;
   const int dx = x - g.x1;
   return (g.rows[(long long)(y - g.y1) * g.sw + (dx >> 6)] >> (dx & 63)) & 1ull;
-}
-
-__device__ __forceinline__ int rle_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // grid (ceil(strips / 4), cap), block 256: wave = one (instance blockIdx.y, strip).  cols [cap][stride]: kEmit = 0 stores the
@@ -153,7 +145,7 @@ __global__ __launch_bounds__(64) void rle_scan_columns_kernel(MaskSet A, int cap
   for (int k0 = 0; k0 < ncols; k0 += 64) {
     const int k = k0 + lane;
     const int v = k < ncols ? c[k] : 0;
-    const int incl = rle_wave_incl_scan(v, lane);
+    const int incl = wave_incl_scan(v, lane);
     if (k < ncols) c[k] = base + incl - v;
     base += __shfl(incl, 63);
   }
@@ -177,12 +169,7 @@ __global__ __launch_bounds__(64) void rle_scan_runs_kernel(MaskSet A, int cap, c
   long long base = 0;
   for (int i0 = 0; i0 <= cap; i0 += 64) {
     const int i = i0 + lane;
-    long long v = i < n ? (long long)sums[i] + 1 : 0, incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
+    const long long v = i < n ? (long long)sums[i] + 1 : 0, incl = wave_incl_scan(v, lane);
     if (i <= cap) run_ptr[i] = base + incl - v;
     base += __shfl(incl, 63);
   }

@@ -1,5 +1,5 @@
 // One set of packed instance masks (include/mnc_hip.h n5), as the mask files share it: inst_masks.hip, mask_overlaps.hip, mask_rle.hip,
-// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip.  Internal to libmnc_hip.so; nothing else includes it.
+// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip, mask_contours.hip.  Internal to libmnc_hip.so; nothing else includes it.
 #pragma once
 #include <vector>
 
@@ -47,6 +47,19 @@ __device__ __forceinline__ u64 mask_word_at(const u64* __restrict__ row, int bit
   u64 v = mask_word(row, q, strips, w);
   if (s) v = (v >> s) | (mask_word(row, q + 1, strips, w) << (64 - s));
   return v;
+}
+
+// Where the words of a set are numbered in raster order, instance after instance, and insts[i].*kFirst is the first word of
+// instance i: the last of the n instances whose first word is at or before g -- the one that holds word g (an instance without
+// words begins where the next does).  At most 11 turns: the entries that number words this way take n <= 2048.
+template <auto kFirst, class Inst>
+__device__ __forceinline__ int mask_owner(const Inst* __restrict__ insts, int n, int g) {
+  int lo = 0, hi = n - 1;
+  for (int turn = 0; turn < 12 && lo < hi; ++turn) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (insts[mid].*kFirst <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
 }
 
 // float32 -> an unsigned key with the floats' order (-0.0 counts as 0.0, as it does for numpy's comparison).  A NaN, which the

@@ -3,7 +3,8 @@ sets of tests/mask_contours_inputs.py, and general loops where csrc/contour_simp
 one of equal vertices, staircases whose vertex counts stand around the 64 of a wave (62, 64, 66), the 256 threads of a workgroup
 (254, 256, 258), a kilo (1022, 1024, 1026: one scan tile) and the 4096 vertices that are staged in LDS (4094, 4096, 4098), one of
 40 000 vertices, a comb whose recursion is hundreds deep, 1000 random loops on a 4 x 4 lattice (ties, repeated vertices, the
-L == 0 and clamped branches) and the loop whose products need more than 64 bits.  Every result of the statement
+L == 0 and clamped branches), the loop whose products need more than 64 bits, and 103 242 loops of 0 to 5 vertices whose 263 173
+kept flags fill 258 scan tiles (more than the 256 that the scan over the tiles takes in one pass).  Every result of the statement
 (mnc_amd.contours.simplify_numpy) is computed once per key and left unchanged."""
 import os
 import sys
@@ -69,6 +70,23 @@ def ties():
     return [rng.integers(0, 4, (int(k), 2)).tolist() for k in rng.integers(3, 41, 1000)]
 
 
+TINY_VERTS = 256 * 1024 + 1025
+
+
+def tiny():
+    """Loops of 0 to 3 random vertices on a 50 x 50 lattice (7 in 10) or of one lattice point five times (kept as three), until
+    there are more than TINY_VERTS vertices: 258 scan tiles, kept flags that are not uniform."""
+    rng = np.random.default_rng(5)
+    loops, verts = [], 0
+    while verts <= TINY_VERTS:
+        if rng.random() < 0.7:
+            loops.append(rng.integers(0, 50, (int(rng.integers(0, 4)), 2)).tolist())
+        else:
+            loops.append([rng.integers(0, 50, 2).tolist()] * 5)
+        verts += len(loops[-1])
+    return loops
+
+
 WIDE = [(-2 ** 24, 0), (0, 8), (2 ** 24, 0), (0, -8)]
 
 GENERAL = {
@@ -78,6 +96,7 @@ GENERAL = {
     "comb": lambda: CT.contours_numpy(comb(), 8),
     "ties": lambda: as_contours(ties()),
     "wide": lambda: as_contours([WIDE]),
+    "tiny": lambda: as_contours(tiny()),
 }
 
 

@@ -1,7 +1,8 @@
 """Inputs shared by tests/test_mask_components_host.py and tests/test_gpu_mask_components.py: packed mask sets placed where
 csrc/mask_components.hip can go wrong -- widths around the 64-column word with many runs and merges, the word seam, the checkerboard
 (the run maximum), a spiral (the longest parent chains), a comb (every merge at the end), rings, a C-shape, holes that touch the box
-edge, nested rings, full and empty masks, instances without rows, dirty padding, 300 small instances, one set at real size.  Every
+edge, nested rings, full and empty masks, instances without rows, dirty padding, 300 small instances, one set at real size -- and, outside SETS (the GPU tests name the operations they run on it), `stripes`: one instance
+whose runs, roots and boundary edges fill more than the 256 scan tiles that the scan over the tiles takes in one pass.  Every
 reference (the numpy statements of mnc_amd.components) is computed once per key and shared."""
 import os
 import sys
@@ -147,6 +148,15 @@ def real():
     return instance_masks_numpy(boxes, np.array(pred["masks"][:10]), H, W, clip=False, binarize_thresh=0.4, classes=pred["cls_name"][:10])
 
 
+def stripes():
+    """520 x 1200, every other column set, one pixel in 100 of them cleared: 308 891 runs (302 scan tiles) in 3666 components at
+    either connectivity, whose roots lie in all of the tiles; 625 114 boundary edges (611 tiles)."""
+    m = np.zeros((520, 1200), bool)
+    m[:, ::2] = True
+    m[np.random.default_rng(1500).random(m.shape) < 0.01] = False
+    return _place([m])
+
+
 SETS = {"widths": widths, "widths_dirty": lambda: widths(True), "seam": seam, "checker": checker, "spiral": spiral, "comb": comb,
         "holes": holes, "holes_dirty": lambda: holes(True), "plain": plain, "many": many, "real": real}
 
@@ -156,7 +166,7 @@ _SETS, _REFERENCE = {}, {}
 def get(name):
     """The set of that name, made once."""
     if name not in _SETS:
-        _SETS[name] = SETS[name]()
+        _SETS[name] = stripes() if name == "stripes" else SETS[name]()
     return _SETS[name]
 
 

@@ -85,6 +85,14 @@ def test_one_loop_of_40000_vertices_past_any_lds_stage(q):
     equals_statement("long", q)
 
 
+@pytest.mark.parametrize("q", (0, 16))
+def test_tiny_loops_whose_flags_fill_more_than_256_scan_tiles(q):
+    """263 173 vertices are 258 tiles of 1024: the scan over the tiles takes a second pass of 256."""
+    c, want = SI.general("tiny"), SI.general_reference("tiny", q)
+    assert len(c.xy) == 263173 > 257 * 1024 and len(want.xy) == 201425
+    assert SI.same_simplified(c.simplify(q / 16.0), want)
+
+
 def test_the_comb_whose_recursion_is_hundreds_deep():
     equals_statement("comb", 16)
 

@@ -62,6 +62,20 @@ def test_split_equals_the_statement(name, connectivity):
     assert CI.same_masks(got, want)
 
 
+def test_stripes_whose_runs_fill_more_than_256_scan_tiles():
+    """308 891 runs are 302 tiles of 1024: the scan over the tiles takes a second pass of 256, for the words' counts (the run ids)
+    and for the root flags (the component numbers) alike."""
+    pm = CI.get("stripes")
+    for connectivity in CI.CONNECTIVITIES:
+        want = CI.reference("stripes", "components", connectivity)
+        assert len(want.area) == 3666 and int(pm.areas[0]) > 257 * 1024      # every set pixel is a run
+        assert CI.same_components(CC.components(pm, connectivity), want)
+    assert CI.same_masks(CC.select(pm, 4, 50, 0), CI.reference("stripes", "select", 4, 50, 0))
+    got, source = CC.split(pm, 4)
+    want, want_source = CI.reference("stripes", "split", 4)
+    assert CI.same_array(source, want_source) and CI.same_masks(got, want)
+
+
 def test_real_size_twice_the_same_bytes_and_every_surface_agrees():
     pm = CI.get("real")
     for connectivity in CI.CONNECTIVITIES:

@@ -36,6 +36,15 @@ def test_contours_equal_the_statement(name, connectivity):
     assert TI.same_contours(got, want)
 
 
+@pytest.mark.parametrize("connectivity", TI.CONNECTIVITIES)
+def test_stripes_whose_edges_fill_more_than_256_scan_tiles(connectivity):
+    """625 114 edges are 611 tiles of 1024: the scans of the edge ids, the leader flags and the vertex counts all take more than
+    one pass of 256 over the tiles."""
+    want = TI.reference("stripes", connectivity)
+    assert len(want.area) == 3666 and len(want.xy) == 4 * 3666 and int(np.abs(want.area).sum()) == int(TI.get("stripes").areas[0])
+    assert TI.same_contours(CT.contours(TI.get("stripes"), connectivity), want)
+
+
 def test_real_size_twice_the_same_bytes_and_every_surface_agrees():
     pm = TI.get("real")
     for connectivity in TI.CONNECTIVITIES:

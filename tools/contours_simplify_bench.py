@@ -17,7 +17,7 @@ import numpy as np
 
 from _task_harness import emit, kernels_us, median_ms, parser, voted_instances
 
-LAUNCHES = 5                    # cs_wave, cs_block, cs_scan_tiles, cs_scan_top, cs_write (csrc/contour_simplify.hip: cs_launch)
+LAUNCHES = 5                    # cs_wave, cs_block, scan_tiles, scan_top (csrc/scan.hip), cs_write (csrc/contour_simplify.hip: cs_launch)
 
 HEADING = """tools/contours_simplify_bench.py --iters %d --host-iters %d --epsilon %g on one MI355X: per image, the outlines (connectivity 8) of the
 %d best instances as a host Contours; mnc_amd.contours.simplify_numpy (a sequential Douglas-Peucker per loop in Python integers)
