@@ -800,6 +800,22 @@ MNC_API int mnc_conv3x3_wino4(mnc_ctx* ctx, const float* d_in_c8, const float* d
                               int H, int W, int Cin, int Cout, int relu);
 MNC_API int mnc_conv3x3_wino4_pool(mnc_ctx* ctx, const float* d_in_c8, const float* d_w_packed, const float* d_bias,
                                    float* d_out_pooled_c8, int H, int W, int Cin, int Cout, int relu);
+/* F(4x4, 3x3) unfused (mnc_amd/csrc/conv_wino4_split.hip): input transform c8 -> V[36][tiles][Cin], the 36 transform positions as one
+ * batched InnerProduct launch (mnc_fc_batch's kernel: tile = row, output channel = column, K = Cin) -> M[36][tiles][Cout], output
+ * transform + bias (+ ReLU, _pool: + the following Pooling MAX 2x2/2) -> c8.  For the small 512-channel maps, which the fused kernel
+ * has to cut into K ranges.  Same arithmetic as mnc_conv3x3_wino4 up to the order of the channel sum.  V and M (36/16 floats per
+ * input and output value) live in d_ws, mnc_conv3x3_wino4_split_ws_bytes(H, W, Cin, Cout) bytes of the caller's.  d_w_split from
+ * mnc_pack_conv3x3_wino4_split: Caffe [Cout][Cin][3][3] -> [36][Cout][Cin] floats (G g G^T in double, rounded once).
+ * Cin%32==0, Cout%32==0 (_ws_bytes: 0 for a shape the split form does not take).  _selected: 1 where the context's tuning value
+ * WINO_SPLIT moves this layer of a net to the split form (0 never, 1 the throughput plan's choice, 2 every supported layer) -- every
+ * executor of a graph asks it, so that all of them run the same kernels. */
+MNC_API int mnc_pack_conv3x3_wino4_split(mnc_ctx* ctx, const float* d_oihw, float* d_packed, int Cout, int Cin);
+MNC_API size_t mnc_conv3x3_wino4_split_ws_bytes(int H, int W, int Cin, int Cout);
+MNC_API int mnc_conv3x3_wino4_split_selected(mnc_ctx* ctx, int H, int W, int Cin, int Cout);
+MNC_API int mnc_conv3x3_wino4_split(mnc_ctx* ctx, const float* d_in_c8, const float* d_w_split, const float* d_bias, float* d_out_c8,
+                                    void* d_ws, int H, int W, int Cin, int Cout, int relu);
+MNC_API int mnc_conv3x3_wino4_split_pool(mnc_ctx* ctx, const float* d_in_c8, const float* d_w_split, const float* d_bias,
+                                         float* d_out_pooled_c8, void* d_ws, int H, int W, int Cin, int Cout, int relu);
 /* Pooling MAX 2x2 stride 2 with Caffe's ceil output size (test.prototxt:69-79,...): c8 [C/8][H][W][8] ->
  * [C/8][OH][OW][8], OH = ceil((H-2)/2)+1. */
 MNC_API int mnc_maxpool2_c8(mnc_ctx* ctx, const float* d_in, float* d_out, int C, int H, int W);
@@ -907,6 +923,12 @@ MNC_API int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float
  * bits): every executor of a graph pairs the same layers. */
 MNC_API int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float* d_bias0, float* d_out0, const float* d_a1,
                         const float* d_w1, const float* d_bias1, float* d_out1, int M, int N, int K, int ldc, int act);
+/* B InnerProducts of ONE shape at constant strides in one launch: out_b[M][N] = a_b . w_b^T with a_b = d_a + b * stride_a floats (and
+ * d_w, d_out alike), b = 0 .. B-1; no bias, no activation, K never cut.  Always the eight-wave fp32 LDS-DMA kernel, whatever the
+ * size of one product (the 36 transform positions of mnc_conv3x3_wino4_split).  K%32==0, operands and strides 16-byte aligned.
+ * Every output's K order is that kernel's: the same bits as B calls with B = 1. */
+MNC_API int mnc_fc_batch(mnc_ctx* ctx, const float* d_a, long stride_a, const float* d_w, long stride_w, float* d_out,
+                         long stride_out, int B, int M, int N, int K, int ldc);
 /* InnerProduct on the bf16 matrix pipe with fp32-class accuracy ("bf16x3": every operand split into hi + lo bf16, product =
  * a_lo*b_hi + a_hi*b_lo + a_hi*b_hi, fp32 accumulate; relative error ~1e-5 per product, see mnc_amd/csrc/gemm_x3.hip).
  * d_w_packed comes from mnc_pack_fc_bf16x3: fp32 [N][K] -> stage-major tiles [ceil(N/128)][K/32][128][(hi x8 | lo x8) x 4] bf16,

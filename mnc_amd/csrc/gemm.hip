@@ -523,14 +523,22 @@ __global__ __launch_bounds__(256 * kWM) void fc_mfma_dma_kernel(const float* __r
 // (tn_ counts both; pair_tn = the tiles of one), so 2 x 32 tiles need 4 K ranges instead of 8 to fill the chip: a workgroup's
 // K range is twice as long (prologue and epilogue paid once per 196 instead of 98 stages) and half as many partial sums are
 // written and read back.
-template <int kMT, int ABL = 0, int BUF = 0>
+// BATCH: B products of one shape at constant strides in ONE launch (fc_batch_launch: the 36 transform positions of a Winograd-domain
+// convolution, conv_wino4_split.hip) -- no bias, no activation, no K cut.  The grid is B x tm x tn; the block order is column tile
+// fastest, then row block, then product, so the workgroups of one product are neighbours on one XCD and its two operands (about
+// 1 MB each there) stay in that XCD's L2.  A_0 / Wt_0 / out_0 advance by batch_a / batch_w / batch_o floats per product (splits_
+// carries tm, tm_ carries B).  With drop_last the row blocks are 304 rows apart instead of 320 (608 rows = two blocks of nineteen
+// live sub-tiles each); a block stores only the rows it owns.  The K order of an output is the kernel's one order: a batched launch
+// returns the bits of B launches of one product each.
+template <int kMT, int ABL = 0, int BUF = 0, int BATCH = 0>
 __global__ __launch_bounds__(512) void fc_mfma_dma16_kernel(const float* __restrict__ A_0, const float* __restrict__ Wt_0,
                                                             const float* __restrict__ bias_0, float* __restrict__ out_0,
                                                             float* __restrict__ part_0, int M, int N, int K, int ldc, int kper,
                                                             int act, int fused, int tn_, int splits_, int tm_, int drop_last,
                                                             const float* __restrict__ A_1,
                                                             const float* __restrict__ Wt_1, const float* __restrict__ bias_1,
-                                                            float* __restrict__ out_1, int pair_tn) {
+                                                            float* __restrict__ out_1, int pair_tn, long batch_a,
+                                                            long batch_w, long batch_o) {
   constexpr int kBM = 32 * kMT;
   constexpr int kRows = kBM + kBN;
   constexpr int kNW = 8;
@@ -545,17 +553,19 @@ __global__ __launch_bounds__(512) void fc_mfma_dma16_kernel(const float* __restr
   const int r16 = lane & 15, g4 = lane >> 4;
   int bn, split, bmz;
   xcd_decode(blockIdx.x, tn_, splits_, tm_, bn, split, bmz);
-  const int which = (pair_tn && bn >= pair_tn) ? 1 : 0;             // (block-uniform) which product of a pair this tile belongs to
+  int which = (pair_tn && bn >= pair_tn) ? 1 : 0;                   // (block-uniform) which product of a pair this tile belongs to
   bn -= which * pair_tn;
-  const float* __restrict__ A = which ? A_1 : A_0;
-  const float* __restrict__ Wt = which ? Wt_1 : Wt_0;
+  if (BATCH) { which = bmz; bmz = split; split = 0; }               // (decoded as column tile, row block, product)
+  const float* __restrict__ A = BATCH ? A_0 + which * batch_a : which ? A_1 : A_0;
+  const float* __restrict__ Wt = BATCH ? Wt_0 + which * batch_w : which ? Wt_1 : Wt_0;
   const float* __restrict__ bias = which ? bias_1 : bias_0;
-  float* __restrict__ out = which ? out_1 : out_0;
+  float* __restrict__ out = BATCH ? out_0 + which * batch_o : which ? out_1 : out_0;
   float* __restrict__ part = part_0;                  // K ranges' partial sums: slabs [tile (both products' column tiles)][range]
-  const int n0 = bn * kBN, m0 = bmz * kBM;
+  constexpr int kLive = kBM - 16;                     // BATCH with drop_last: rows a block owns
+  const int n0 = bn * kBN, m0 = bmz * (BATCH && drop_last ? kLive : kBM);
   const int kbeg = split * kper, kend = min(K, kbeg + kper);
   const int nstages = (kend - kbeg) / 32;
-  const int mrows = min(M - m0, kBM);
+  const int mrows = min(M - m0, BATCH && drop_last ? kLive : kBM);
 
   const float* src[kPer];
 #pragma unroll
@@ -688,6 +698,21 @@ __global__ __launch_bounds__(512) void fc_mfma_dma16_kernel(const float* __restr
   }
 
   const bool final_out = fused == 1;
+  if (BATCH) {                                       // the product as it is, the rows this block owns
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int n = n0 + wn * 32 + c * 16 + r16;
+      if (n >= N) continue;
+#pragma unroll
+      for (int i = 0; i < TS; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = wm * TS * 16 + i * 16 + 4 * g4 + e;
+          if (r < mrows) out[(long)(m0 + r) * ldc + n] = acc[i][c][e];
+        }
+    }
+    return;
+  }
   if (fused == 0) {
     // K ranges finished by the reduction launch (fc_reduce_slab_kernel): the accumulators as they sit in registers, [tile][range]
     // [wave][sub-tile i][column half c][lane] x 16 bytes -- one kilobyte per wave instruction (rounds 1-4 stored them row-major:
@@ -912,6 +937,31 @@ __global__ void pack_fc_kernel(const float* __restrict__ in, float* __restrict__
   }
 }
 
+// B products of one shape at constant strides, out_b[M][N] = a_b . w_b^T (b = 0 .. B - 1; no bias, no activation, no K cut), as ONE
+// launch of the eight-wave LDS-DMA kernel: grid B x row blocks x column tiles, one product's workgroups together.  Whatever the
+// shape, below mnc_fc's 2 GFLOP bar too: the caller (conv_wino4_split.hip) knows that 36 such products together are large.  Launch
+// only -- the caller's LaunchScope books it.
+int fc_batch_launch(mnc_ctx* ctx, const float* d_a, long stride_a, const float* d_w, long stride_w, float* d_out, long stride_o, int B,
+                    int M, int N, int K, int ldc) {
+  MNC_REQUIRE(ctx && d_a && d_w && d_out, "fc_batch: null pointer");
+  MNC_REQUIRE(B > 0 && M > 0 && N > 0 && K > 0 && K % kBK == 0 && ldc >= N && stride_a >= 0 && stride_w >= 0 && stride_o >= 0,
+              "fc_batch: unsupported shape B=%d M=%d N=%d K=%d ldc=%d (need K%%32==0)", B, M, N, K, ldc);
+  // (buffer descriptors: 32-bit byte offsets from a workgroup's first row; the strides and bases must keep the 16-byte pieces aligned)
+  MNC_REQUIRE(320.0 * (double)K * 4.0 < 1.8e9 && stride_a % 4 == 0 && stride_w % 4 == 0 &&
+                  ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_w)) & 15) == 0,
+              "fc_batch: operands must be 16-byte aligned, K=%d below the descriptor range", K);
+  // row blocks of 304 rows (the last sub-tile's MFMAs skipped) when that needs no more blocks than 320-row ones: 608 = 2 x 304
+  const int drop = cdiv(M, 304) == cdiv(M, 320) ? 1 : 0;
+  const int tn = cdiv(N, kBN), tm = cdiv(M, drop ? 304 : 320);
+  MNC_REQUIRE((double)B * tn * tm < 2.0e9, "fc_batch: too many workgroups");
+  constexpr int lds = 65536 + (320 + kBN) * 32 * 4;
+  MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 1, 1>>(ctx->device, lds)));
+  hipLaunchKernelGGL((fc_mfma_dma16_kernel<10, 0, 1, 1>), dim3(B * tn * tm), dim3(512), lds, ctx->stream, d_a, d_w, (const float*)nullptr,
+                     d_out, (float*)nullptr, M, N, K, ldc, K, 0, 1, tn, tm, B, drop, (const float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, (float*)nullptr, 0, stride_a, stride_w, stride_o);
+  return MNC_OK;
+}
+
 }  // namespace mnc
 
 using namespace mnc;
@@ -973,7 +1023,7 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
         MNC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL(kern, dim3(tn * splits * tm), dim3(512), lds, ctx->stream, d_a, d_w, d_bias, d_out, part, M, N, K, ldc, kper,
                            act, splits == 1 ? 1 : 0, tn, splits, tm, p.drop, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, (float*)nullptr, 0);
+                           (const float*)nullptr, (float*)nullptr, 0, 0L, 0L, 0L);
       } else if (tune(ctx, T_FC_MFMA16, 1) == 0 || waves == 4 || dabl) {
         launched = true;
         if (dabl == 1) MNC_FC_DMA_LAUNCH(1, 1);      // 1: every copy re-reads stage 0 (L2-hot operands), 3: only the weight copies do
@@ -989,7 +1039,8 @@ int mnc_fc(mnc_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias
         else MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 0>>(ctx->device, lds)));
         hipLaunchKernelGGL((p.buf ? fc_mfma_dma16_kernel<10, 0, 1> : fc_mfma_dma16_kernel<10, 0, 0>), dim3(tn * splits * tm), dim3(512), lds,
                            ctx->stream, d_a, d_w, d_bias, d_out, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, tn, splits,
-                           tm, p.drop, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0);
+                           tm, p.drop, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0, 0L, 0L,
+                           0L);
       }
     }
     else if (mt == 2) MNC_FC_LAUNCH(2, 32, 0);
@@ -1076,7 +1127,7 @@ int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float*
     MNC_HIP_TRY((lds_limit_once<fc_mfma_dma16_kernel<10, 0, 1>>(ctx->device, lds)));
     hipLaunchKernelGGL((fc_mfma_dma16_kernel<10, 0, 1>), dim3(2 * tn * splits * tm), dim3(512), lds, ctx->stream, d_a0, d_w0, d_bias0,
                        d_out0, part, M, N, K, ldc, kper, act, splits == 1 ? 1 : 0, 2 * tn, splits, tm, p.drop, d_a1, d_w1,
-                       d_bias1, d_out1, tn);
+                       d_bias1, d_out1, tn, 0L, 0L, 0L);
     int rc = ls.finish("fc_mfma_dma16_kernel");
     if (rc) return rc;
   }
@@ -1089,6 +1140,15 @@ int mnc_fc_pair(mnc_ctx* ctx, const float* d_a0, const float* d_w0, const float*
     return ls.finish("fc_reduce_slab_kernel");
   }
   return MNC_OK;
+}
+
+int mnc_fc_batch(mnc_ctx* ctx, const float* d_a, long stride_a, const float* d_w, long stride_w, float* d_out, long stride_out,
+                 int B, int M, int N, int K, int ldc) {
+  MNC_REQUIRE(ctx, "mnc_fc_batch: null context");
+  LaunchScope ls(ctx, "fc_batch", 2.0 * B * M * (double)N * K, 4.0 * B * ((double)N * K + (double)M * K + (double)M * N));
+  const int rc = fc_batch_launch(ctx, d_a, stride_a, d_w, stride_w, d_out, stride_out, B, M, N, K, ldc);
+  const int rf = ls.finish("fc_mfma_dma16_kernel");          // (closes the profile record also when the launcher refused the call)
+  return rc ? rc : rf;
 }
 
 int mnc_softmax_rows_ld(mnc_ctx* ctx, const float* d_in, int ld_in, float* d_out, int M, int N) {

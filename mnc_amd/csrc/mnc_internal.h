@@ -308,6 +308,12 @@ void fc_reduce_launch(hipStream_t stream, const float* part, const float* bias, 
                       int act);   // gemm.hip: out = act(sum of the K splits' partial sums + bias), shared by the three FC kernels
 bool fc_reduce_launch_sm(hipStream_t stream, const float* part, const float* bias, float* out, int M, int N, int ldc, int splits,
                          int act, void* sm, int sm_fmt, long sm_rows, long sm_row0);   // + the rows in the next InnerProduct's form
+// gemm.hip: B InnerProducts of one shape at constant strides (floats) in one launch of the eight-wave LDS-DMA kernel; launch only
+int fc_batch_launch(mnc_ctx* ctx, const float* d_a, long stride_a, const float* d_w, long stride_w, float* d_out, long stride_o, int B,
+                    int M, int N, int K, int ldc);
+// conv_wino4_split.hip: can the split form run this layer at all / does this context's WINO_SPLIT value move it there?
+bool wino4_split_supported(int H, int W, int Cin, int Cout);
+bool wino4_split_selected(const mnc_ctx* ctx, int H, int W, int Cin, int Cout);
 bool fc_reduce_pair_launch_sm(hipStream_t stream, const float* part0, const float* part1, const float* bias0, const float* bias1,
                               float* out0, float* out1, int M, int N, int ldc, int splits, int act, void* sm0, void* sm1, int sm_fmt,
                               long sm_rows, bool* sm_done);   // two products' reductions in one launch (gemm.hip)

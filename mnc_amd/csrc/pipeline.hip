@@ -83,6 +83,7 @@ struct mnc_net {
   // device weights
   float* w_c3 = nullptr;                       // conv1_1 [Cout][3][3][3]
   void* w_conv[14] = {nullptr};                // packed conv3x3 weights: trunk 1..12, [13] = rpn_conv_3x3
+  float* w_split[14] = {nullptr};              // fp32 F(4x4): the same layers' weights as [36][Cout][Cin] where WINO_SPLIT may pick the split form
   bool packed_trunk = false;                   // bf16x3 / f16 / bf16 with every trunk layer on the tuned kernel: 2-byte activations
   bool conv_fast[14] = {false};                // tuned 3x3 kernels (Cout % 32 == 0) or the general convolution (reduced widths)
   float* b_conv[14] = {nullptr};               // biases: trunk 0..12 -> [0..12], rpn -> [13]
@@ -97,6 +98,7 @@ struct mnc_net {
   // the result block: [per-class counts: 256 B | the ProposalLayer's row count: 256 B | instance records] -- laid out like the
   // pinned buffer it is copied into, so that an image's results come down in ONE copy
   DevBuf outblk;
+  DevBuf wino_ws;         // V and M of the F(4x4) layers that run in the split form (conv_wino4_split.hip): the largest of them
   DevBuf hwc5;            // conv5_3 pixel-major: made once per image, gathered from by both stages' ROIWarping
   float* records() const { return (float*)((char*)outblk.p + 512); }
   int* counts() const { return (int*)outblk.p; }
@@ -293,6 +295,16 @@ int finalize(mnc_net* n) {
         NET_TRY(mnc_dev_alloc(n->ctx, (size_t)cout * cin * 9 * 4, &n->w_conv[i]));
         NET_TRY(mnc_pack_conv_weights(n->ctx, raw, (float*)n->w_conv[i], cout, cin, 3, 3));
       }
+      // the layers this context's WINO_SPLIT value can move to the split form keep both packed forms (the latency plan and the
+      // maps below one row block of tiles stay on the fused kernel)
+      const int ws = tune(n->ctx, T_WINO_SPLIT, kWinoSplitDefault);
+      if (n->conv_fast[i] && conv_math(c) == 0 && c.winograd == 4 && wino4_split_supported(4, 4, cin, cout) &&
+          (ws == 2 || (ws == 1 && wino4_split_plan_channels(cin, cout)))) {
+        void* u = nullptr;
+        NET_TRY(mnc_dev_alloc(n->ctx, (size_t)36 * cout * cin * 4, &u));
+        n->w_split[i] = (float*)u;
+        NET_TRY(mnc_pack_conv3x3_wino4_split(n->ctx, raw, n->w_split[i], cout, cin));
+      }
       NET_TRY(mnc_dev_free(n->ctx, raw));
     }
     cin = cout;
@@ -351,14 +363,24 @@ int ensure_buffers(mnc_net* n, int H, int W, int OH, int OW) {
   NET_TRY(dev_ensure(n, &n->taps, (size_t)(2 * OW + 2 * OH) * 4));
   NET_TRY(dev_ensure(n, &n->data, (size_t)3 * OH * OW * 4));
   int h = OH, w = OW, pi = 0;
+  size_t split_ws = 0;
+  auto split_need = [&](int i, int hh, int ww, int cin, int cout) {
+    if (n->w_split[i] && wino4_split_selected(n->ctx, hh, ww, cin, cout)) {
+      const size_t b = mnc_conv3x3_wino4_split_ws_bytes(hh, ww, cin, cout);
+      if (b > split_ws) split_ws = b;
+    }
+  };
   for (int i = 0; i < 13; ++i) {
     const int ch = c.trunk_channels[kTrunkStage[i]];
+    if (i > 0) split_need(i, h, w, c.trunk_channels[kTrunkStage[i - 1]], ch);
     NET_TRY(dev_ensure(n, &n->act[i], (size_t)ch * h * w * 4));
     if (kPoolAfter[i]) {
       h = pool_out(h); w = pool_out(w);
       NET_TRY(dev_ensure(n, &n->pooled[pi++], (size_t)ch * h * w * 4));
     }
   }
+  split_need(13, h, w, c.trunk_channels[4], c.rpn_channels);
+  if (split_ws) NET_TRY(dev_ensure(n, &n->wino_ws, split_ws));
   const int A = c.num_anchors;
   if (n->packed_trunk) NET_TRY(dev_ensure(n, &n->act12_pk, (size_t)c.trunk_channels[4] * h * w * 4));
   NET_TRY(dev_ensure(n, &n->hwc5, (size_t)c.trunk_channels[4] * h * w * 4));
@@ -439,6 +461,8 @@ int conv3(mnc_net* n, int i, const float* in, float* out, int h, int w, int cin,
     if (cm == 2) return mnc_conv2d_f16(n->ctx, in, n->w_conv[i], n->b_conv[i], nullptr, out, h, w, cin, cout, 3, 3, 1, 1, 1);
     return mnc_conv2d(n->ctx, in, (const float*)n->w_conv[i], n->b_conv[i], nullptr, out, h, w, cin, cout, 3, 3, 1, 1, 1);
   }
+  if (cm == 0 && c.winograd == 4 && n->w_split[i] && wino4_split_selected(n->ctx, h, w, cin, cout))
+    return mnc_conv3x3_wino4_split(n->ctx, in, n->w_split[i], n->b_conv[i], out, n->wino_ws.p, h, w, cin, cout, 1);
   if (cm == 0 && c.winograd == 4)
     return mnc_conv3x3_wino4(n->ctx, in, (const float*)n->w_conv[i], n->b_conv[i], out, h, w, cin, cout, 1);
   if (cm == 0 && c.winograd)
@@ -495,6 +519,9 @@ int run_trunk(mnc_net* n) {
     if (kPoolAfter[i] && i > 0 && conv_math(c) == 0 && c.winograd && n->conv_fast[i]) {
       // conv + ReLU + MAX 2x2/2 in one kernel (the engine's fused plan; the full-resolution blob is not produced)
       float* p = (float*)n->pooled[pi++].p;
+      if (c.winograd == 4 && n->w_split[i] && wino4_split_selected(ctx, h, w, cin, cout))
+        NET_TRY(mnc_conv3x3_wino4_split_pool(ctx, cur, n->w_split[i], n->b_conv[i], p, n->wino_ws.p, h, w, cin, cout, 1));
+      else
       NET_TRY(c.winograd == 4 ? mnc_conv3x3_wino4_pool(ctx, cur, (const float*)n->w_conv[i], n->b_conv[i], p, h, w, cin, cout, 1)
                               : mnc_conv3x3_wino_pool(ctx, cur, (const float*)n->w_conv[i], n->b_conv[i], p, h, w, cin, cout, 1));
       h = pool_out(h); w = pool_out(w);
@@ -842,6 +869,7 @@ int mnc_net_create_shared(mnc_ctx* ctx, mnc_net* parent, mnc_net** out) {
   n->w_c3 = parent->w_c3;
   for (int i = 0; i < 14; ++i) {
     n->w_conv[i] = parent->w_conv[i];
+    n->w_split[i] = parent->w_split[i];
     n->b_conv[i] = parent->b_conv[i];
     n->conv_fast[i] = parent->conv_fast[i];
   }
@@ -1118,7 +1146,8 @@ int mnc_net_destroy(mnc_net* net) {
   DevBuf* bufs[] = {&net->img, &net->taps, &net->data, &net->rpn_out, &net->rpn_score, &net->rpn_prob, &net->rois,
                     &net->rois_ext, &net->feat14, &net->h_mask, &net->m14, &net->box7, &net->mask7, &net->f6, &net->f6m, &net->join,
                     &net->feat14_sm, &net->box7_sm, &net->mask7_sm, &net->f6_sm, &net->f6m_sm,
-                    &net->heads, &net->boxes, &net->masks, &net->scores, &net->outblk, &net->hwc5, &net->act12_pk};
+                    &net->heads, &net->boxes, &net->masks, &net->scores, &net->outblk, &net->hwc5, &net->act12_pk,
+                    &net->wino_ws};
   for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
   for (auto& b : net->act) if (b.p) (void)hipFree(b.p);
   for (auto& b : net->pooled) if (b.p) (void)hipFree(b.p);
@@ -1129,6 +1158,7 @@ int mnc_net_destroy(mnc_net* net) {
     for (void* p : singles) if (p) (void)hipFree(p);
     for (int i = 0; i < 14; ++i) {
       if (net->w_conv[i]) (void)hipFree(net->w_conv[i]);
+      if (net->w_split[i]) (void)hipFree(net->w_split[i]);
       if (net->b_conv[i]) (void)hipFree(net->b_conv[i]);
     }
     mnc_net::Fc* fcs[] = {&net->fc_maskest, &net->fc_maskpred, &net->fc6, &net->fc7, &net->fc6m, &net->fc7m, &net->fc_heads};

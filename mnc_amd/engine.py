@@ -913,6 +913,26 @@ class Net(object):
                 return packed
             d_w = self._dev_param(key + ("w", self.conv_math, ("wino%d" % self._wino) if (self._winograd and not x3) else "direct"), build)
 
+            def split_form(H, Wd):
+                """(weights, workspace) of the unfused F(4x4) form where the context's WINO_SPLIT value moves this layer there (the
+                native pipeline asks the same question, so both run the same kernels), else None."""
+                selected = getattr(_lib.load(), "mnc_conv3x3_wino4_split_selected", None)     # (None: a backend without the split form)
+                if x3 or self._wino != 4 or selected is None or not selected(self._h(), H, Wd, cin, cout):
+                    return None
+
+                def build_split():
+                    raw = self._upload(W)
+                    packed = self._ctx.alloc(36 * cout * cin * 4)
+                    _lib.call("mnc_pack_conv3x3_wino4_split", self._h(), raw, packed, cout, cin)
+                    self._ctx.free(raw)
+                    return packed
+                need = int(_lib.load().mnc_conv3x3_wino4_split_ws_bytes(H, Wd, cin, cout))
+                have = max([k[1] for k in self._dev_params if k[0] == "wino4_split_ws"] or [0])
+                if have < need:       # (grow-only; a smaller one stays allocated until close: launches in flight may still use it)
+                    have = need
+                    self._dev_params[("wino4_split_ws", have)] = self._ctx.alloc(have)
+                return self._dev_param(key + ("w", "wino4split"), build_split), self._dev_params[("wino4_split_ws", have)]
+
             def run():
                 N, _, H, Wd = bot.shape
                 pk = _PACKED_OF.get(self.conv_math)
@@ -933,7 +953,12 @@ class Net(object):
                     OH, OW = _pool_out(H), _pool_out(Wd)
                     top.reshape(N, cout, OH, OW)
                     dst = top.dev_out("c8")
+                    sp = split_form(H, Wd)
                     for n in range(N):
+                        if sp:
+                            _lib.call("mnc_conv3x3_wino4_split_pool", self._h(), src + n * cin * H * Wd * 4, sp[0], d_b,
+                                      dst + n * cout * OH * OW * 4, sp[1], H, Wd, cin, cout, relu)
+                            continue
                         _lib.call("mnc_conv3x3_wino4_pool" if self._wino == 4 else "mnc_conv3x3_wino_pool", self._h(), src + n * cin * H * Wd * 4, d_w, d_b,
                                   dst + n * cout * OH * OW * 4, H, Wd, cin, cout, relu)
                     return
@@ -947,7 +972,12 @@ class Net(object):
                                   dst + n * cout * H * Wd * ob, H, Wd, cin, cout, relu, 1 if in_h else 0, 1 if L.out_h else 0)
                     return
                 dst = top.dev_out("c8")
+                sp = split_form(H, Wd)
                 for n in range(N):
+                    if sp:
+                        _lib.call("mnc_conv3x3_wino4_split", self._h(), src + n * cin * H * Wd * 4, sp[0], d_b,
+                                  dst + n * cout * H * Wd * 4, sp[1], H, Wd, cin, cout, relu)
+                        continue
                     _lib.call(conv, self._h(), src + n * cin * H * Wd * 4, d_w, d_b, dst + n * cout * H * Wd * 4, H, Wd, cin,
                               cout, relu)
             return run
