@@ -1052,6 +1052,35 @@ MNC_API int mnc_fc_bf16x3_ex(mnc_ctx* ctx, const float* d_a, const void* d_a_sm,
  * and mnc_fc_unpack_act(.., fmt = 3). */
 MNC_API int mnc_fc_bf16_ex(mnc_ctx* ctx, const float* d_a, const void* d_a_sm, int m_stride, const void* d_w_packed,
                            const float* d_bias, float* d_out, int M, int N, int K, int ldc, int act, void* d_out_sm, int out_sm_fmt);
+/* ---- "f8" math mode: InnerProduct on OCP e4m3fn operands (csrc/gemm_f8.hip) ----
+ * Both operands as e4m3fn codes (NOT gfx942's e4m3fnuz) with ONE power-of-two scale 2^e per row, fp32 accumulation on
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with both hardware block scales at 1.0, the row exponents applied after all K ranges are summed:
+ *   out[m][n] = act(ldexp(sum_k dec(qa[m][k]) * dec(qw[n][k]), ea[m] + ew[n]) + bias[n]).
+ * Row rule: amax = f * 2^p (f in [0.5, 1)), e = p - 9 when f <= 0.875, else p - 8, clamped to [-64, 64], 0 for a zero row; codes =
+ * e4m3(x * 2^-e), nearest even, saturating at +-448.  amax is taken over the row's finite values: an infinity saturates at +-448, a
+ * NaN stays NaN (0x7F | sign).  mnc_amd/f8.py states all of it in numpy; the kernels follow it bit for bit
+ * except for the fp32 summation order, which is fixed (the same bits from run to run).  Like "bf16" the mode claims no parity bar.
+ * Products over fewer than four stages (K < 512; none in a net) decode the codes to fp16, exactly, and multiply on the fp16 MFMA: the
+ * scaled instruction drops products 2^16 below the largest of their K group, which an fp32 summation of so few terms would not.
+ * K%128==0 everywhere; anything else, a null operand and the like are refused with MNC_ERR_INVALID before any launch.
+ *   mnc_pack_fc_f8      Caffe weight [N][K] fp32 -> codes [ceil(N/256)][K/128][256][128] (mnc_pack_fc_f8_bytes(N, K) bytes; rows
+ *                       past N are zero codes) and d_wexp, ceil(N/256)*256 int32 row exponents.  Once at load.
+ *   mnc_fc_pack_act_f8  the activation quantiser: M rows from fp32 rows [M][K] (d_a) OR from the fp16 stage-major format-1 panel
+ *                       [K/64][m_stride][64] (d_a_sm) -- exactly one non-NULL -- -> codes [K/128][M][128] (M*K bytes), d_aexp M int32.
+ *   mnc_fc_f8           mnc_fc's interface: quantises the fp32 rows in the context's scratch and multiplies.
+ *   mnc_fc_f8_ex        activations in either form (as mnc_fc_f16_ex); optionally the result rows a second time as fp16 in the
+ *                       stage-major format 1 (out_sm_fmt == 1, N%64==0) the next InnerProduct reads; bit for bit
+ *                       mnc_fc_pack_act(d_out, f16 = 1) (dense rows, ldc == N, for that comparison; any ldc is accepted).
+ *   mnc_fc_f8_pre       activations already quantised by mnc_fc_pack_act_f8 (m_stride = rows per stage of d_q). */
+MNC_API size_t mnc_pack_fc_f8_bytes(int N, int K);
+MNC_API int mnc_pack_fc_f8(mnc_ctx* ctx, const float* d_w, void* d_packed, int* d_wexp, int N, int K);
+MNC_API int mnc_fc_pack_act_f8(mnc_ctx* ctx, const float* d_a, const void* d_a_sm, int m_stride, void* d_q, int* d_aexp, int M, int K);
+MNC_API int mnc_fc_f8(mnc_ctx* ctx, const float* d_a, const void* d_w_packed, const int* d_wexp, const float* d_bias, float* d_out,
+                      int M, int N, int K, int ldc, int act);
+MNC_API int mnc_fc_f8_ex(mnc_ctx* ctx, const float* d_a, const void* d_a_sm, int m_stride, const void* d_w_packed, const int* d_wexp,
+                         const float* d_bias, float* d_out, int M, int N, int K, int ldc, int act, void* d_out_sm, int out_sm_fmt);
+MNC_API int mnc_fc_f8_pre(mnc_ctx* ctx, const void* d_q, const int* d_aexp, int m_stride, const void* d_w_packed, const int* d_wexp,
+                          const float* d_bias, float* d_out, int M, int N, int K, int ldc, int act);
 MNC_API int mnc_roi_warp_sm(mnc_ctx* ctx, const float* d_feat_c8, int C, int H, int W, const float* d_rois, int R, int PH, int PW,
                             float spatial_scale, int pool2, float* d_out_rhwc, void* d_sm, int sm_fmt);
 MNC_API int mnc_maxpool2_rhwc_sm(mnc_ctx* ctx, const float* d_in, float* d_out, int R, int PH, int PW, int C, void* d_sm,

@@ -88,7 +88,8 @@ struct mnc_net {
   bool conv_fast[14] = {false};                // tuned 3x3 kernels (Cout % 32 == 0) or the general convolution (reduced widths)
   float* b_conv[14] = {nullptr};               // biases: trunk 0..12 -> [0..12], rpn -> [13]
   float *w_rpn = nullptr, *b_rpn = nullptr;    // rpn_cls_score (2A rows) and rpn_bbox_pred (4A rows) as ONE [6A][RC] 1x1 convolution
-  struct Fc { void* w = nullptr; float* b = nullptr; int N = 0, K = 0, kind = 0; };   // kind 0 fp32, 1 bf16x3, 2 f16, 3 plain bf16
+  struct Fc { void* w = nullptr; float* b = nullptr; int N = 0, K = 0, kind = 0; int* wexp = nullptr; };   // kind 0 fp32, 1 bf16x3, 2 f16, 3 plain bf16,
+                                               // 4 e4m3 (wexp: the rows' exponents, behind the codes in w's allocation)
   Fc fc_maskest, fc_maskpred, fc6, fc7, fc6m, fc7m, fc_heads;
   // geometry of the buffers below
   int cap_ph = 0, cap_pw = 0, cap_src = 0;
@@ -184,7 +185,8 @@ int need(mnc_net* n, const char* layer, int index, size_t count, const HostBlob*
 // math 3 ("mixed", round 4): the convolutions in bf16x3 (fp32-class), the large InnerProducts in fp16 -- the reduced-precision mode
 // that keeps the 1e-3 bar (mnc_hip.h, mnc_net_config::math)
 // math 4 ("bf16"): plain bf16, one product per term, fp32 tensors between the layers (BASELINE configs[2] as written; measured only)
-static inline int conv_math(const mnc_net_config& c) { return c.math == 3 ? 1 : c.math; }
+// math 5 ("f8"): the f16 mode with the large InnerProducts whose K is a multiple of 128 on e4m3 operands (gemm_f8.hip; measured only)
+static inline int conv_math(const mnc_net_config& c) { return c.math == 3 ? 1 : c.math == 5 ? 2 : c.math; }
 static inline int lowp_mode(int cm) { return cm == 1 ? 0 : cm == 2 ? 1 : 2; }      // conv_math 1 / 2 / 4 -> mnc_conv3x3_lowp's mode
 static inline int fc_math(const mnc_net_config& c) { return c.math == 3 ? 2 : c.math; }
 
@@ -209,7 +211,21 @@ int prepare_fc(mnc_net* n, const char* layer, int N, int K, int C, int PH, int P
   const bool big = 2.0 * n->cfg.post_nms_topn * (double)N * (double)K >= 2.0e9;
   // mixed: an InnerProduct over more than 50 000 inputs (fc6_maskest: 100 352) stays split-bf16 -- fp16 operands leave the sigmoid
   // masks behind it at 1.0-1.2e-3, the only head output of the f16 mode on the wrong side of the bar (engine.py: the same rule)
-  const int fm = (n->cfg.math == 3 && K > 50000) ? 1 : fc_math(n->cfg);
+  int fm = (n->cfg.math == 3 && K > 50000) ? 1 : fc_math(n->cfg);
+  if (fm == 5) {
+    // f8: e4m3 codes + one exponent per row when the product is large and K holds whole 128-value stages; otherwise the f16 rules
+    if (big && K % 128 == 0) {
+      const size_t code_bytes = mnc_pack_fc_f8_bytes(N, K);
+      void* packed = nullptr;
+      NET_TRY(mnc_dev_alloc(n->ctx, code_bytes + (size_t)((N + 255) / 256) * 256 * 4, &packed));
+      int* wexp = (int*)((char*)packed + code_bytes);
+      NET_TRY(mnc_pack_fc_f8(n->ctx, raw, packed, wexp, N, K));
+      NET_TRY(mnc_dev_free(n->ctx, raw));
+      fc->kind = 4; fc->w = packed; fc->wexp = wexp;
+      return MNC_OK;
+    }
+    fm = 2;
+  }
   const bool bf = fm == 4 && K % 64 == 0 && big;
   const bool f16 = (fm == 2 && K % 64 == 0 && big) || bf;
   const bool x3 = !f16 && (fm == 1 || fm == 2) && K % 32 == 0 && big;
@@ -226,6 +242,7 @@ int prepare_fc(mnc_net* n, const char* layer, int N, int K, int C, int PH, int P
 
 int run_fc(mnc_ctx* ctx, const mnc_net::Fc& fc, const float* a, float* out, int M, int ldc, int act) {
   if (M == 0) return MNC_OK;
+  if (fc.kind == 4) return mnc_fc_f8(ctx, a, fc.w, fc.wexp, fc.b, out, M, fc.N, fc.K, ldc, act);
   if (fc.kind == 3) return mnc_fc_bf16(ctx, a, fc.w, fc.b, out, M, fc.N, fc.K, ldc, act);
   if (fc.kind == 2) return mnc_fc_f16(ctx, a, fc.w, fc.b, out, M, fc.N, fc.K, ldc, act);
   if (fc.kind == 1) return mnc_fc_bf16x3(ctx, a, fc.w, fc.b, out, M, fc.N, fc.K, ldc, act);
@@ -242,6 +259,7 @@ int sm_format(const mnc_net* n, const mnc_net::Fc& fc, int C) {
   if (fc.kind == 2) return C % 64 == 0 ? 1 : 0;
   if (fc.kind == 1) return C % 32 == 0 ? 2 : 0;
   if (fc.kind == 3) return C % 64 == 0 ? 3 : 0;          // plain bf16 (round 6): fp16's layout, bf16 values
+  if (fc.kind == 4) return C % 64 == 0 ? 1 : 0;          // e4m3: the producers write the fp16 panel as in f16; the InnerProduct quantises it
   return 0;
 }
 // the InnerProduct on rows that exist in both forms: a_sm (m_stride = M rows) when the kernel takes it, the fp32 rows otherwise
@@ -250,6 +268,8 @@ int run_fc_sm(mnc_ctx* ctx, const mnc_net::Fc& fc, const float* a, const void* a
               void* out_sm = nullptr, int out_fmt = 0) {
   if (M == 0) return MNC_OK;
   if (!out_sm) out_fmt = 0;
+  if (fc.kind == 4) return mnc_fc_f8_ex(ctx, fmt == 1 ? nullptr : a, fmt == 1 ? a_sm : nullptr, M, fc.w, fc.wexp, fc.b, out, M, fc.N, fc.K,
+                                        ldc, act, out_fmt ? out_sm : nullptr, out_fmt);
   if (fc.kind == 2) return mnc_fc_f16_ex(ctx, fmt == 1 ? nullptr : a, fmt == 1 ? a_sm : nullptr, M, fc.w, fc.b, out, M, fc.N, fc.K, ldc,
                                          act, out_fmt ? out_sm : nullptr, out_fmt);
   if (fc.kind == 1) return mnc_fc_bf16x3_ex(ctx, fmt == 2 ? nullptr : a, fmt == 2 ? a_sm : nullptr, M, fc.w, fc.b, out, M, fc.N, fc.K,
@@ -573,10 +593,13 @@ int run_stage(mnc_net* n, const float* rois, int R, bool second, int row0) {
   // Round 6: in the fp16 InnerProduct modes whose head runs as paired launches the 14x14 tensor exists in its stage-major fp16 form
   // only -- fc6_maskest multiplies from it, the poolings read it (mnc_box_mask_pool_ex) -- 120 MB per stage neither written nor read
   const bool fork0 = n->ctx_b && ctx->profiling == 0 && R > 0;
-  const bool lowp_pairs = n->fuse_small && n->fuse_pools && sm_box == sm_mask && !fork0 && n->fc6.kind != 0 && n->fc6m.kind == n->fc6.kind &&
+  const bool lowp_pairs = n->fuse_small && n->fuse_pools && sm_box == sm_mask && !fork0 && n->fc6.kind != 0 && n->fc6.kind != 4 && n->fc6m.kind == n->fc6.kind &&
                           n->fc7.kind == n->fc6.kind && n->fc7m.kind == n->fc6.kind && n->fc6.K == n->fc6m.K &&
                           sm_format(n, n->fc7, F) == sm_format(n, n->fc7m, F) && R > 0;
-  const bool sm_only = lowp_pairs && sm_box != 0;                 // box7 / mask7: stage-major only
+  // e4m3 (kind 4): no paired launch, but every product quantises from the fp16 panels, so the same fp32 tensors are left out
+  const bool f8_head = n->fuse_small && n->fuse_pools && sm_box == sm_mask && !fork0 && n->fc6.kind == 4 && n->fc6m.kind == 4 &&
+                       n->fc7.kind == 4 && n->fc7m.kind == 4 && R > 0;
+  const bool sm_only = (lowp_pairs || f8_head) && sm_box != 0;    // box7 / mask7: stage-major only
   const bool feat_sm_only = sm_only && sm_feat != 0 && (P * P * C5) % 64 == 0 && roi_warp_sm_only_ok(ctx, C5, second ? 0 : 1);
   if (feat_sm_only) feat14 = nullptr;
   if (n->fuse_small)
@@ -808,7 +831,7 @@ int mnc_net_create(mnc_ctx* ctx, const mnc_net_config* cfg, mnc_net** out) {
               "mnc_net_create: head shape");
   // the per-class counts travel in a fixed 256-byte header (device `counts` buffer, pinned [counts | proposal count | records])
   MNC_REQUIRE(cfg->num_classes <= 64, "mnc_net_create: num_classes %d > 64 (the result header holds 64 counts)", cfg->num_classes);
-  MNC_REQUIRE(cfg->math >= 0 && cfg->math <= 4, "mnc_net_create: math must be 0 (fp32), 1 (bf16x3), 2 (f16), 3 (mixed) or 4 (bf16)");
+  MNC_REQUIRE(cfg->math >= 0 && cfg->math <= 5, "mnc_net_create: math must be 0 (fp32), 1 (bf16x3), 2 (f16), 3 (mixed), 4 (bf16) or 5 (f8)");
   MNC_REQUIRE(cfg->target_size > 0 && cfg->max_size >= cfg->target_size, "mnc_net_create: target_size / max_size");
   // The RoI launchers read the conventions from the context.  conventions.inherit (set by mnc_net_default_config) keeps what is
   // in force there; anything else is validated and applied -- an explicit all-zero member included (the all-zero value

@@ -31,6 +31,19 @@ from .devarray import DeviceArray
 WINOGRAD_DEFAULT = "4"
 
 
+MATH_MODES = ("fp32", "bf16x3", "f16", "mixed", "bf16", "f8")
+
+
+def math_modes(math=None):
+    """math= of Net (None: the environment's MNC_MATH, default fp32) -> (math, conv_math, fc_math); an unknown mode raises."""
+    m = (os.environ.get("MNC_MATH", "fp32") if math is None else math).lower()
+    if m not in MATH_MODES:
+        raise ValueError("math must be 'fp32', 'bf16x3', 'f16', 'mixed', 'bf16' or 'f8', got %r" % m)
+    conv = "bf16x3" if m == "mixed" else "f16" if m == "f8" else m
+    fc = "f16" if m == "mixed" else m
+    return m, conv, fc
+
+
 def winograd_mode(value):
     """None / bool / 0 / 2 / 4 / "0" / "1" / "2" / "4" -> 0 (direct), 2 (F(2x2)) or 4 (F(4x4))."""
     import os
@@ -441,17 +454,16 @@ class Net(object):
         # into hi + lo bf16 and three products per term (fp32-class accuracy, see csrc/gemm_x3.hip); "f16" = the same
         # layers in plain fp16 (operands rounded to fp16, fp32 accumulate: one product per term, ~3e-4 relative error per
         # layer -- the reduced-precision mode BASELINE configs[4] names); math= / MNC_MATH
-        self.math = (os.environ.get("MNC_MATH", "fp32") if math is None else math).lower()
-        if self.math not in ("fp32", "bf16x3", "f16", "mixed", "bf16"):
-            raise ValueError("math must be 'fp32', 'bf16x3', 'f16', 'mixed' or 'bf16', got %r" % self.math)
+        self.math, self.conv_math, self.fc_math = math_modes(math)
         # "bf16" (round 4): BASELINE configs[2] as written -- the 3x3 convolutions and the large InnerProducts with both operands
         # rounded to bf16, ONE product per term (mnc_conv3x3_bf16 / mnc_fc_bf16), fp32 tensors between the layers.  Measured, not
         # recommended: 8 mantissa bits put the network far outside the 1e-3 bar (tests/test_gpu_parity8.py records it).
         # "mixed" (round 4): the convolutions (trunk, RPN head) in bf16x3 -- fp32-class -- and the large InnerProducts in fp16: the
         # reduced-precision mode that keeps the 1e-3 bar (13 fp16 trunk layers in a row leave conv5_3 at 1e-3 of its range and the
         # RPN probabilities at 3.6e-3; behind a bf16x3 trunk the two fp16 InnerProducts of a head branch cost ~3e-4)
-        self.conv_math = "bf16x3" if self.math == "mixed" else self.math
-        self.fc_math = "f16" if self.math == "mixed" else self.math
+        # "f8": the "f16" mode with every large InnerProduct whose K is a multiple of 128 on OCP e4m3 operands, one power-of-two
+        # scale per row (csrc/gemm_f8.hip, mnc_amd/f8.py).  Like "bf16" it claims no parity bar; its distance from fp32 is recorded in
+        # tests/test_gpu_fc_f8.py.
         self._wino = winograd_mode(winograd)
         self._winograd = self._wino != 0
         # MNC_SPECULATE_ROIS=0: read the ProposalLayer's RoI count back before the heads are launched (one stream sync in the
@@ -663,7 +675,7 @@ class Net(object):
         # early because of the one-pass pooling above) -- are ONE launch (mnc_fc_pair: half the K ranges, half the partial sums).
         # The whole-image pipeline pairs the same layers (csrc/pipeline.hip: run_stage), so the two executors keep the same bits.
         # Round 6: fp16 / plain bf16 InnerProducts pair the same way (mnc_fc_lowp_pair).
-        if os.environ.get("MNC_FUSE_SMALL", "1") != "0" and self.fc_math in ("fp32", "f16", "bf16", "bf16x3"):
+        if os.environ.get("MNC_FUSE_SMALL", "1") != "0" and self.fc_math in ("fp32", "f16", "bf16", "bf16x3", "f8"):      # (f8: its fp32 / fp16 fall-backs pair; e4m3 does not)
             produced_at = {}
             for i, L in enumerate(self._layers):
                 if L.skip:
@@ -1249,6 +1261,8 @@ class Net(object):
             if 2.0 * M * n_out * K < _X3_MIN_FLOPS:
                 continue
             fm = "bf16x3" if (self.math == "mixed" and K > 50000) else self.fc_math      # (weights_for's rule)
+            if fm == "f8":             # e4m3 (K % 128 == 0) multiplies from the fp16 panel too; other K: the f16 rules
+                fm = "f16"
             if fm == "f16" and K % 64 == 0 and C % 64 == 0:
                 fmt = 1
             elif fm == "bf16":                            # round 6: format 3 = fp16's layout, bf16 values (mnc_fc_bf16_ex)
@@ -1379,6 +1393,27 @@ class Net(object):
             big = 2.0 * M * n_out * K >= _X3_MIN_FLOPS
             # mixed: an InnerProduct over more than 50 000 inputs (fc6_maskest: 100 352) stays split-bf16 (pipeline.hip: prepare_fc)
             fm = "bf16x3" if (self.math == "mixed" and K > 50000) else self.fc_math
+            if fm == "f8" and not (big and K % 128 == 0):      # f8: only the large products over whole 128-value stages;
+                fm = "f16"                                     # otherwise the f16 rules (pipeline.hip: prepare_fc)
+            if fm == "f8":
+                def finish8(d_w):
+                    code_bytes = _lib.load().mnc_pack_fc_f8_bytes(n_out, K)
+                    packed = self._ctx.alloc(code_bytes + (n_out + 255) // 256 * 256 * 4)      # codes, then the rows' exponents
+                    _lib.call("mnc_pack_fc_f8", self._h(), d_w, packed, packed + code_bytes, n_out, K)
+                    self._ctx.free(d_w)
+                    return packed
+                state["wexp_off"] = _lib.load().mnc_pack_fc_f8_bytes(n_out, K)
+                if len(shape) == 4 and shape[2] * shape[3] > 1:
+                    geo8 = (shape[1], shape[2], shape[3])
+
+                    def build8():
+                        raw = self._upload(W)
+                        perm = self._ctx.alloc(W.nbytes)
+                        _lib.call("mnc_pack_fc_weights", self._h(), raw, perm, n_out, geo8[0], geo8[1], geo8[2])
+                        self._ctx.free(raw)
+                        return finish8(perm)
+                    return self._dev_param(key + ("w",) + geo8 + ("f8",), build8), "rhwc", "mnc_fc_f8"
+                return self._dev_param(key + ("w", "plain", "f8"), lambda: finish8(self._upload(W))), "plain", "mnc_fc_f8"
             bf = fm == "bf16" and K % 64 == 0 and big          # plain bf16: the fp16 kernel's layout and launcher
             f16 = (fm == "f16" and K % 64 == 0 and big) or bf
             x3 = (not f16) and fm in ("bf16x3", "f16") and K % 32 == 0 and big
@@ -1411,7 +1446,7 @@ class Net(object):
             """(fp32 rows or None, stage-major rows or None, dst, second-output format, second output or None) of this layer's
             reduced-precision call, with its top made ready: the rows arrive in the kernel's own 2-byte form when the producer
             wrote them (Blob._sm: no conversion pass), and leave in the NEXT InnerProduct's form as well when one will read them."""
-            want = {"mnc_fc_f16": 1, "mnc_fc_bf16x3": 2, "mnc_fc_bf16": 3}.get(state.get("fn"), 0)
+            want = {"mnc_fc_f16": 1, "mnc_fc_bf16x3": 2, "mnc_fc_bf16": 3, "mnc_fc_f8": 1}.get(state.get("fn"), 0)
             sm = bot._sm
             pre = bool(want and sm is not None and sm["fmt"] == want and sm["M"] == M and sm["K"] == K
                        and (bot._dev_valid or bot._sm_only) and bot.layout == state["layout"])
@@ -1419,6 +1454,8 @@ class Net(object):
             top.reshape(M, n_out)
             dst = top.dev_out("plain")
             ofmt = self._sm_format(top.name, M, n_out, n_out) if (want and top._view is None) else 0
+            if state.get("fn") == "mnc_fc_f8" and ofmt != 1:   # (mnc_fc_f8_ex writes the fp16 panel only)
+                ofmt = 0
             return src, (sm["ptr"] if pre else None), dst, ofmt, (top.sm_out(ofmt, M, n_out) if ofmt else None)
 
         def run():
@@ -1431,6 +1468,11 @@ class Net(object):
             if M and "w" not in state:
                 state["w"], state["layout"], state["fn"] = weights_for(bot.shape, M)
             P = L.pair
+            if M and state.get("fn") == "mnc_fc_f8":           # e4m3: single launches (no paired form)
+                src, pre, dst, ofmt, osm = lowp_args(M)
+                _lib.call("mnc_fc_f8_ex", self._h(), src, pre, M, state["w"], state["w"] + state["wexp_off"], d_b, dst, M, n_out, K,
+                          top._ld(), act, osm, ofmt)
+                return
             if M and state.get("fn") in LOWP_PAIR and P is not None and P.ip_prepare is not None:
                 src, pre, dst, ofmt, osm = lowp_args(M)
                 other = P.ip_prepare(M, K, state["fn"])

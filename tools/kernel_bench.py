@@ -7,6 +7,9 @@
     python tools/kernel_bench.py convwino4             the same on the fused Winograd F(4x4,3x3) fp32 kernel (csrc/conv_wino4.hip)
     python tools/kernel_bench.py fc   [--reps 20]      the FC shapes of one head stage at 300 RoIs
     python tools/kernel_bench.py fcx3                  the same on the bf16x3 kernel
+    python tools/kernel_bench.py fcf16 | fcf8 [--sm]   the same in fp16 / on e4m3 operands (csrc/gemm_f8.hip: the quantise pass, the product
+                                                       and the reduction are listed separately); --sm: the activations arrive as the
+                                                       fp16 stage-major panel, as the head stages hand them over
     python tools/kernel_bench.py conv1x1 [--f16]       the 1x1 convolutions of the ResNet-50 C4 trunk at 800x1333: the GEMM kernel
                                                        (csrc/conv1x1.hip; MNC_CONV1X1_TILE=ct,pt) next to the general kernel
 Environment knobs understood by the library (tuning aids): MNC_CONV_COT=1|2|4."""
@@ -52,7 +55,7 @@ def records(dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["conv", "convx3", "convf16", "convsw", "convwino", "convwino4", "fc", "fcx3", "fcf16", "conv1x1"])
+    ap.add_argument("what", choices=["conv", "convx3", "convf16", "convsw", "convwino", "convwino4", "fc", "fcx3", "fcf16", "fcf8", "conv1x1"])
     ap.add_argument("--f16", action="store_true", help="conv1x1: packed fp16 tensors (mnc_conv1x1_f16_pk) instead of fp32")
     ap.add_argument("--mode", default="f16", help="convsw: bf16x3 | f16 | bf16 (mnc_conv3x3_lowp, packed tensors)")
     ap.add_argument("--reps", type=int, default=20)
@@ -62,6 +65,8 @@ def main():
                     "the matrix pipe is power limited, operand values move the clock")
     ap.add_argument("--pair", action="store_true", help="fcx3 / fcf16: TWO products of the shape in one launch (mnc_fc_lowp_pair, activations "
                     "already stage-major: the box + mask branch call of the head stages)")
+    ap.add_argument("--sm", action="store_true", help="fcf16 / fcf8: activations already in the fp16 stage-major form (mnc_fc_f16_pre / "
+                    "mnc_fc_f8_ex on the panel): no conversion pass in fp16, the quantise pass reads 2-byte values in f8")
     ap.add_argument("--gap-ms", type=float, default=0.0, help="fc*: synchronise and sleep this long before every timed launch (a kernel that "
                     "starts on a rested chip runs at a higher clock than the same kernel back to back)")
     ap.add_argument("--packed", action="store_true", help="convx3 / convf16: 2-byte activation tensors in and out")
@@ -218,7 +223,27 @@ def main():
                 wp = dev.empty(((N + 127) // 128 * 128 * K // 2,))
                 dev.call("mnc_pack_fc_f16", w, wp, N, K)
                 w, fn = wp, "mnc_fc_f16"
-            if args.pair and args.what in ("fcx3", "fcf16"):
+            elif args.what == "fcf8":
+                if K % 128:
+                    continue
+                from mnc_amd import _lib
+                wp = dev.alloc(_lib.load().mnc_pack_fc_f8_bytes(N, K))
+                wexp = dev.alloc((N + 255) // 256 * 256 * 4)
+                dev.call("mnc_pack_fc_f8", w, wp, wexp, N, K)
+                w, fn = wp, "mnc_fc_f8"
+            if args.sm and args.what in ("fcf16", "fcf8") and not args.pair:
+                asm = dev.alloc(M * K * 2)
+                dev.call("mnc_fc_pack_act", a, asm, M, K, 1)
+
+                def run():
+                    if args.what == "fcf8":
+                        dev.call("mnc_fc_f8_ex", None, asm, M, w, wexp, b, y, M, N, K, N, 1, None, 0)
+                    else:
+                        dev.call("mnc_fc_f16_pre", asm, M, w, b, y, M, N, K, N, 1)
+            elif args.what == "fcf8":
+                def run():
+                    dev.call("mnc_fc_f8", a, w, wexp, b, y, M, N, K, N, 1)
+            elif args.pair and args.what in ("fcx3", "fcf16"):
                 f16 = 1 if args.what == "fcf16" else 0
                 asm = dev.empty((M * K // 2 if f16 else M * K,))
                 dev.call("mnc_fc_pack_act", a, asm, M, K, f16)
@@ -239,9 +264,9 @@ def main():
                     time.sleep(args.gap_ms * 1e-3)
                 run()
             rec = records(dev)
-            t = np.array([r[1] for r in rec if r[0].startswith("fc_mfma") or r[0] in ("fc_bf16x3", "fc_bf16x3_small", "fc_f16", "fc_f16_small")])
-            tr = np.array([r[1] for r in rec if r[0] == "fc_reduce"] or [0.0])
-            ts = np.array([r[1] for r in rec if r[0] in ("fc_bf16x3_split", "fc_f16_convert")] or [0.0])
+            t = np.array([r[1] for r in rec if r[0].startswith("fc_mfma") or r[0] in ("fc_bf16x3", "fc_bf16x3_small", "fc_f16", "fc_f16_small", "fc_f8")])
+            tr = np.array([r[1] for r in rec if r[0] in ("fc_reduce", "fc_f8_reduce")] or [0.0])
+            ts = np.array([r[1] for r in rec if r[0] in ("fc_bf16x3_split", "fc_f16_convert", "fc_f8_quantise")] or [0.0])
             fl = 2.0 * M * N * K * (2 if args.pair and args.what in ("fcx3", "fcf16") else 1)
             tot = np.median(t) + np.median(tr) + np.median(ts)
             print("%-12s M=%d N=%-4d K=%-6d  gemm %.1f us + reduce %.1f us + split %.1f us = %.1f us   %.1f TF/s (gemm)  %.1f TF/s (all)" %
