@@ -629,6 +629,66 @@ MNC_API int mnc_contours_simplify(const long long* vert_ptr, const int* xy, size
 MNC_API int mnc_contours_simplify_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n15 The masks as distances: the squared Euclidean distance transform of packed masks, the largest inscribed disc, and
+ *     erosion, dilation, opening and closing by a disc (csrc/mask_distance.hip) -- on the layout of n5.  The statements of the
+ *     rules are mnc_amd/distance.py:distance_numpy, inscribed_numpy and morph_numpy.
+ *     All arithmetic is integer and all rules are frame-free: a mask M is a set of lattice pixels that is empty outside its
+ *     bounds (padding bits are not trusted); the image size enters only as an optional final clip of the dilation.
+ *     Inside distance: D(p) = min |p - q|^2 over all pixels q not in M, pixels beyond the bounds included, for p in M; D(p) = 0
+ *     for p not in M.  (scipy.ndimage.distance_transform_edt of the mask padded by one pixel of zeros, squared.)  D <=
+ *     ((min(w, h) + 1) / 2)^2.
+ *     Inscribed disc: per instance the pixel of maximal D, the lowest (y, x) on ties, and that D.
+ *     Disc morphology: the structuring element of squared radius R2 >= 0 is {(dx, dy): dx^2 + dy^2 <= R2}, rho = isqrt(R2).
+ *     erode keeps p iff D(p) > R2.  dilate sets p iff some pixel of M lies within R2 -- the same transform on the complement,
+ *     in the bounds grown by rho on every side, beyond which nothing is set.  open = dilate(erode), close = erode(dilate) with
+ *     the erosion taken in the unclipped grown frame.  Opening and closing never leave the input's bounds.
+ *     Two passes per transform.  The first gives every pixel g, the distance along its row to the nearest pixel outside the set
+ *     (count-leading / -trailing-zero walks over the packed words, cut off at a cap that no reader can mistake: rho + 1 for the
+ *     morphology, (min(w, h) + 1) / 2 + 1 for the maps), as uint16; the second, one lane per pixel, takes min(g^2 + dy^2) over
+ *     the rows y +- dy while dy^2 is below the best so far (for the morphology: dy <= rho, and until the decision is made) and
+ *     writes the distance, or one ballot word per wave with its popcount added to the area, or joins a 64-bit integer maximum
+ *     of (D << 32) | (0xffffffff - linear index).  2 launches (4 for open and close) whatever the data, no read-back between
+ *     them; integer atomics only: the same input gives the same bytes on every run.
+ *     Every entry takes the set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds.
+ *     n == 0 and sets without a single row are answered on the host.  MNC_ERR_INVALID, checked on the host before anything is
+ *     launched, for every entry: everything mnc_mask_boundary refuses about a set (n outside [0, 2048], |coordinate| >= 2^24,
+ *     more than 2^26 pixels in one bound, an offset that is negative or not a multiple of 8, rows that reach past bytes); more
+ *     than 2^27 pixels of rows in the call; a null pointer where one is needed.  (There are no forms that read a
+ *     device-resident mnc_mask_records result: the PackedMasks methods fetch such a result first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* The maps.  Outputs: dist_ptr [n + 1] (dist_ptr[0] = 0; instance i has the h * w entries dist_ptr[i] .. dist_ptr[i + 1] - 1,
+ * row-major with row stride w; none without rows), *dist_total = dist_ptr[n], dist [*dist_total] the D of every pixel.
+ * dist == NULL: dist_ptr and *dist_total only, nothing is launched.  Otherwise dist_cap is the room of dist in entries;
+ * dist_cap < *dist_total is MNC_ERR_INVALID with dist_ptr and *dist_total set and nothing else written.  Entries past
+ * *dist_total are never written. */
+MNC_API int mnc_mask_distance(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
+                              long long* dist_ptr, unsigned* dist, size_t dist_cap, size_t* dist_total, int device_id);
+/* The inscribed discs.  Outputs: xy [n][2] (x, y of the pixel in image coordinates: bounds x1 + dx, bounds y1 + dy), r2 [n] its
+ * D.  An instance without rows or without a set pixel gives (-1, -1) and 0. */
+MNC_API int mnc_mask_inscribed(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int* xy, int* r2,
+                               int device_id);
+/* The morphology.  op: 0 erode, 1 dilate, 2 open, 3 close; r2 = R2; H, W both 0: no clip, else the image the dilation's bounds
+ * are intersected with (looked at by op 1 only).  The result has the layout of n5 as mnc_mask_boundary writes it: out_offsets
+ * [n] are multiples of 8, in order without gaps; out_areas [n] are the true bit counts; padding bits are 0.  erode, open and
+ * close keep the input's bounds (an instance without rows keeps them and gets no rows).  dilate gives (x1 - rho, y1 - rho,
+ * x2 + rho, y2 + rho), not tightened; with H, W these intersected with [0, W-1] x [0, H-1], (0, 0, -1, -1) where nothing is left
+ * or where the instance had no rows (without H, W an instance without rows keeps its bounds).  out_bounds, out_offsets and
+ * *bits_bytes follow from the bounds alone and are computed on the host: with out_bits == NULL the call returns them and
+ * launches nothing (out_areas may be NULL then); bits_cap < *bits_bytes is MNC_ERR_INVALID with the three set and nothing else
+ * written.  Bytes past *bits_bytes are never written.  MNC_ERR_INVALID as above, with nothing written, and: op outside [0, 3];
+ * r2 outside [0, 1024^2]; H and W neither both 0 nor both in [1, 32768]; for dilate and close, whose frames are the bounds grown
+ * by rho: a grown coordinate with |c| >= 2^24, a grown instance of more than 2^26 pixels, more than 2^27 pixels of grown rows
+ * in the call. */
+MNC_API int mnc_mask_morph(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int op, int r2,
+                           int H, int W, int* out_bounds, long long* out_offsets, long long* out_areas, void* out_bits,
+                           size_t bits_cap, size_t* bits_bytes, int device_id);
+/* For tools/mask_distance_bench.py.  on = 1: the following calls of the three entries above put a HIP event pair around their
+ * launches (without the copies of the set and of the results) and keep the last call's time in milliseconds; on = 0: they do
+ * not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on
+ * forgets it. */
+MNC_API int mnc_mask_distance_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -262,6 +262,40 @@ def mask_boundary(pm, H, W, d=None):
     return pm.boundary(H, W, d, device_id=cfg.GPU_ID)
 
 
+def mask_distance(pm):
+    """The squared Euclidean inside distances of a PackedMasks on the GPU (mnc_mask_distance, csrc/mask_distance.hip) ->
+    mnc_amd.distance.DistanceMaps(dist_ptr, sq, shapes)."""
+    return pm.distance(device_id=cfg.GPU_ID)
+
+
+def mask_inscribed(pm):
+    """The centre and squared radius of the largest inscribed disc of every instance on the GPU (mnc_mask_inscribed) -> (xy int32
+    [n, 2], r2 int32 [n])."""
+    return pm.inscribed(device_id=cfg.GPU_ID)
+
+
+def mask_erode(pm, radius=None, r2=None):
+    """A PackedMasks eroded by the disc of that radius (or exact squared radius r2) on the GPU (mnc_mask_morph) ->
+    mnc_amd.masks.PackedMasks with the input's bounds."""
+    return pm.erode(radius, r2, device_id=cfg.GPU_ID)
+
+
+def mask_dilate(pm, radius=None, r2=None, H=None, W=None):
+    """A PackedMasks dilated by the disc on the GPU (mnc_mask_morph) -> mnc_amd.masks.PackedMasks with the bounds grown by
+    isqrt(r2), with H, W clipped to the image."""
+    return pm.dilate(radius, r2, H, W, device_id=cfg.GPU_ID)
+
+
+def mask_open(pm, radius=None, r2=None):
+    """dilate(erode) of a PackedMasks by the disc on the GPU (mnc_mask_morph) -> mnc_amd.masks.PackedMasks with the input's bounds."""
+    return pm.open(radius, r2, device_id=cfg.GPU_ID)
+
+
+def mask_close(pm, radius=None, r2=None):
+    """erode(dilate) of a PackedMasks by the disc on the GPU (mnc_mask_morph) -> mnc_amd.masks.PackedMasks with the input's bounds."""
+    return pm.close(radius, r2, device_id=cfg.GPU_ID)
+
+
 def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
                         ratio=0.02, return_iou=False):
     """mask_match on the overlap min(mask IoU, boundary IoU) in an H x W image -- COCO's iouType "boundary" -- on the GPU

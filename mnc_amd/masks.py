@@ -18,6 +18,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
     PackedMasks.components / .select / .fill_holes / .split   connected components and what is built on them (mnc_amd/components.py, n12)
     PackedMasks.contours / .polygons   the outlines as closed loops of lattice points, and as COCO polygons (mnc_amd/contours.py, n13),
                                        simplified to a tolerance with polygons(epsilon=) (n14)
+    PackedMasks.distance / .inscribed / .erode / .dilate / .open / .close   the squared Euclidean distance transform, the deepest
+                                       pixel of every instance, and the morphology by a disc (mnc_amd/distance.py, n15)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -245,6 +247,47 @@ class PackedMasks(object):
         cv2.approxPolyDP does after findContours); epsilon == 0, the default, is the exact pixel staircase."""
         from . import contours
         return contours.polygons(self, connectivity, device_id, epsilon)
+
+    def distance(self, device_id=None):
+        """The squared Euclidean inside distance of every pixel -> mnc_amd.distance.DistanceMaps(dist_ptr, sq, shapes), .map(i) the
+        uint32 [h, w] of instance i, by the rule of mnc_amd.distance.distance_numpy (include/mnc_hip.h n15, csrc/mask_distance.hip)
+        on the GPU.  A device-resident result is fetched to the host first."""
+        from . import distance
+        return distance.distance(self, device_id)
+
+    def inscribed(self, device_id=None):
+        """The centre of the largest inscribed disc of every instance -> (xy int32 [n, 2] in image coordinates, r2 int32 [n] its
+        squared radius): the pixel of maximal inside distance, the lowest (y, x) on ties; (-1, -1) and 0 for an instance without
+        a set pixel (mnc_amd.distance.inscribed_numpy's rule through mnc_mask_inscribed).  A device-resident result is fetched to
+        the host first."""
+        from . import distance
+        return distance.inscribed(self, device_id)
+
+    def erode(self, radius=None, r2=None, device_id=None):
+        """These masks eroded by the disc {dx^2 + dy^2 <= r2} (r2 exact, or radius: mnc_amd.distance.radius_sq) -> a host
+        PackedMasks with this one's bounds, by the rule of mnc_amd.distance.morph_numpy through mnc_mask_morph.  A device-resident
+        result is fetched to the host first."""
+        from . import distance
+        return distance.morph(self, "erode", radius, r2, None, None, device_id)
+
+    def dilate(self, radius=None, r2=None, H=None, W=None, device_id=None):
+        """These masks dilated by the disc -> a host PackedMasks whose bounds are this one's grown by isqrt(r2) on every side, with
+        H, W intersected with the image (morph_numpy's rule).  A device-resident result is fetched to the host first."""
+        from . import distance
+        return distance.morph(self, "dilate", radius, r2, H, W, device_id)
+
+    def open(self, radius=None, r2=None, device_id=None):
+        """dilate(erode) by the disc, without leaving the device in between: spurs, necks and specks narrower than the disc go ->
+        a host PackedMasks with this one's bounds (morph_numpy's rule).  A device-resident result is fetched to the host first."""
+        from . import distance
+        return distance.morph(self, "open", radius, r2, None, None, device_id)
+
+    def close(self, radius=None, r2=None, device_id=None):
+        """erode(dilate) by the disc, the erosion taken in the unclipped grown frame: notches, pinholes and gaps narrower than the
+        disc fill -> a host PackedMasks with this one's bounds (morph_numpy's rule).  A device-resident result is fetched to the
+        host first."""
+        from . import distance
+        return distance.morph(self, "close", radius, r2, None, None, device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

@@ -5,7 +5,7 @@ optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
                          [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E]]
-                         [--min-component-area A [--largest-component]]
+                         [--min-component-area A [--largest-component]] [--smooth-radius R]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -19,7 +19,10 @@ annotations) whose segmentations are polygons: the outer loops of the masks' out
 with --cpu mnc_amd.contours.contours_numpy).  Polygons belong in annotation files; COCO results files carry RLE, which is what
 --save-coco writes.  tools/eval_coco.py --gt FILE --polygons reads the file.  --polygon-epsilon E simplifies those polygons to E
 pixels (Contours.simplify, csrc/contour_simplify.hip; with --cpu mnc_amd.contours.simplify_numpy); 0, the default, writes the exact
-pixel staircase."""
+pixel staircase.  --smooth-radius R opens, then closes every written mask by the disc of radius R (PackedMasks.open / .close,
+csrc/mask_distance.hip; with --cpu mnc_amd.distance.morph_numpy): spurs, necks and notches narrower than the disc and the resize
+staircase go.  It runs before the component selection -- an opening can cut a neck, and the selection then drops the speck; 0, the
+default, leaves the masks as they are."""
 import argparse
 import os
 import time
@@ -68,6 +71,9 @@ def parse_args(argv=None):
                         "--save-annotations write")
     p.add_argument("--largest-component", dest="largest_component", action="store_true",
                    help="keep only the largest 8-connected component of every written mask")
+    p.add_argument("--smooth-radius", dest="smooth_radius", default=0.0, type=float, metavar="R",
+                   help="open, then close the masks --save-masks / --save-coco / --save-annotations write by the disc of radius R, "
+                        "before the component selection [0: off]")
     return p.parse_args(argv)
 
 
@@ -187,6 +193,16 @@ def _select_components(packed, min_area, largest, cpu=False):
     return components.select_numpy(packed.fetch(), *args) if cpu else packed.select(*args)
 
 
+def _smooth(packed, radius, cpu=False):
+    """The written masks opened, then closed by the disc of that radius (on the GPU, csrc/mask_distance.hip; cpu=True: the numpy
+    statement).  A device-resident result is fetched first."""
+    from mnc_amd import distance
+    r2 = distance.radius_sq(radius)
+    if cpu:
+        return distance.morph_numpy(distance.morph_numpy(packed.fetch(), "open", r2), "close", r2)
+    return packed.open(r2=r2).close(r2=r2)
+
+
 def _coco_results(image_id, im_shape, packed, cpu=False):
     """-> COCO result entries of one image's PackedMasks: the mask run-length encoded in the image (on the GPU where the masks
     lie, csrc/mask_rle.hip; cpu=True: mnc_amd.rle's numpy statement), bbox = [x, y, w, h] of the tight box of its pixels."""
@@ -294,6 +310,8 @@ def main(argv=None):
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
             packed = _packed_masks(im.shape, result_mask, result_box, blk.view() if blk is not None else None, args.vis_thresh,
                                    args.cpu_mode)
+            if args.smooth_radius > 0:
+                packed = _smooth(packed, args.smooth_radius, args.cpu_mode)
             if args.min_component_area > 0 or args.largest_component:
                 packed = _select_components(packed, args.min_component_area, args.largest_component, args.cpu_mode)
             if args.save_coco:                                    # (first: a device-resident result is encoded where it lies)
