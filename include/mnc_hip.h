@@ -689,6 +689,52 @@ MNC_API int mnc_mask_morph(const int* bounds, const long long* offsets, const vo
 MNC_API int mnc_mask_distance_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n16 The masks as shapes: the moments of order up to two, the convex hull, the rectangle of least area and the diameter
+ *     of packed masks (csrc/mask_shape.hip) -- on the layout of n5.  The statements of the rules are
+ *     mnc_amd/shape.py:moments_numpy, hull_numpy and oriented_numpy.  Every result is an integer; the floats a caller wants
+ *     (centroid, axes, corners, angle) follow from them on the host.
+ *     Moments: m_pq = sum of x^p y^q over the set pixels, x and y the pixel's column and row relative to the bounds' (x1, y1);
+ *     six sums per instance in the order m00, m10, m01, m20, m11, m02, each below 2^56.  Padding bits are not counted.
+ *     Hull: the convex hull of the union of the closed unit squares [x, x + 1] x [y, y + 1] of the set pixels.  Vertices are
+ *     lattice points in image coordinates with n13's conventions: clockwise on screen (the set on the right of every edge, y
+ *     pointing down), from the smallest vertex in (y, x) order on, no three consecutive vertices collinear, the first not
+ *     repeated.  area2 is twice the shoelace area.  The candidates are, per lattice row Y, the least first set column and the
+ *     greatest (last set column + 1) over the pixel rows Y - 1 and Y; a candidate is a vertex exactly when its extreme tangents
+ *     to the candidates above and below make a strictly convex angle, which every candidate decides by itself.
+ *     Rectangle of least area: for hull edge k with tail a and vector e, over the hull vertices p, t = (p - a) . e and s =
+ *     ex (p_y - a_y) - ey (p_x - a_x) >= 0; the rectangle on the edge has the area (tmax - tmin) smax / |e|^2 (numerator below
+ *     2^64, denominator below 2^32); the least wins, compared by cross-multiplication in 128 bits, the lowest k on ties.
+ *     Diameter: the greatest squared distance between two hull vertices i < j, the lexicographically lowest pair on ties.
+ *     An instance without rows or without a set pixel gives zeros and no vertices.
+ *     Every entry takes the set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds.
+ *     n == 0 and sets without a single row are answered on the host.  MNC_ERR_INVALID, checked on the host before anything is
+ *     launched and with nothing written: everything mnc_mask_boundary refuses about a set (n outside [0, 2048], |coordinate|
+ *     >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or not a multiple of 8, rows that reach past
+ *     bytes); a bound wider or taller than 32768; a null pointer where one is needed.  The launch counts do not depend on the
+ *     data; the only atomics are the 64-bit integer adds of the moments: the same input gives the same bytes on every run.
+ *     (There are no forms that read a device-resident mnc_mask_records result: the PackedMasks methods fetch such a result
+ *     first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* moments [n][6]. */
+MNC_API int mnc_mask_moments(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, long long* moments,
+                             int device_id);
+/* Outputs: vert_ptr [n + 1] (vert_ptr[0] = 0; instance i has the vertices vert_ptr[i] .. vert_ptr[i + 1] - 1), *n_verts = V =
+ * vert_ptr[n]; xy [V][2] (x, y), area2 [n].  xy == NULL: vert_ptr and *n_verts only (area2 is not looked at).  Otherwise vert_cap
+ * is the room of xy in vertices; vert_cap < V is MNC_ERR_INVALID with vert_ptr and *n_verts set and nothing else written, so that
+ * the caller calls again with room.  Entries past V are never written. */
+MNC_API int mnc_mask_hull(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, long long* vert_ptr,
+                          int* xy, long long* area2, size_t vert_cap, size_t* n_verts, int device_id);
+/* Hull and calipers in one call; the hull's vertices do not come to the host.  box [n][8] = (k, ax, ay, ex, ey, tmin, tmax, smax)
+ * with a in image coordinates and k the edge's index in the hull mnc_mask_hull gives; diameter [n][3] = (d2, i, j). */
+MNC_API int mnc_mask_oriented(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, long long* box,
+                              long long* diameter, int device_id);
+/* For tools/mask_shape_bench.py.  on = 1: the following calls of the three entries above put a HIP event pair around their
+ * launches (without the copies of the set and of the results) and keep the last call's time in milliseconds; on = 0: they do
+ * not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on
+ * forgets it. */
+MNC_API int mnc_mask_shape_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

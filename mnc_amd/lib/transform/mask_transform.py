@@ -296,6 +296,28 @@ def mask_close(pm, radius=None, r2=None):
     return pm.close(radius, r2, device_id=cfg.GPU_ID)
 
 
+def mask_moments(pm):
+    """The moments of order up to two of a PackedMasks on the GPU (mnc_mask_moments, csrc/mask_shape.hip) ->
+    mnc_amd.shape.Moments(m int64 [n, 6], origin)."""
+    return pm.moments(device_id=cfg.GPU_ID)
+
+
+def mask_hull(pm):
+    """The convex hulls of a PackedMasks on the GPU (mnc_mask_hull) -> mnc_amd.shape.Hulls(vert_ptr, xy, area2)."""
+    return pm.hull(device_id=cfg.GPU_ID)
+
+
+def mask_solidity(pm):
+    """Pixel count over hull area of every instance of a PackedMasks on the GPU -> float64 [n]."""
+    return pm.solidity(device_id=cfg.GPU_ID)
+
+
+def mask_oriented_boxes(pm):
+    """The rectangles of least area and the diameters of a PackedMasks on the GPU (mnc_mask_oriented) ->
+    mnc_amd.shape.OrientedBoxes(box int64 [n, 8], diameter int64 [n, 3])."""
+    return pm.oriented_boxes(device_id=cfg.GPU_ID)
+
+
 def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
                         ratio=0.02, return_iou=False):
     """mask_match on the overlap min(mask IoU, boundary IoU) in an H x W image -- COCO's iouType "boundary" -- on the GPU

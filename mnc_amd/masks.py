@@ -20,6 +20,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        simplified to a tolerance with polygons(epsilon=) (n14)
     PackedMasks.distance / .inscribed / .erode / .dilate / .open / .close   the squared Euclidean distance transform, the deepest
                                        pixel of every instance, and the morphology by a disc (mnc_amd/distance.py, n15)
+    PackedMasks.moments / .hull / .solidity / .oriented_boxes   the moments of order up to two, the convex hull, the rectangle of
+                                       least area and the diameter (mnc_amd/shape.py, n16)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -288,6 +290,34 @@ class PackedMasks(object):
         host first."""
         from . import distance
         return distance.morph(self, "close", radius, r2, None, None, device_id)
+
+    def moments(self, device_id=None):
+        """The moments of order up to two of every instance -> mnc_amd.shape.Moments(m int64 [n, 6], origin): (m00, m10, m01, m20,
+        m11, m02) relative to the bounds' corner, with .centroid(), .central(), .orientation() and .axes() on the host, by the
+        rule of mnc_amd.shape.moments_numpy (include/mnc_hip.h n16, csrc/mask_shape.hip) on the GPU.  A device-resident result
+        is fetched to the host first."""
+        from . import shape
+        return shape.moments(self, device_id)
+
+    def hull(self, device_id=None):
+        """The convex hull of every instance's pixel squares -> mnc_amd.shape.Hulls(vert_ptr, xy, area2): lattice vertices in
+        image coordinates, clockwise on screen from the smallest (y, x), and twice the area, by the rule of
+        mnc_amd.shape.hull_numpy through mnc_mask_hull.  A device-resident result is fetched to the host first."""
+        from . import shape
+        return shape.hull(self, device_id)
+
+    def solidity(self, device_id=None):
+        """float64 [n]: .areas over the hull's area, 2 area / area2; 0 for an instance without a set pixel.  A device-resident
+        result is fetched to the host first."""
+        from . import shape
+        return shape.hull(self, device_id).solidity(self.areas)
+
+    def oriented_boxes(self, device_id=None):
+        """The rectangle of least area around every instance and its diameter -> mnc_amd.shape.OrientedBoxes(box int64 [n, 8],
+        diameter int64 [n, 3]) with .corners() and .rbox() on the host, by the rule of mnc_amd.shape.oriented_numpy through
+        mnc_mask_oriented (hull and calipers in one call).  A device-resident result is fetched to the host first."""
+        from . import shape
+        return shape.oriented(self, device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

@@ -4,7 +4,7 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E]]
+                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes]]
                          [--min-component-area A [--largest-component]] [--smooth-radius R]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
@@ -22,7 +22,10 @@ pixels (Contours.simplify, csrc/contour_simplify.hip; with --cpu mnc_amd.contour
 pixel staircase.  --smooth-radius R opens, then closes every written mask by the disc of radius R (PackedMasks.open / .close,
 csrc/mask_distance.hip; with --cpu mnc_amd.distance.morph_numpy): spurs, necks and notches narrower than the disc and the resize
 staircase go.  It runs before the component selection -- an opening can cut a neck, and the selection then drops the speck; 0, the
-default, leaves the masks as they are."""
+default, leaves the masks as they are.  --oriented-boxes adds to every annotation of --save-annotations "rbox": [cx, cy, w, h, angle]
+-- the rectangle of least area around the written mask, the angle in degrees from +x towards +y (OrientedBoxes.rbox of
+PackedMasks.oriented_boxes, csrc/mask_shape.hip; with --cpu mnc_amd.shape.oriented_numpy; null for a mask without a pixel) -- and
+"solidity", its pixel count over the area of its convex hull; without the flag the file is what it was."""
 import argparse
 import os
 import time
@@ -66,6 +69,9 @@ def parse_args(argv=None):
     p.add_argument("--polygon-epsilon", dest="polygon_epsilon", default=0.0, type=float, metavar="E",
                    help="simplify the polygons --save-annotations writes to E pixels (Douglas-Peucker on the closed loops) [0: the "
                         "exact outline]")
+    p.add_argument("--oriented-boxes", dest="oriented_boxes", action="store_true",
+                   help="add \"rbox\": [cx, cy, w, h, angle in degrees] (the rectangle of least area) and \"solidity\" (pixels over "
+                        "convex hull area) to every annotation --save-annotations writes, after the smoothing and the selection")
     p.add_argument("--min-component-area", dest="min_component_area", default=0, type=int, metavar="A",
                    help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco / "
                         "--save-annotations write")
@@ -227,12 +233,14 @@ def _coco_results(image_id, im_shape, packed, cpu=False):
     return out
 
 
-def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0):
+def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0, oriented=False):
     """-> COCO annotation entries of one image's PackedMasks: segmentation = the outer loops of the 8-connected outline as polygons
     (on the GPU, csrc/mask_contours.hip; cpu=True: the numpy statement), bbox = [x, y, w, h] of the polygons' extent (the tight box
     of the mask's pixels; with epsilon > 0 the extent of the polygons written), area = the mask's pixel count, iscrowd 0.  An
     instance without a set pixel has no polygons.  epsilon > 0 simplifies the loops to that many pixels (csrc/contour_simplify.hip;
-    cpu=True: simplify_numpy).  A device-resident result is fetched first."""
+    cpu=True: simplify_numpy).  oriented: "rbox" = [cx, cy, w, h, angle] of the rectangle of least area (null for an instance
+    without a set pixel) and "solidity" = area over convex hull area as well (csrc/mask_shape.hip; cpu=True: the numpy statements
+    of mnc_amd.shape).  A device-resident result is fetched first."""
     from mnc_amd import contours
     packed = packed.fetch()
     c = contours.contours_numpy(packed, 8) if cpu else packed.contours(8)
@@ -248,6 +256,13 @@ def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0):
             bbox = [0.0, 0.0, 0.0, 0.0]
         out.append({"id": first_id + i, "image_id": image_id, "category_id": int(packed.classes[i]), "segmentation": c.polygons(i),
                     "bbox": bbox, "area": float(packed.areas[i]), "iscrowd": 0, "score": float(packed.scores[i])})
+    if oriented:
+        from mnc_amd import shape
+        hulls = shape.hull_numpy(packed) if cpu else packed.hull()
+        rbox = (shape.oriented_numpy(packed, hulls) if cpu else packed.oriented_boxes()).rbox()
+        for i, solidity in enumerate(hulls.solidity(packed.areas)):
+            out[i]["rbox"] = [float(v) for v in rbox[i]] if hulls.area2[i] else None
+            out[i]["solidity"] = float(solidity)
     return out
 
 
@@ -319,7 +334,8 @@ def main(argv=None):
             if args.save_annotations:
                 image_entries.append({"id": name, "file_name": os.path.basename(path) if path else name, "height": int(im.shape[0]),
                                       "width": int(im.shape[1])})
-                annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode, args.polygon_epsilon))
+                annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode, args.polygon_epsilon,
+                                                     args.oriented_boxes))
             if args.save_masks:
                 out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, packed=packed)
                 print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
