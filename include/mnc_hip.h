@@ -735,6 +735,68 @@ MNC_API int mnc_mask_oriented(const int* bounds, const long long* offsets, const
 MNC_API int mnc_mask_shape_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n17 The set algebra of packed masks: and, or, xor, minus, copy and complement of two sets instance by instance, the union
+ *     or intersection of groups of instances, and the layering of a set into disjoint instances (csrc/mask_algebra.hip) --
+ *     on the layout of n5.  The statements of the rules are mnc_amd/algebra.py:combine_numpy, merge_numpy and layer_numpy.
+ *     Frame-free integer set arithmetic on lattice pixels: a mask is empty outside its bounds, bounds may be negative or
+ *     unclipped, input padding bits are not trusted.
+ *     Every result has the layout of n5 as mnc_mask_boundary writes it -- out_offsets are multiples of 8, in order without
+ *     gaps; out_areas are the true bit counts; padding bits are 0 -- and TIGHT bounds: the smallest box that holds the
+ *     instance's set pixels; an instance without a set pixel gets (0, 0, -1, -1) and no rows.
+ *     The size of a result depends on the data; an upper bound, *bits_bound, depends on the bounds alone: the bytes of the
+ *     LOOSE FRAMES.  The loose frame of an output instance is the intersection of the operands' bounds (and; an intersecting
+ *     merge), the hull of the bounds of the operands that have rows (or, xor; a uniting merge), a's own bounds (minus, copy,
+ *     layer) or the window (not), each intersected with the window where one is given.
+ *     Protocol, alike for the three entries: out_bits == NULL sets *bits_bound on the host and launches nothing (the other
+ *     outputs are not looked at); with bits_cap >= *bits_bound one call writes the tight result and sets *bits_bytes (and
+ *     *bits_bound); a smaller bits_cap is MNC_ERR_INVALID with only *bits_bound set.  Bytes past *bits_bytes are never written.
+ *     Three passes, five launches whatever the data, nothing read back in between: every lane forms a result word of the
+ *     loose frame from funnel-shifted reads of the operands' rows and the wave joins an integer min / max of the non-zero
+ *     rows and bit columns per instance; the extents become the result's table and a prefix sum places the offsets; one lane
+ *     per word of the tight frame evaluates the same expression again, writes its word once and the wave adds its popcount
+ *     to the area.  No floating point; integer atomics only: the same input gives the same bytes on every run.
+ *     Every entry takes a set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds.
+ *     n == 0, G == 0 and calls whose loose frames have no row are answered on the host.  MNC_ERR_INVALID, checked on the
+ *     host before anything is launched and with nothing written: everything mnc_mask_boundary refuses about a set (n outside
+ *     [0, 2048], |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or not a multiple of
+ *     8, rows that reach past bytes); more than 2^27 pixels of loose-frame rows in the call; a null pointer where one is
+ *     needed; and what the entries name below.  (There are no forms that read a device-resident mnc_mask_records result: the
+ *     PackedMasks methods fetch such a result first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Instance i of a with instance i of b (n_b == n_a) or with b's only instance (n_b == 1); n_b == 0: no b (its other arguments
+ * are not looked at).  op: 0 and, 1 or, 2 xor, 3 minus (a & ~b), 4 copy (a alone: tightens, or crops to the window), 5 not (the
+ * complement of a inside the window).  window: NULL or (x1, y1, x2, y2) inclusive, which the result is intersected with before
+ * it is tightened.  Outputs: out_bounds [n_a][4], out_offsets [n_a], out_areas [n_a], out_bits.  MNC_ERR_INVALID as above, and:
+ * op outside [0, 5]; n_b outside {0, 1, n_a}; op 0 .. 3 with n_b == 0 (and n_a > 0); op 5 without a window; a window coordinate
+ * with |c| >= 2^24; a window with x2 < x1 or y2 < y1. */
+MNC_API int mnc_mask_combine(const int* a_bounds, const long long* a_offsets, const void* a_bits, size_t a_bytes, int n_a,
+                             const int* b_bounds, const long long* b_offsets, const void* b_bits, size_t b_bytes, int n_b, int op,
+                             const int* window, int* out_bounds, long long* out_offsets, long long* out_areas, void* out_bits,
+                             size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id);
+/* One result instance per group g: the union (intersect == 0) or the intersection of the instances members[group_ptr[g] ..
+ * group_ptr[g + 1] - 1], indices into the set in any order, repeats allowed; a group without members gives an instance
+ * without a pixel either way.  Outputs [G].  MNC_ERR_INVALID as above, and: G outside [0, 2048]; group_ptr[0] != 0 or group_ptr
+ * not monotone; more than 2^20 members; a member outside [0, n - 1]. */
+MNC_API int mnc_mask_merge(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
+                           const long long* group_ptr, const int* members, int G, int intersect, int* out_bounds,
+                           long long* out_offsets, long long* out_areas, void* out_bits, size_t bits_cap, size_t* bits_bound,
+                           size_t* bits_bytes, int device_id);
+/* Instance i minus the union of every instance before it in the order: pairwise disjoint instances with the same union, in
+ * input index order.  order [n]: a permutation of 0 .. n - 1, first the instance that keeps all its pixels; NULL: by scores [n]
+ * descending, the lower index first on equal scores (mnc_mask_nms's order; scores is not looked at when order is given).
+ * Outputs [n].  The earlier instances whose bounds meet instance i's are listed on the host and uploaded with the set.
+ * MNC_ERR_INVALID as above, and: order that is not a permutation; neither order nor scores; a NaN score when the order comes
+ * from the scores. */
+MNC_API int mnc_mask_layer(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, const float* scores,
+                           const int* order, int* out_bounds, long long* out_offsets, long long* out_areas, void* out_bits,
+                           size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id);
+/* For tools/mask_algebra_bench.py.  on = 1: the following calls of the three entries above put a HIP event pair around their
+ * launches (without the copies of the set and of the results) and keep the last call's time in milliseconds; on = 0: they do
+ * not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on
+ * forgets it. */
+MNC_API int mnc_mask_algebra_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

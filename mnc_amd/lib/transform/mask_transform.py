@@ -318,6 +318,24 @@ def mask_oriented_boxes(pm):
     return pm.oriented_boxes(device_id=cfg.GPU_ID)
 
 
+def mask_combine(a, b, op, window=None):
+    """Two PackedMasks combined instance by instance on the GPU (mnc_mask_combine, csrc/mask_algebra.hip): op "and", "or",
+    "xor", "minus", "copy" or "not", an optional window (x1, y1, x2, y2) -> a host PackedMasks with tight bounds."""
+    return a.combine(b, op, window, device_id=cfg.GPU_ID)
+
+
+def mask_merge(pm, groups=None, intersect=False, by=None):
+    """The union (intersection) of groups of instances of a PackedMasks on the GPU (mnc_mask_merge): pycocotools' merge.  groups
+    None: everything in one group; by="class": one group per distinct class -> a host PackedMasks, one instance per group."""
+    return pm.merge(groups, intersect, by, device_id=cfg.GPU_ID)
+
+
+def mask_layered(pm, order=None):
+    """A PackedMasks made pairwise disjoint on the GPU (mnc_mask_layer): every pixel stays with the first instance in `order`
+    (None: descending score) that covers it -> a host PackedMasks in the input's index order."""
+    return pm.layered(order, device_id=cfg.GPU_ID)
+
+
 def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
                         ratio=0.02, return_iou=False):
     """mask_match on the overlap min(mask IoU, boundary IoU) in an H x W image -- COCO's iouType "boundary" -- on the GPU

@@ -22,6 +22,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        pixel of every instance, and the morphology by a disc (mnc_amd/distance.py, n15)
     PackedMasks.moments / .hull / .solidity / .oriented_boxes   the moments of order up to two, the convex hull, the rectangle of
                                        least area and the diameter (mnc_amd/shape.py, n16)
+    PackedMasks.combine / & | ^ - / .tighten / .crop / .complement / .merge / .layered   the set algebra: two sets instance by
+                                       instance, groups united or intersected, a set made disjoint (mnc_amd/algebra.py, n17)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -318,6 +320,65 @@ class PackedMasks(object):
         mnc_mask_oriented (hull and calipers in one call).  A device-resident result is fetched to the host first."""
         from . import shape
         return shape.oriented(self, device_id)
+
+    def combine(self, other, op, window=None, device_id=None):
+        """These masks combined with `other` instance by instance (len(other) == len(self), or 1: that instance against every
+        one) -> a host PackedMasks with tight bounds and this one's classes and scores.  op "and", "or", "xor", "minus" (self &
+        ~other), "copy" or "not" (other is not looked at: this set tightened or cropped, resp. its complement inside the
+        window, which "not" requires); window (x1, y1, x2, y2), inclusive, cuts the result.  By the rule of
+        mnc_amd.algebra.combine_numpy (include/mnc_hip.h n17, csrc/mask_algebra.hip) on the GPU.  Device-resident results are
+        fetched to the host first."""
+        from . import algebra
+        return algebra.combine(self, other, op, window, device_id)
+
+    def __and__(self, other):
+        return self.combine(other, "and")
+
+    def __or__(self, other):
+        return self.combine(other, "or")
+
+    def __xor__(self, other):
+        return self.combine(other, "xor")
+
+    def __sub__(self, other):
+        return self.combine(other, "minus")
+
+    def tighten(self, device_id=None):
+        """These masks with tight bounds -- the smallest box of every instance's set pixels, (0, 0, -1, -1) and no rows for one
+        without a pixel -- and the canonical layout (padding bits 0, true areas): combine's "copy" without a window."""
+        return self.combine(None, "copy", None, device_id)
+
+    def crop(self, x1, y1, x2, y2, device_id=None):
+        """These masks intersected with the window (x1, y1, x2, y2), inclusive, tight bounds: combine's "copy" in the window."""
+        return self.combine(None, "copy", (x1, y1, x2, y2), device_id)
+
+    def complement(self, H, W, device_id=None):
+        """The pixels of the H x W image that every instance does not have, tight bounds: combine's "not" in the window (0, 0,
+        W - 1, H - 1)."""
+        return self.combine(None, "not", (0, 0, int(W) - 1, int(H) - 1), device_id)
+
+    def merge(self, groups=None, intersect=False, by=None, device_id=None):
+        """One instance per group of instances: their union, or with intersect their intersection (pycocotools' merge) -> a host
+        PackedMasks with tight bounds, the class and score of every group's first member.  groups: a list of index lists (any
+        order, repeats allowed, an empty list gives an empty instance); None: everything in one group; by="class": one group
+        per distinct class in ascending class order -- the per-class semantic masks.  By the rule of
+        mnc_amd.algebra.merge_numpy through mnc_mask_merge.  A device-resident result is fetched to the host first."""
+        from . import algebra
+        if by is not None:
+            if by != "class" or groups is not None:
+                raise ValueError("merge: by=%r is not \"class\", or groups were given as well" % (by,))
+            groups = algebra.class_groups(self.classes)[1]
+        elif groups is None:
+            groups = [np.arange(len(self))]
+        return algebra.merge(self, *algebra.groups_csr(groups), intersect=intersect, device_id=device_id)
+
+    def layered(self, order=None, device_id=None):
+        """These instances made pairwise disjoint: each minus the union of every instance before it in `order` (a permutation;
+        None: descending score, the lower index first on equal scores -- nms()'s order), so that every pixel belongs to the best
+        instance that covers it -> a host PackedMasks of len(self) instances in this order of indices, tight bounds, by the rule
+        of mnc_amd.algebra.layer_numpy through mnc_mask_layer.  A device-resident result is fetched to the host first."""
+        from . import algebra
+        return algebra.layer(self, order, device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

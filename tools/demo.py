@@ -5,7 +5,7 @@ optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
                          [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes]]
-                         [--min-component-area A [--largest-component]] [--smooth-radius R]
+                         [--min-component-area A [--largest-component]] [--smooth-radius R] [--exclusive]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -25,7 +25,10 @@ staircase go.  It runs before the component selection -- an opening can cut a ne
 default, leaves the masks as they are.  --oriented-boxes adds to every annotation of --save-annotations "rbox": [cx, cy, w, h, angle]
 -- the rectangle of least area around the written mask, the angle in degrees from +x towards +y (OrientedBoxes.rbox of
 PackedMasks.oriented_boxes, csrc/mask_shape.hip; with --cpu mnc_amd.shape.oriented_numpy; null for a mask without a pixel) -- and
-"solidity", its pixel count over the area of its convex hull; without the flag the file is what it was."""
+"solidity", its pixel count over the area of its convex hull; without the flag the file is what it was.  --exclusive makes the
+written instances of an image pairwise disjoint: every pixel stays with the best-scoring instance that covers it
+(PackedMasks.layered, csrc/mask_algebra.hip; with --cpu mnc_amd.algebra.layer_numpy), which is what the COCO panoptic format and an
+object PNG want.  It runs after --smooth-radius and before the component selection, and leaves every instance tight bounds."""
 import argparse
 import os
 import time
@@ -80,6 +83,9 @@ def parse_args(argv=None):
     p.add_argument("--smooth-radius", dest="smooth_radius", default=0.0, type=float, metavar="R",
                    help="open, then close the masks --save-masks / --save-coco / --save-annotations write by the disc of radius R, "
                         "before the component selection [0: off]")
+    p.add_argument("--exclusive", dest="exclusive", action="store_true",
+                   help="make the masks --save-masks / --save-coco / --save-annotations write pairwise disjoint: each pixel goes to "
+                        "the best-scoring instance that covers it; after --smooth-radius, before the component selection")
     return p.parse_args(argv)
 
 
@@ -209,6 +215,13 @@ def _smooth(packed, radius, cpu=False):
     return packed.open(r2=r2).close(r2=r2)
 
 
+def _exclusive(packed, cpu=False):
+    """The written masks made pairwise disjoint, each minus every better-scoring one (on the GPU, csrc/mask_algebra.hip; cpu=True:
+    the numpy statement).  A device-resident result is fetched first."""
+    from mnc_amd import algebra
+    return algebra.layer_numpy(packed.fetch()) if cpu else packed.layered()
+
+
 def _coco_results(image_id, im_shape, packed, cpu=False):
     """-> COCO result entries of one image's PackedMasks: the mask run-length encoded in the image (on the GPU where the masks
     lie, csrc/mask_rle.hip; cpu=True: mnc_amd.rle's numpy statement), bbox = [x, y, w, h] of the tight box of its pixels."""
@@ -327,6 +340,8 @@ def main(argv=None):
                                    args.cpu_mode)
             if args.smooth_radius > 0:
                 packed = _smooth(packed, args.smooth_radius, args.cpu_mode)
+            if args.exclusive:
+                packed = _exclusive(packed, args.cpu_mode)
             if args.min_component_area > 0 or args.largest_component:
                 packed = _select_components(packed, args.min_component_area, args.largest_component, args.cpu_mode)
             if args.save_coco:                                    # (first: a device-resident result is encoded where it lies)
