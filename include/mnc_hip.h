@@ -797,6 +797,57 @@ MNC_API int mnc_mask_layer(const int* bounds, const long long* offsets, const vo
 MNC_API int mnc_mask_algebra_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n18 Geometric transforms of packed masks: the eight lattice isometries plus a translation -- flips, the transpose, the
+ *     rotations by quarter turns -- and the nearest-neighbour gather through an integer affine inverse map -- resize, rotate,
+ *     shear (csrc/mask_warp.hip) -- on the layout of n5.  The statements of the rules are mnc_amd/warp.py:isometry_numpy and
+ *     warp_numpy.  Frame-free integer arithmetic on lattice pixels: a mask is empty outside its bounds, bounds may be negative
+ *     or unclipped, input padding bits are not trusted.  Output instance i is the image of input instance i.
+ *     Every result has the layout and the TIGHT bounds of n17: out_offsets multiples of 8, in order without gaps; out_areas
+ *     the true bit counts; padding bits 0; (0, 0, -1, -1) and no rows for an instance without a set pixel.
+ *     The protocol is n17's, unchanged: out_bits == NULL sets *bits_bound -- the bytes of the LOOSE FRAMES, which follow from
+ *     the bounds, the map and the window alone -- on the host and launches nothing; with bits_cap >= *bits_bound one call
+ *     writes the tight result and sets *bits_bytes; a smaller bits_cap is MNC_ERR_INVALID with only *bits_bound set.  Bytes
+ *     past *bits_bytes are never written.
+ *     Three passes, five launches whatever the data, nothing read back in between: a wave forms a 64 x 64 bit block of the
+ *     loose frame and joins an integer min / max of its non-zero rows and bit columns per instance; the extents become the
+ *     result's table and a prefix sum places the offsets; a wave per block of the tight frame evaluates the same expression
+ *     again, writes each word once and adds its popcount to the area.  No floating point; integer atomics only: the same
+ *     input gives the same bytes on every run.
+ *     n == 0 and calls whose loose frames have no row are answered on the host.  MNC_ERR_INVALID, checked on the host before
+ *     anything is launched and with nothing written: everything mnc_mask_combine refuses about a set; more than 2^27 pixels
+ *     of loose-frame rows in the call; a null pointer where one is needed; and what the entries name below.  (There are no
+ *     forms that read a device-resident mnc_mask_records result: the PackedMasks methods fetch such a result first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* A set pixel (x, y) goes to (x', y'):  (u, v) = (y, x) if code & 1, else (x, y);  u = -u if code & 2;  v = -v if code & 4;
+ * (x', y') = (u + tx, v + ty).  In an H x W image np.fliplr is (2, W - 1, 0), np.flipud (4, 0, H - 1), the transpose (1, 0, 0),
+ * np.rot90 by k = 1, 2, 3 quarter turns (5, 0, W - 1), (6, W - 1, H - 1), (3, H - 1, 0).  The loose frame of an instance is the
+ * image of its bounds.  Codes without bit 0 read each result word from one funnel-shifted (and bit-reversed) word of a source
+ * row; codes with bit 0 transpose 64 x 64 bit blocks with ballots.  Outputs [n].  MNC_ERR_INVALID as above, and: code outside
+ * [0, 7]; |tx| or |ty| >= 2^24; a coordinate of the image of an instance's bounds with |c| >= 2^24. */
+MNC_API int mnc_mask_isometry(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int code, int tx,
+                              int ty, int* out_bounds, long long* out_offsets, long long* out_areas, void* out_bits,
+                              size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id);
+/* Destination pixel (x, y) inside window = (x1, y1, x2, y2), inclusive, is set iff source pixel (sx, sy) is set in the
+ * instance: sx = floor((coef[0] x + coef[1] y + coef[2]) / den), sy = floor((coef[3] x + coef[4] y + coef[5]) / den), the floor
+ * towards minus infinity, the numerators in int64.  One denominator serves both axes: a map whose axes have denominators of
+ * their own (the centre-aligned resize, sx = floor((2x + 1) W / (2 W2)), sy = floor((2y + 1) H / (2 H2))) is brought to one by
+ * cross-multiplying, coef = (4 W H2, 0, 2 W H2, 0, 4 H W2, 2 H W2) over den = 4 W2 H2, which a common factor may be divided out
+ * of (mnc_amd/warp.py:resize_map).  The loose frame of an instance is the box, floor of the least and ceiling of the greatest
+ * coordinate, of the parallelogram x1 den <= coef[0] x + coef[1] y + coef[2] <= (x2 + 1) den - 1 (alike in y) of destination
+ * pixels whose source lies in its bounds (x1, y1, x2, y2) -- its corners solved exactly as rationals over det = coef[0] coef[4]
+ * - coef[1] coef[3] in 128-bit integers -- intersected with the window.  Outputs [n].  MNC_ERR_INVALID as above, and: den outside
+ * [1, 2^32]; |coef[0]|, |coef[1]|, |coef[3]| or |coef[4]| > 2^32; |coef[2]| or |coef[5]| > 2^60 (every numerator stays below
+ * 2^62); det == 0; a window coordinate with |c| >= 2^24; a window with x2 < x1 or y2 < y1. */
+MNC_API int mnc_mask_warp(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, const long long* coef,
+                          long long den, const int* window, int* out_bounds, long long* out_offsets, long long* out_areas,
+                          void* out_bits, size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id);
+/* For tools/mask_warp_bench.py.  on = 1: the following calls of the two entries above put a HIP event pair around their
+ * launches (without the copies of the set and of the results) and keep the last call's time in milliseconds; on = 0: they do
+ * not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on
+ * forgets it. */
+MNC_API int mnc_mask_warp_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

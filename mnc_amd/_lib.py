@@ -21,7 +21,7 @@ class MncError(RuntimeError):
 
 _CTYPES = {
     "int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
-    "long": ctypes.c_long,
+    "long": ctypes.c_long, "long long": ctypes.c_longlong,
     "void": None,
 }
 

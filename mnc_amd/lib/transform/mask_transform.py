@@ -336,6 +336,49 @@ def mask_layered(pm, order=None):
     return pm.layered(order, device_id=cfg.GPU_ID)
 
 
+def mask_isometry(pm, code, tx=0, ty=0):
+    """A lattice isometry plus a translation of a PackedMasks on the GPU (mnc_mask_isometry, csrc/mask_warp.hip) -> a host
+    PackedMasks with tight bounds."""
+    return pm.isometry(code, tx, ty, device_id=cfg.GPU_ID)
+
+
+def mask_fliplr(pm, W):
+    """A PackedMasks mirrored left to right in an image W wide on the GPU (mnc_mask_isometry)."""
+    return pm.fliplr(W, device_id=cfg.GPU_ID)
+
+
+def mask_flipud(pm, H):
+    """A PackedMasks mirrored top to bottom in an image H high on the GPU (mnc_mask_isometry)."""
+    return pm.flipud(H, device_id=cfg.GPU_ID)
+
+
+def mask_transpose(pm):
+    """A PackedMasks with x and y exchanged on the GPU (mnc_mask_isometry)."""
+    return pm.transpose(device_id=cfg.GPU_ID)
+
+
+def mask_rot90(pm, k, H, W):
+    """A PackedMasks of an H x W image turned by k quarter turns in numpy's direction on the GPU (mnc_mask_isometry)."""
+    return pm.rot90(k, H, W, device_id=cfg.GPU_ID)
+
+
+def mask_resize(pm, H, W, H2, W2):
+    """A PackedMasks of an H x W image in its centre-aligned nearest-neighbour resize to H2 x W2 on the GPU (mnc_mask_warp)."""
+    return pm.resize(H, W, H2, W2, device_id=cfg.GPU_ID)
+
+
+def mask_warp_affine(pm, M, H2, W2, frac_bits=16, inverse=False):
+    """A PackedMasks under a 2 x 3 matrix in cv2.warpAffine's convention, nearest neighbour, into an H2 x W2 image on the GPU
+    (mnc_mask_warp)."""
+    return pm.warp_affine(M, H2, W2, frac_bits, inverse, device_id=cfg.GPU_ID)
+
+
+def mask_warp(pm, coef, den, window):
+    """The nearest-neighbour gather of a PackedMasks through an integer affine inverse map on the GPU (mnc_mask_warp) -> a host
+    PackedMasks with tight bounds inside the window."""
+    return pm.warp(coef, den, window, device_id=cfg.GPU_ID)
+
+
 def mask_match_boundary(dt, gt, H, W, iscrowd=None, ignore=None, eval_area=None, iou_thrs=None, area_rngs=None, max_det=100, d=None,
                         ratio=0.02, return_iou=False):
     """mask_match on the overlap min(mask IoU, boundary IoU) in an H x W image -- COCO's iouType "boundary" -- on the GPU

@@ -24,6 +24,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        least area and the diameter (mnc_amd/shape.py, n16)
     PackedMasks.combine / & | ^ - / .tighten / .crop / .complement / .merge / .layered   the set algebra: two sets instance by
                                        instance, groups united or intersected, a set made disjoint (mnc_amd/algebra.py, n17)
+    PackedMasks.translate / .fliplr / .flipud / .transpose / .rot90 / .isometry / .resize / .warp_affine / .warp   the geometric
+                                       transforms: flips, quarter turns, and nearest-neighbour affine maps (mnc_amd/warp.py, n18)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -379,6 +381,58 @@ class PackedMasks(object):
         of mnc_amd.algebra.layer_numpy through mnc_mask_layer.  A device-resident result is fetched to the host first."""
         from . import algebra
         return algebra.layer(self, order, device_id)
+
+    def translate(self, dx, dy):
+        """These masks moved by (dx, dy) -> a host PackedMasks: arithmetic on the bounds, no bit is touched and nothing is
+        tightened (mnc_amd.warp.translate)."""
+        from . import warp
+        return warp.translate(self, dx, dy)
+
+    def isometry(self, code, tx=0, ty=0, device_id=None):
+        """A lattice isometry and a translation: pixel (x, y) goes to (u + tx, v + ty) with (u, v) = (y, x) if code & 1 else (x, y),
+        u negated if code & 2, v negated if code & 4 -> a host PackedMasks with tight bounds, by the rule of
+        mnc_amd.warp.isometry_numpy (include/mnc_hip.h n18, csrc/mask_warp.hip) on the GPU.  A device-resident result is fetched
+        to the host first."""
+        from . import warp
+        return warp.isometry(self, code, tx, ty, device_id)
+
+    def fliplr(self, W, device_id=None):
+        """These masks mirrored left to right in an image W wide (np.fliplr of full(i, H, W)): isometry(2, W - 1, 0)."""
+        return self.isometry(2, int(W) - 1, 0, device_id)
+
+    def flipud(self, H, device_id=None):
+        """These masks mirrored top to bottom in an image H high (np.flipud): isometry(4, 0, H - 1)."""
+        return self.isometry(4, 0, int(H) - 1, device_id)
+
+    def transpose(self, device_id=None):
+        """These masks with x and y exchanged (.T of full(i, H, W)): isometry(1, 0, 0)."""
+        return self.isometry(1, 0, 0, device_id)
+
+    def rot90(self, k, H, W, device_id=None):
+        """These masks of an H x W image turned by k quarter turns in numpy's direction (np.rot90(full(i, H, W), k)), any integer
+        k; an odd k gives masks of a W x H image."""
+        from . import warp
+        return self.isometry(*warp.rot90_code(k, H, W), device_id=device_id)
+
+    def warp(self, coef, den, window, device_id=None):
+        """The nearest-neighbour gather through an integer affine inverse map: destination pixel (x, y) of window = (x1, y1, x2, y2),
+        inclusive, is set iff source pixel ((c0 x + c1 y + c2) // den, (c3 x + c4 y + c5) // den) is -> a host PackedMasks with
+        tight bounds, by the rule of mnc_amd.warp.warp_numpy through mnc_mask_warp.  A device-resident result is fetched to the
+        host first."""
+        from . import warp
+        return warp.warp(self, coef, den, window, device_id)
+
+    def resize(self, H, W, H2, W2, device_id=None):
+        """These masks of an H x W image in its centre-aligned nearest-neighbour resize to H2 x W2 (mnc_amd.warp.resize_map): warp
+        in the window of the new image."""
+        from . import warp
+        return warp.warp(self, *warp.resize_map(H, W, H2, W2), window=(0, 0, int(W2) - 1, int(H2) - 1), device_id=device_id)
+
+    def warp_affine(self, M, H2, W2, frac_bits=16, inverse=False, device_id=None):
+        """These masks under the 2 x 3 float64 matrix M in cv2.warpAffine's convention, nearest neighbour, into an H2 x W2 image:
+        warp by mnc_amd.warp.affine_map(M, frac_bits, inverse) in the window of that image."""
+        from . import warp
+        return warp.warp(self, *warp.affine_map(M, frac_bits, inverse), window=(0, 0, int(W2) - 1, int(H2) - 1), device_id=device_id)
 
     def rle_counts(self, H, W, device_id=None):
         """(run_ptr int64 [n + 1], runs uint32): the COCO run-length counts of every instance in an H x W image, column-major

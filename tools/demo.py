@@ -6,6 +6,7 @@ optional visualisation.
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
                          [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes]]
                          [--min-component-area A [--largest-component]] [--smooth-radius R] [--exclusive]
+                         [--flip-tta [--tta-nms T]]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -28,7 +29,11 @@ PackedMasks.oriented_boxes, csrc/mask_shape.hip; with --cpu mnc_amd.shape.orient
 "solidity", its pixel count over the area of its convex hull; without the flag the file is what it was.  --exclusive makes the
 written instances of an image pairwise disjoint: every pixel stays with the best-scoring instance that covers it
 (PackedMasks.layered, csrc/mask_algebra.hip; with --cpu mnc_amd.algebra.layer_numpy), which is what the COCO panoptic format and an
-object PNG want.  It runs after --smooth-radius and before the component selection, and leaves every instance tight bounds."""
+object PNG want.  It runs after --smooth-radius and before the component selection, and leaves every instance tight bounds.
+--flip-tta is test-time augmentation by the mirror image: every image is also run mirrored (im[:, ::-1]), the mirrored run's packed
+masks are flipped back into the image's frame (PackedMasks.fliplr, csrc/mask_warp.hip; with --cpu mnc_amd.warp.isometry_numpy), the
+two sets are concatenated and reduced by the class-aware mask NMS at IoU --tta-nms (default 0.5), before everything above.  Off by
+default; without the flag the output is what it was."""
 import argparse
 import os
 import time
@@ -86,6 +91,11 @@ def parse_args(argv=None):
     p.add_argument("--exclusive", dest="exclusive", action="store_true",
                    help="make the masks --save-masks / --save-coco / --save-annotations write pairwise disjoint: each pixel goes to "
                         "the best-scoring instance that covers it; after --smooth-radius, before the component selection")
+    p.add_argument("--flip-tta", dest="flip_tta", action="store_true",
+                   help="also run every image mirrored, flip its masks back and merge the two sets by class-aware mask NMS, before "
+                        "--smooth-radius, --exclusive and the component selection")
+    p.add_argument("--tta-nms", dest="tta_nms", default=0.5, type=float, metavar="T",
+                   help="mask IoU above which --flip-tta drops the lower-scoring of two instances of a class [0.5]")
     return p.parse_args(argv)
 
 
@@ -222,6 +232,23 @@ def _exclusive(packed, cpu=False):
     return algebra.layer_numpy(packed.fetch()) if cpu else packed.layered()
 
 
+def _flip_tta(packed, mirrored, width, thresh=0.5, cpu=False):
+    """The masks of an image merged with those of its mirror image: `mirrored` flipped back into the frame of the image `width`
+    wide (on the GPU, csrc/mask_warp.hip; cpu=True: the numpy statement), the two sets concatenated, and the class-aware mask NMS
+    at IoU `thresh` over both (cpu=True: mask_nms_numpy) -> a host PackedMasks of the kept instances, those of `packed` first,
+    each part in its own order.  Device-resident results are fetched first."""
+    from mnc_amd import warp
+    from mnc_amd.masks import PackedMasks, mask_nms_numpy, merge_sets
+    packed, mirrored = packed.fetch(), mirrored.fetch()
+    back = warp.isometry_numpy(mirrored, 2, int(width) - 1, 0) if cpu else mirrored.fliplr(width)
+    parts = (packed, back)
+    bounds, offsets, areas, bits = merge_sets(parts, [(p, i) for p in (0, 1) for i in range(len(parts[p]))])
+    both = PackedMasks(bounds, offsets, areas, np.concatenate((packed.classes, back.classes)),
+                       np.concatenate((packed.scores, back.scores)), bits)
+    keep = mask_nms_numpy(both, thresh, class_aware=True) if cpu else both.nms(thresh, class_aware=True)
+    return both.take(np.sort(keep))
+
+
 def _coco_results(image_id, im_shape, packed, cpu=False):
     """-> COCO result entries of one image's PackedMasks: the mask run-length encoded in the image (on the GPU where the masks
     lie, csrc/mask_rle.hip; cpu=True: mnc_amd.rle's numpy statement), bbox = [x, y, w, h] of the tight box of its pixels."""
@@ -338,6 +365,15 @@ def main(argv=None):
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
             packed = _packed_masks(im.shape, result_mask, result_box, blk.view() if blk is not None else None, args.vis_thresh,
                                    args.cpu_mode)
+            if args.flip_tta:
+                packed = packed.fetch()                           # (the mirrored run reuses the device buffers)
+                m_boxes, m_masks, m_scores = im_detect(np.ascontiguousarray(im[:, ::-1]), net)
+                m_mask, m_box = gpu_mask_voting(m_masks, m_boxes, m_scores, len(CLASSES) + 1, 100, im.shape[1], im.shape[0])
+                m_blk = getattr(m_boxes._net, "_inst", None) if isinstance(m_boxes, DeviceArray) else None
+                mirrored = _packed_masks(im.shape, m_mask, m_box, m_blk.view() if m_blk is not None else None, args.vis_thresh,
+                                         args.cpu_mode)
+                packed = _flip_tta(packed, mirrored, im.shape[1], args.tta_nms, args.cpu_mode)
+                print("%d instances after merging with the mirrored run" % len(packed))
             if args.smooth_radius > 0:
                 packed = _smooth(packed, args.smooth_radius, args.cpu_mode)
             if args.exclusive:
@@ -363,7 +399,9 @@ def main(argv=None):
             # fetched for the count above) only places the text labels
             from mnc_amd.devarray import DeviceArray
             blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
-            view = blk.view() if cfg.TEST.USE_GPU_VIS and blk is not None and im.dtype == np.uint8 else None
+            # (after --flip-tta's mirrored run the block holds the mirror image's records: the overlay then is the host's)
+            flipped = args.flip_tta and (args.save_masks or args.save_coco or args.save_annotations)
+            view = blk.view() if cfg.TEST.USE_GPU_VIS and blk is not None and im.dtype == np.uint8 and not flipped else None
             _visualise(im, pred, out, view, args.vis_thresh)
             print("wrote", out)
     if args.save_coco:
