@@ -15,67 +15,42 @@
 // through mask_word_at (funnel shift of two neighbouring words, padding bits masked, 0 outside the row), a row outside an
 // operand's bounds reads 0, and the frame -- which already is intersected with the window -- is applied as a word mask.
 //
-//   al_extent_kernel   one lane per word of the loose frame: al_word, then the word's row and its lowest and highest set column
-//                      (ctz / clz), reduced over the wave by shuffles and joined by integer atomicMin / atomicMax into four
-//                      extents per instance, relative to the frame.
-//   al_size_kernel     one lane per instance: the tight bounds from the extents ((0, 0, -1, -1) when no word was non-zero) and
-//                      the words of its rows; scan_launch (scan.h) turns the counts into the offsets.
-//   al_fill_kernel     one lane per word of the TIGHT frame (the grid is sized for the loose one; lanes past the tight words
-//                      leave): al_word again at the tight position, stored once; the popcounts are summed over the wave and
-//                      added to the instance's area by one integer atomic.
-// Five launches whatever the data, nothing read back in between; the tight bounds and the areas come back first, the host derives
-// the offsets from the bounds exactly as the scan did, and copies exactly the bytes of the result.  The only atomics are integer
-// min, max and add: the same input gives the same bytes on every run.
+// The result is tight and its size depends on the data: the protocol, its five launches and its driver are mask_tight.h's.  Here
+// the unit of work is a lane per word:
+//   al_extent_kernel   one lane per word of the loose frame: al_word, then tight_join.
+//   al_fill_kernel     one lane per word of the TIGHT frame: al_word again at the tight position, stored once, then tight_count.
 //
 // Bound: latency.  100 instances of an image are a few hundred KB of words that sit in L2; a lane reads at most two words per
 // operand and row.  A merge reads every member per output word, a layer every listed neighbour.  Measured at 100 instances of a
-// 600 x 1000 image, call with its copies / kernels alone: a | b 0.24 ms / 27 us, merge(by="class") 0.24 ms / 71 us (a class's frame
-// is nearly the image and every word reads 25 members), layered() 0.16 ms / 26 us (profiles/mask_algebra_bench.txt).  20 VGPRs, no
+// 600 x 1000 image, call with its copies / kernels alone: a | b 0.24 ms / 27 us, merge(by="class") 0.21 ms / 69 us (a class's frame
+// is nearly the image and every word reads 25 members), layered() 0.15 ms / 26 us (profiles/mask_algebra_bench.txt).  20 VGPRs, no
 // LDS and no scratch in any kernel.
 #include <algorithm>
 #include <climits>
 #include <vector>
 
-#include "mask_set.h"
-#include "scan.h"
+#include "mask_tight.h"
 
 namespace mnc {
 
 constexpr int kAlThreads = 256;
-constexpr int kAlMaxN = 2048;                  // instances of a set and of a result (mnc_mask_boundary's limit)
-constexpr int kAlMaxCoord = 1 << 24;
-constexpr long long kAlMaxPixels = 1ll << 27;  // pixels of the loose frames of one call
 constexpr long long kAlMaxMembers = 1ll << 20;
 
 enum AlOp { kAlAnd = 0, kAlOr = 1, kAlXor = 2, kAlMinus = 3, kAlCopy = 4, kAlNot = 5 };
 
-// One output instance: the loose frame (fw or fh 0: no pixel, skipped by every kernel), the operand of A (-1: none) and the list.
-struct AlJob {
-  int fx, fy, fw, fh;
-  int a, lo, hi, pad_;
+// One output instance: its loose frame, the operand of A (-1: none) and the list.  The frame stays the head of the job -- one
+// table, one copy and one 32-byte read per lane -- and tight_size_kernel steps over the rest.
+struct AlJob : TightFrame {
+  int a = -1, lo = 0, hi = 0, pad_ = 0;
 };
-
-// Extents relative to the frame (al_extent_kernel; maxx < 0: no pixel), then the tight bounds in image coordinates (al_size_kernel).
-struct AlBox {
-  int x1, y1, x2, y2;
-};
-
-// The 64 bits of instance i from image column x on, in image row y: 0 outside its bounds.
-__device__ __forceinline__ u64 al_read(const mnc_mask_info* __restrict__ info, const u64* __restrict__ bits, int i, int x, int y) {
-  const mnc_mask_info& m = info[i];
-  const int x1 = m.x1, y1 = m.y1, w = m.x2 - x1 + 1;
-  if (w < 1 || y < y1 || y > m.y2) return 0ull;
-  const int strips = mask_strips(w);
-  return mask_word_at(bits + m.offset / 8 + (long long)(y - y1) * strips, x - x1, strips, w);
-}
 
 // The 64 result bits of job j from image column x >= j.fx on, in image row y of the frame.  Both passes call it.
 __device__ __forceinline__ u64 al_word(const AlJob& j, const MaskSet& A, const MaskSet& B, const int* __restrict__ idx, int op, int all,
                                        int x, int y) {
-  const u64 p = j.a >= 0 ? al_read(A.info, A.bits, j.a, x, y) : 0ull;
+  const u64 p = j.a >= 0 ? mask_read(A.info[j.a], A.bits, x, y) : 0ull;
   u64 q = all ? ~0ull : 0ull;
   for (int k = j.lo; k < j.hi; ++k) {
-    const u64 r = al_read(B.info, B.bits, idx[k], x, y);
+    const u64 r = mask_read(B.info[idx[k]], B.bits, x, y);
     q = all ? q & r : q | r;
   }
   u64 v = op == kAlAnd ? p & q : op == kAlOr ? p | q : op == kAlXor ? p ^ q : op == kAlMinus ? p & ~q : op == kAlCopy ? p : ~p;
@@ -86,199 +61,89 @@ __device__ __forceinline__ u64 al_word(const AlJob& j, const MaskSet& A, const M
 
 // grid (ceil(most loose-frame words / 256), jobs), block 256: a lane per word of the loose frame.
 __global__ __launch_bounds__(kAlThreads) void al_extent_kernel(const AlJob* __restrict__ jobs, MaskSet A, MaskSet B,
-                                                               const int* __restrict__ idx, int op, int all, AlBox* __restrict__ ext) {
+                                                               const int* __restrict__ idx, int op, int all, TightBox* __restrict__ ext) {
   const int o = blockIdx.y;
   const AlJob j = jobs[o];
   if (j.fw < 1 || j.fh < 1) return;
   const int strips = mask_strips(j.fw);
   const long long t = (long long)blockIdx.x * kAlThreads + threadIdx.x;
-  int minx = INT_MAX, miny = INT_MAX, maxx = -1, maxy = -1;
+  int y = 0, c = 0;
+  u64 v = 0ull;
   if (t < (long long)j.fh * strips) {
-    const int y = (int)(t / strips), c = (int)(t - (long long)y * strips);
-    const u64 v = al_word(j, A, B, idx, op, all, j.fx + c * 64, j.fy + y);
-    if (v) {
-      minx = c * 64 + (__ffsll((long long)v) - 1);
-      maxx = c * 64 + 63 - __clzll((long long)v);
-      miny = maxy = y;
-    }
+    y = (int)(t / strips);
+    c = (int)(t - (long long)y * strips);
+    v = al_word(j, A, B, idx, op, all, j.fx + c * 64, j.fy + y);
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    minx = min(minx, __shfl_xor(minx, s));
-    miny = min(miny, __shfl_xor(miny, s));
-    maxx = max(maxx, __shfl_xor(maxx, s));
-    maxy = max(maxy, __shfl_xor(maxy, s));
-  }
-  if ((threadIdx.x & 63) == 0 && maxx >= 0) {
-    atomicMin(&ext[o].x1, minx);
-    atomicMin(&ext[o].y1, miny);
-    atomicMax(&ext[o].x2, maxx);
-    atomicMax(&ext[o].y2, maxy);
-  }
-}
-
-// grid ceil(jobs / 256), block 256: the extents in place into the tight bounds, and the words of their rows.
-__global__ __launch_bounds__(kAlThreads) void al_size_kernel(const AlJob* __restrict__ jobs, int n, AlBox* __restrict__ box,
-                                                             int* __restrict__ words) {
-  const int o = blockIdx.x * kAlThreads + threadIdx.x;
-  if (o >= n) return;
-  const AlJob j = jobs[o];
-  const AlBox e = box[o];
-  AlBox b = {0, 0, -1, -1};
-  int count = 0;
-  if (j.fw >= 1 && j.fh >= 1 && e.x2 >= 0) {
-    b.x1 = j.fx + e.x1; b.y1 = j.fy + e.y1; b.x2 = j.fx + e.x2; b.y2 = j.fy + e.y2;
-    count = (e.y2 - e.y1 + 1) * mask_strips(e.x2 - e.x1 + 1);      // (at most the 2^27 words of the call's loose frames)
-  }
-  box[o] = b;
-  words[o] = count;
+  tight_join(ext + o, v, c * 64, y);
 }
 
 // grid (ceil(most loose-frame words / 256), jobs), block 256: a lane per word of the tight frame.
 __global__ __launch_bounds__(kAlThreads) void al_fill_kernel(const AlJob* __restrict__ jobs, MaskSet A, MaskSet B,
-                                                             const int* __restrict__ idx, int op, int all, const AlBox* __restrict__ box,
-                                                             Scanned first, u64* __restrict__ out, u64* __restrict__ area) {
+                                                             const int* __restrict__ idx, int op, int all,
+                                                             const TightBox* __restrict__ box, Scanned first, u64* __restrict__ out,
+                                                             u64* __restrict__ area) {
   const int o = blockIdx.y;
-  const AlBox b = box[o];
+  const TightBox b = box[o];
   if (b.x2 < b.x1) return;
   const AlJob j = jobs[o];
   const int strips = mask_strips(b.x2 - b.x1 + 1);
   const long long t = (long long)blockIdx.x * kAlThreads + threadIdx.x;
   const bool live = t < (long long)(b.y2 - b.y1 + 1) * strips;
   if (__ballot(live) == 0ull) return;                      // (the whole wave)
-  int set = 0;
+  u64 v = 0ull;
   if (live) {
     const int y = (int)(t / strips), c = (int)(t - (long long)y * strips);
-    const u64 v = al_word(j, A, B, idx, op, all, b.x1 + c * 64, b.y1 + y);
+    v = al_word(j, A, B, idx, op, all, b.x1 + c * 64, b.y1 + y);
     out[(long long)first.at(o) + t] = v;
-    set = __popcll(v);
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) set += __shfl_xor(set, s);
-  if ((threadIdx.x & 63) == 0 && set) atomicAdd(&area[o], (u64)set);
+  tight_count(area + o, v);
 }
 
 namespace {
 
-inline bool al_rows(const mnc_mask_info& a) { return a.x2 >= a.x1 && a.y2 >= a.y1; }
-
-// The jobs of one call and what its launches need.
-struct AlCall {
-  std::vector<AlJob> jobs;
+// One call (mask_tight.h): the jobs, and beside them the sets (B null: A is B), the lists of the jobs and the expression.
+struct AlCall : TightCall<AlJob> {
+  HostMaskSet& A;
+  HostMaskSet* B;
   std::vector<int> idx;
+  int* d_idx = nullptr;
   int op = kAlOr, all = 0;
-  const int* window = nullptr;
-  long long most_words = 0, bound_words = 0, pixels = 0;
+  AlCall(HostMaskSet& a, HostMaskSet* b) : A(a), B(b) {}
   // The job of the next output instance: the frame (x1, y1, x2, y2) intersected with the window.
   void add(int x1, int y1, int x2, int y2, int a, long long lo, long long hi) {
-    if (window) {
-      x1 = std::max(x1, window[0]); y1 = std::max(y1, window[1]);
-      x2 = std::min(x2, window[2]); y2 = std::min(y2, window[3]);
-    }
-    AlJob j = {0, 0, 0, 0, a, (int)lo, (int)hi, 0};
-    if (x2 >= x1 && y2 >= y1) {
-      j.fx = x1; j.fy = y1; j.fw = x2 - x1 + 1; j.fh = y2 - y1 + 1;
-      const long long w = (long long)j.fh * mask_strips(j.fw);
-      pixels += (long long)j.fw * j.fh;
-      bound_words += w;
-      most_words = std::max(most_words, w);
-    }
-    jobs.push_back(j);
+    AlJob j;
+    j.a = a; j.lo = (int)lo; j.hi = (int)hi;
+    TightCall::add(x1, y1, x2, y2, j);
   }
-  void add_empty() { add(0, 0, -1, -1, -1, 0, 0); }
+  void take(WsLayout& l) {
+    A.take(l);
+    if (B) B->take(l);
+    d_idx = l.take<int>(idx.size());
+  }
+  hipError_t upload(const HostScope& hs) const {
+    hipError_t e = A.upload(hs);
+    if (e == hipSuccess && B) e = B->upload(hs);
+    return e != hipSuccess ? e : hs.up(d_idx, idx.data(), idx.size() * sizeof(int));
+  }
+  dim3 grid() const { return dim3((unsigned)((most_words + kAlThreads - 1) / kAlThreads), (unsigned)jobs.size()); }
+  void extent(hipStream_t s, const AlJob* d_jobs, TightBox* d_ext) const {
+    hipLaunchKernelGGL(al_extent_kernel, grid(), dim3(kAlThreads), 0, s, d_jobs, A.view(), (B ? B : &A)->view(), d_idx, op, all,
+                       d_ext);
+  }
+  void fill(hipStream_t s, const AlJob* d_jobs, const TightBox* d_box, Scanned first, u64* d_out, u64* d_area) const {
+    hipLaunchKernelGGL(al_fill_kernel, grid(), dim3(kAlThreads), 0, s, d_jobs, A.view(), (B ? B : &A)->view(), d_idx, op, all,
+                       d_box, first, d_out, d_area);
+  }
 };
 
 // What every entry refuses about a set, as mnc_mask_boundary does.
 int al_check_set(const char* who, const char* name, HostMaskSet* set, const int* bounds, const long long* offsets, const void* bits,
                  size_t bytes, int n, const float* scores) {
-  MNC_REQUIRE(n >= 0 && n <= kAlMaxN, "%s: %s has n=%d not in [0, %d]", who, name, n, kAlMaxN);
-  std::vector<long long> areas((size_t)n, 0);
-  return set->check(who, name, bounds, offsets, areas.data(), bits, bytes, n, nullptr, scores);
+  MNC_REQUIRE(n >= 0 && n <= kTightMaxN, "%s: %s has n=%d not in [0, %d]", who, name, n, kTightMaxN);
+  return set->check(who, name, bounds, offsets, bits, bytes, n, nullptr, scores);
 }
 
 CallTimer g_al_timer;
-
-// The rest of every entry once its jobs are made: the protocol of the sizes, the answers of the host, the launches, the copies.
-int al_run(const char* who, const AlCall& c, HostMaskSet& a, HostMaskSet* B, int* out_bounds, long long* out_offsets,
-           long long* out_areas, void* out_bits, size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id) {
-  const int n = (int)c.jobs.size();
-  MNC_REQUIRE(c.pixels <= kAlMaxPixels, "%s: %lld pixels of loose-frame rows in the call (limit %lld)", who, c.pixels, kAlMaxPixels);
-  MNC_REQUIRE(!out_bits || bits_bytes, "%s: null bits_bytes", who);
-  MNC_REQUIRE(!out_bits || n == 0 || (out_bounds && out_offsets && out_areas), "%s: null output pointer", who);
-  const size_t bound = (size_t)c.bound_words * 8;
-  *bits_bound = bound;
-  if (!out_bits) { clear_error(); return MNC_OK; }
-  MNC_REQUIRE(bits_cap >= bound, "%s: bits_cap %zu is below the %zu bytes of the loose frames", who, bits_cap, bound);
-  for (int o = 0; o < n; ++o) {
-    int* q = out_bounds + 4 * (size_t)o;
-    q[0] = 0; q[1] = 0; q[2] = -1; q[3] = -1;
-    out_offsets[o] = 0;
-    out_areas[o] = 0;
-  }
-  *bits_bytes = 0;
-  if (bound == 0) { clear_error(); return MNC_OK; }        // no frame has a row
-  const bool two = B != nullptr;
-  AlJob* d_jobs; int *d_idx, *d_words, *d_tile; AlBox* d_box; u64 *d_out, *d_area;
-  auto layout = [&](WsLayout l) {
-    a.take(l);
-    if (two) B->take(l);
-    d_jobs = l.take<AlJob>(n);
-    d_idx = l.take<int>(c.idx.size());
-    d_box = l.take<AlBox>(n);
-    d_words = l.take<int>(n);
-    d_tile = l.take<int>((size_t)scan_tiles(n) + 1);
-    d_out = l.take<u64>((size_t)c.bound_words);
-    d_area = l.take<u64>(n);
-    return l.bytes();
-  };
-  HostScope hs;
-  int rc = hs.open(device_id, layout(WsLayout()));
-  if (rc) return rc;
-  layout(WsLayout(hs.buf));
-  std::vector<AlBox> box((size_t)n, AlBox{INT_MAX, INT_MAX, -1, -1});
-  std::vector<u64> area((size_t)n, 0ull);
-  MNC_HIP_TRY(a.upload(hs));
-  if (two) MNC_HIP_TRY(B->upload(hs));
-  MNC_HIP_TRY(hs.up(d_jobs, c.jobs.data(), (size_t)n * sizeof(AlJob)));
-  MNC_HIP_TRY(hs.up(d_idx, c.idx.data(), c.idx.size() * sizeof(int)));
-  MNC_HIP_TRY(hs.up(d_box, box.data(), (size_t)n * sizeof(AlBox)));
-  MNC_HIP_TRY(hs.up(d_area, area.data(), (size_t)n * sizeof(u64)));
-  const MaskSet va = a.view(), vb = two ? B->view() : va;
-  const dim3 grid((unsigned)((c.most_words + kAlThreads - 1) / kAlThreads), (unsigned)n);
-  TimedSpan span(g_al_timer);
-  span.begin(hs.stream);
-  hipLaunchKernelGGL(al_extent_kernel, grid, dim3(kAlThreads), 0, hs.stream, d_jobs, va, vb, d_idx, c.op, c.all, d_box);
-  hipLaunchKernelGGL(al_size_kernel, dim3((unsigned)((n + kAlThreads - 1) / kAlThreads)), dim3(kAlThreads), 0, hs.stream, d_jobs, n,
-                     d_box, d_words);
-  const Scanned first = scan_launch(hs.stream, d_words, n, d_tile);
-  hipLaunchKernelGGL(al_fill_kernel, grid, dim3(kAlThreads), 0, hs.stream, d_jobs, va, vb, d_idx, c.op, c.all, d_box, first, d_out,
-                     d_area);
-  span.end(hs.stream);
-  MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hs.down(box.data(), d_box, (size_t)n * sizeof(AlBox)));
-  MNC_HIP_TRY(hs.down(area.data(), d_area, (size_t)n * sizeof(u64)));
-  MNC_HIP_TRY(hs.sync());
-  span.keep();
-  long long at = 0;                                        // the offsets as the scan placed them: the bytes of the tight rows
-  for (int o = 0; o < n; ++o) at += mask_bytes(box[o].x2 - box[o].x1 + 1, box[o].y2 - box[o].y1 + 1);
-  if (at < 0 || (size_t)at > bound) {                      // (cannot be: a tight frame lies inside its loose one)
-    set_error("%s: the result's %lld bytes exceed the bound %zu", who, at, bound);
-    return MNC_ERR_HIP;
-  }
-  MNC_HIP_TRY(hs.down(out_bits, d_out, (size_t)at));
-  MNC_HIP_TRY(hs.sync());
-  at = 0;
-  for (int o = 0; o < n; ++o) {
-    int* q = out_bounds + 4 * (size_t)o;
-    q[0] = box[o].x1; q[1] = box[o].y1; q[2] = box[o].x2; q[3] = box[o].y2;
-    out_offsets[o] = at;
-    out_areas[o] = (long long)area[o];
-    at += mask_bytes(box[o].x2 - box[o].x1 + 1, box[o].y2 - box[o].y1 + 1);
-  }
-  *bits_bytes = (size_t)at;
-  clear_error();
-  return MNC_OK;
-}
 
 }  // namespace
 
@@ -298,10 +163,8 @@ int mnc_mask_combine(const int* a_bounds, const long long* a_offsets, const void
   MNC_REQUIRE(op >= kAlCopy || n_b > 0 || n_a <= 0, "%s: op=%d needs a set b", who, op);
   MNC_REQUIRE(op != kAlNot || window, "%s: op 5 (not) needs a window", who);
   if (window) {
-    for (int k = 0; k < 4; ++k)
-      MNC_REQUIRE(window[k] > -kAlMaxCoord && window[k] < kAlMaxCoord, "%s: window coordinate %d out of range", who, window[k]);
-    MNC_REQUIRE(window[2] >= window[0] && window[3] >= window[1], "%s: the window (%d, %d, %d, %d) is empty", who, window[0],
-                window[1], window[2], window[3]);
+    const int rc = tight_check_window(who, window);
+    if (rc) return rc;
   }
   HostMaskSet A, B;
   int rc = al_check_set(who, "a", &A, a_bounds, a_offsets, a_bits, a_bytes, n_a, nullptr);
@@ -311,21 +174,21 @@ int mnc_mask_combine(const int* a_bounds, const long long* a_offsets, const void
     rc = al_check_set(who, "b", &B, b_bounds, b_offsets, b_bits, b_bytes, n_b, nullptr);
     if (rc) return rc;
   }
-  AlCall c;
+  AlCall c(A, two ? &B : nullptr);
   c.op = op;
   c.window = window;
   for (int i = 0; i < n_a; ++i) {
     const mnc_mask_info& a = A.info[i];
     if (!two) {
       if (op == kAlNot) c.add(window[0], window[1], window[2], window[3], i, 0, 0);
-      else if (al_rows(a)) c.add(a.x1, a.y1, a.x2, a.y2, i, 0, 0);
+      else if (mask_has_rows(a)) c.add(a.x1, a.y1, a.x2, a.y2, i, 0, 0);
       else c.add_empty();
       continue;
     }
     const int k = n_b == 1 ? 0 : i;
     const mnc_mask_info& b = B.info[k];
     c.idx.push_back(k);
-    const bool ra = al_rows(a), rb = al_rows(b);
+    const bool ra = mask_has_rows(a), rb = mask_has_rows(b);
     if (op == kAlAnd) {
       if (ra && rb) c.add(std::max(a.x1, b.x1), std::max(a.y1, b.y1), std::min(a.x2, b.x2), std::min(a.y2, b.y2), i, i, i + 1);
       else c.add_empty();
@@ -341,8 +204,7 @@ int mnc_mask_combine(const int* a_bounds, const long long* a_offsets, const void
       c.add_empty();
     }
   }
-  return al_run(who, c, A, two ? &B : nullptr, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes,
-                device_id);
+  return tight_run(who, c, g_al_timer, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
 }
 
 // see include/mnc_hip.h
@@ -351,7 +213,7 @@ int mnc_mask_merge(const int* bounds, const long long* offsets, const void* bits
                    void* out_bits, size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id) {
   const char* who = "mnc_mask_merge";
   MNC_REQUIRE(bits_bound, "%s: null bits_bound", who);
-  MNC_REQUIRE(G >= 0 && G <= kAlMaxN, "%s: G=%d not in [0, %d]", who, G, kAlMaxN);
+  MNC_REQUIRE(G >= 0 && G <= kTightMaxN, "%s: G=%d not in [0, %d]", who, G, kTightMaxN);
   MNC_REQUIRE(G == 0 || group_ptr, "%s: null group_ptr", who);
   HostMaskSet A;
   int rc = al_check_set(who, "masks", &A, bounds, offsets, bits, bytes, n, nullptr);
@@ -366,7 +228,7 @@ int mnc_mask_merge(const int* bounds, const long long* offsets, const void* bits
     for (long long k = 0; k < group_ptr[G]; ++k)
       MNC_REQUIRE(members[k] >= 0 && members[k] < n, "%s: members[%lld]=%d not in [0, %d)", who, k, members[k], n);
   }
-  AlCall c;
+  AlCall c(A, nullptr);
   c.op = kAlOr;
   c.all = intersect ? 1 : 0;
   if (G > 0) c.idx.assign(members, members + group_ptr[G]);
@@ -375,7 +237,7 @@ int mnc_mask_merge(const int* bounds, const long long* offsets, const void* bits
     bool any = false, every = true;
     for (long long k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
       const mnc_mask_info& m = A.info[members[k]];
-      if (!al_rows(m)) { every = false; continue; }
+      if (!mask_has_rows(m)) { every = false; continue; }
       if (!any || !intersect) {
         x1 = any ? std::min(x1, m.x1) : m.x1; y1 = any ? std::min(y1, m.y1) : m.y1;
         x2 = any ? std::max(x2, m.x2) : m.x2; y2 = any ? std::max(y2, m.y2) : m.y2;
@@ -387,7 +249,7 @@ int mnc_mask_merge(const int* bounds, const long long* offsets, const void* bits
     if (any && (every || !intersect)) c.add(x1, y1, x2, y2, -1, group_ptr[g], group_ptr[g + 1]);
     else c.add_empty();
   }
-  return al_run(who, c, A, nullptr, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
+  return tight_run(who, c, g_al_timer, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
 }
 
 // see include/mnc_hip.h
@@ -415,19 +277,19 @@ int mnc_mask_layer(const int* bounds, const long long* offsets, const void* bits
     std::stable_sort(seq.begin(), seq.end(), [&](int p, int q) { return scores[p] > scores[q]; });
     for (int k = 0; k < n; ++k) rank[seq[k]] = k;
   }
-  AlCall c;
+  AlCall c(A, nullptr);
   c.op = kAlMinus;
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = A.info[i];
-    if (!al_rows(a)) { c.add_empty(); continue; }
+    if (!mask_has_rows(a)) { c.add_empty(); continue; }
     const long long lo = (long long)c.idx.size();
     for (int k = 0; k < rank[i]; ++k) {                    // the instances before i whose bounds meet i's
       const mnc_mask_info& m = A.info[seq[k]];
-      if (al_rows(m) && m.x1 <= a.x2 && m.x2 >= a.x1 && m.y1 <= a.y2 && m.y2 >= a.y1) c.idx.push_back(seq[k]);
+      if (mask_has_rows(m) && m.x1 <= a.x2 && m.x2 >= a.x1 && m.y1 <= a.y2 && m.y2 >= a.y1) c.idx.push_back(seq[k]);
     }
     c.add(a.x1, a.y1, a.x2, a.y2, i, lo, (long long)c.idx.size());
   }
-  return al_run(who, c, A, nullptr, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
+  return tight_run(who, c, g_al_timer, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
 }
 
 // see include/mnc_hip.h

@@ -242,8 +242,7 @@ int mnc_mask_boundary(const int* bounds, const long long* offsets, const void* b
   MNC_REQUIRE(n == 0 || !out_bits || out_areas, "%s: null out_areas", who);
   HostMaskSet set;
   std::vector<mnc_mask_info> out;
-  std::vector<long long> areas((size_t)n, 0);
-  rc = set.check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+  rc = set.check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   *bits_bytes = 0;
   if (n == 0) { clear_error(); return MNC_OK; }

@@ -395,8 +395,7 @@ struct CcJob {
     MNC_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity=%d is not 4 or 8", who, connectivity);
     MNC_REQUIRE(n_in >= 0 && n_in <= kCcMaxN, "%s: n=%d not in [0, %d]", who, n_in, kCcMaxN);
     n = n_in; frame = frame_in; e = connectivity == 8; device = device_id;
-    std::vector<long long> areas((size_t)n, 0);
-    const int rc = set.check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+    const int rc = set.check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
     if (rc) return rc;
     insts.assign((size_t)n + 1, CcInst());
     long long at = 0, real = 0, end = 0;

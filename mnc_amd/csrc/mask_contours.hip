@@ -242,8 +242,7 @@ int mnc_mask_contours(const int* bounds, const long long* offsets, const void* b
   MNC_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity=%d is not 4 or 8", who, connectivity);
   MNC_REQUIRE(n >= 0 && n <= kCtMaxN, "%s: n=%d not in [0, %d]", who, n, kCtMaxN);
   HostMaskSet set;
-  std::vector<long long> no_areas((size_t)n, 0);
-  int rc = set.check(who, "masks", bounds, offsets, no_areas.data(), bits, bytes, n, nullptr, nullptr);
+  int rc = set.check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   std::vector<CtInst> insts((size_t)n + 1);
   long long at = 0;

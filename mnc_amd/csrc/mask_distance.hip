@@ -216,12 +216,11 @@ int md_isqrt(int v) {
   return r;
 }
 
-inline bool md_rows(const mnc_mask_info& a) { return a.x2 >= a.x1 && a.y2 >= a.y1; }
 
 // A whole frame as window: the erode stage of a mask on its bounds, for the maps (cap as the head says) or at a disc.
 MdInst md_on_bounds(const mnc_mask_info& a, long long src_words, int cap, long long out_off) {
   MdInst m = MdInst();
-  if (!md_rows(a)) return m;
+  if (!mask_has_rows(a)) return m;
   m.src_words = src_words;
   m.sw = m.fw = m.ow = a.x2 - a.x1 + 1;
   m.sh = m.fh = m.oh = a.y2 - a.y1 + 1;
@@ -254,12 +253,11 @@ void md_launch_final(hipStream_t s, const MdStage& st, const MdInst* d_inst, con
 int md_check_set(const char* who, HostMaskSet* set, const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
                  long long* pixels) {
   MNC_REQUIRE(n >= 0 && n <= kMdMaxN, "%s: n=%d not in [0, %d]", who, n, kMdMaxN);
-  std::vector<long long> areas((size_t)n, 0);
-  const int rc = set->check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+  const int rc = set->check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   *pixels = 0;
   for (const mnc_mask_info& a : set->info)
-    if (md_rows(a)) *pixels += (long long)(a.x2 - a.x1 + 1) * (a.y2 - a.y1 + 1);
+    if (mask_has_rows(a)) *pixels += (long long)(a.x2 - a.x1 + 1) * (a.y2 - a.y1 + 1);
   MNC_REQUIRE(*pixels <= kMdMaxPixels, "%s: %lld pixels of rows in the call (limit %lld)", who, *pixels, kMdMaxPixels);
   return MNC_OK;
 }
@@ -285,7 +283,7 @@ int mnc_mask_distance(const int* bounds, const long long* offsets, const void* b
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = set.info[i];
     dist_ptr[i] = st.g_entries;                            // (a frame is the bounds: the maps are numbered as the g plane is)
-    st.add(md_on_bounds(a, a.offset / 8, md_rows(a) ? md_map_cap(a) : 0, st.g_entries));
+    st.add(md_on_bounds(a, a.offset / 8, mask_has_rows(a) ? md_map_cap(a) : 0, st.g_entries));
   }
   dist_ptr[n] = st.g_entries;
   *dist_total = (size_t)pixels;
@@ -332,7 +330,7 @@ int mnc_mask_inscribed(const int* bounds, const long long* offsets, const void* 
   MdStage st;
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = set.info[i];
-    st.add(md_on_bounds(a, a.offset / 8, md_rows(a) ? md_map_cap(a) : 0, 0));
+    st.add(md_on_bounds(a, a.offset / 8, mask_has_rows(a) ? md_map_cap(a) : 0, 0));
   }
   MdInst* d_inst; unsigned short* d_g; u64* d_key;
   auto layout = [&](WsLayout l) {
@@ -394,7 +392,7 @@ int mnc_mask_morph(const int* bounds, const long long* offsets, const void* bits
     pixels = 0;
     for (int i = 0; i < n; ++i) {
       const mnc_mask_info& a = set.info[i];
-      if (!md_rows(a)) continue;
+      if (!mask_has_rows(a)) continue;
       MNC_REQUIRE(a.x1 - rho > -kMdMaxCoord && a.y1 - rho > -kMdMaxCoord && a.x2 + rho < kMdMaxCoord && a.y2 + rho < kMdMaxCoord,
                   "%s: masks[%d] grown by %d leaves the coordinate range", who, i, rho);
       const long long p = (long long)(a.x2 - a.x1 + 1 + 2 * rho) * (a.y2 - a.y1 + 1 + 2 * rho);
@@ -415,7 +413,7 @@ int mnc_mask_morph(const int* bounds, const long long* offsets, const void* bits
     int* q = &ob[4 * (size_t)i];
     q[0] = a.x1; q[1] = a.y1; q[2] = a.x2; q[3] = a.y2;
     oo[i] = out_words * 8;
-    if (!md_rows(a)) {
+    if (!mask_has_rows(a)) {
       if (clip) { q[0] = 0; q[1] = 0; q[2] = -1; q[3] = -1; }
       first.add(MdInst());
       if (op >= 2) second.add(MdInst());

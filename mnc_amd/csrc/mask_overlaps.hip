@@ -131,9 +131,9 @@ __global__ __launch_bounds__(kOvThreads) void mask_keep_kernel(const int* __rest
 
 // The instance table of a host set, checked: MNC_ERR_INVALID before anything is launched.  (Declared in mask_set.h: every host
 // entry of the mask files checks its sets here.)
-int HostMaskSet::check(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas,
-                       const void* bits_in, size_t bytes, int n, const int* classes, const float* scores) {
-  MNC_REQUIRE(n == 0 || (bounds && offsets && areas), "%s: null pointer in set %s", who, set);
+int HostMaskSet::check(const char* who, const char* set, const int* bounds, const long long* offsets, const void* bits_in,
+                       size_t bytes, int n, const int* classes, const float* scores) {
+  MNC_REQUIRE(n == 0 || (bounds && offsets), "%s: null pointer in set %s", who, set);
   info.assign((size_t)n, mnc_mask_info());
   bits = bits_in;
   used = 0;
@@ -156,10 +156,19 @@ int HostMaskSet::check(const char* who, const char* set, const int* bounds, cons
     d.score = scores ? scores[i] : 0.f;
     d.row = i;
     d.offset = offsets[i];
-    d.area = areas[i];
+    d.area = 0;
   }
   MNC_REQUIRE(used == 0 || bits, "%s: null bits in set %s", who, set);
   return MNC_OK;
+}
+
+// The same of a set whose areas are given: a null `areas` is refused with the other null pointers.
+int HostMaskSet::check(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas,
+                       const void* bits_in, size_t bytes, int n, const int* classes, const float* scores) {
+  MNC_REQUIRE(n == 0 || areas, "%s: null pointer in set %s", who, set);
+  const int rc = check(who, set, bounds, offsets, bits_in, bytes, n, classes, scores);
+  for (int i = 0; rc == MNC_OK && i < n; ++i) info[i].area = areas[i];
+  return rc;
 }
 
 // (Declared in mask_set.h: mask_match.hip launches the overlap kernel too.)

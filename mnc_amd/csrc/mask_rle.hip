@@ -333,8 +333,7 @@ int mnc_mask_rle(const int* bounds, const long long* offsets, const void* bits, 
   MNC_REQUIRE(H >= 1 && W >= 1 && H <= kRleMaxSide && W <= kRleMaxSide, "mnc_mask_rle: image %d x %d not in [1, %d]", H, W, kRleMaxSide);
   MNC_REQUIRE(run_ptr && runs_total, "mnc_mask_rle: null output pointer");
   HostMaskSet set;
-  std::vector<long long> areas((size_t)n, 0);
-  int rc = set.check("mnc_mask_rle", "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+  int rc = set.check("mnc_mask_rle", "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   *runs_total = 0;
   run_ptr[0] = 0;

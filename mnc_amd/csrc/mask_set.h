@@ -1,5 +1,5 @@
 // One set of packed instance masks (include/mnc_hip.h n5), as the mask files share it: inst_masks.hip, mask_overlaps.hip, mask_rle.hip,
-// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip.  Internal to libmnc_hip.so; nothing else includes it.
+// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip and, through mask_tight.h, mask_tight.hip.  Internal to libmnc_hip.so; nothing else includes it.
 #pragma once
 #include <vector>
 
@@ -12,6 +12,9 @@ typedef unsigned long long u64;
 // Words of one row of w columns, and the bytes of a w x h mask: rows of whole 64-bit words, no bytes without rows.
 __host__ __device__ inline int mask_strips(int w) { return (w + 63) >> 6; }
 __host__ __device__ inline long long mask_bytes(int w, int h) { return w < 1 || h < 1 ? 0 : (long long)h * mask_strips(w) * 8; }
+
+// An instance has rows: its bounds hold a pixel position.
+__host__ __device__ inline bool mask_has_rows(const mnc_mask_info& m) { return m.x2 >= m.x1 && m.y2 >= m.y1; }
 
 // A set on the device -- the instance table, the words, and the count (read from *n_ptr when that is set).
 struct MaskSet {
@@ -49,6 +52,14 @@ __device__ __forceinline__ u64 mask_word_at(const u64* __restrict__ row, int bit
   return v;
 }
 
+// The 64 bits of instance m from image column x on, in image row y: 0 outside its bounds.
+__device__ __forceinline__ u64 mask_read(const mnc_mask_info& m, const u64* __restrict__ bits, int x, int y) {
+  const int x1 = m.x1, y1 = m.y1, w = m.x2 - x1 + 1;
+  if (w < 1 || y < y1 || y > m.y2) return 0ull;
+  const int strips = mask_strips(w);
+  return mask_word_at(bits + m.offset / 8 + (long long)(y - y1) * strips, x - x1, strips, w);
+}
+
 // Where the words of a set are numbered in raster order, instance after instance, and insts[i].*kFirst is the first word of
 // instance i: the last of the n instances whose first word is at or before g -- the one that holds word g (an instance without
 // words begins where the next does).  At most 11 turns: the entries that number words this way take n <= 2048.
@@ -80,9 +91,11 @@ struct HostMaskSet {
   mnc_mask_info* d_info = nullptr;
   u64* d_bits = nullptr;
   // mask_overlaps.hip: the table, checked against the coordinate, pixel and offset limits of mnc_mask_overlaps -- MNC_ERR_INVALID
-  // before anything is launched
+  // before anything is launched.  Without `areas`, for a set whose areas are not given, every area is stored as 0.
   int check(const char* who, const char* set, const int* bounds, const long long* offsets, const long long* areas, const void* bits,
             size_t bytes, int n, const int* classes, const float* scores);
+  int check(const char* who, const char* set, const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
+            const int* classes, const float* scores);
   void take(WsLayout& l) {
     d_info = l.take<mnc_mask_info>(info.size());
     d_bits = l.take<u64>(used / 8);

@@ -332,14 +332,13 @@ struct MsPlan {
 int ms_check_set(const char* who, HostMaskSet* set, const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
                  MsPlan* plan) {
   MNC_REQUIRE(n >= 0 && n <= kMsMaxN, "%s: n=%d not in [0, %d]", who, n, kMsMaxN);
-  std::vector<long long> areas((size_t)n, 0);
-  const int rc = set->check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+  const int rc = set->check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
   if (rc) return rc;
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = set->info[i];
     MsInst m = MsInst();
     m.cand0 = (int)plan->cands;
-    if (a.x2 >= a.x1 && a.y2 >= a.y1) {
+    if (mask_has_rows(a)) {
       m.w = a.x2 - a.x1 + 1;
       m.h = a.y2 - a.y1 + 1;
       MNC_REQUIRE(m.w <= kMsMaxExtent && m.h <= kMsMaxExtent, "%s: masks[%d] is %d x %d (limit %d a side)", who, i, m.w, m.h,

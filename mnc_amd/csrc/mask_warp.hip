@@ -19,53 +19,33 @@
 //               formed once per lane and, for the rows, handed round by a shuffle: two divisions per lane and block, not 128.
 // The frame -- which already is intersected with the window -- is applied as a word and row mask.
 //
-//   wp_extent_kernel   a wave per block of the loose frame: wp_block, then each lane's row and its lowest and highest set column
-//                      (ctz / clz), reduced over the wave by shuffles and joined by integer atomicMin / atomicMax into four
-//                      extents per instance, relative to the frame.
-//   wp_size_kernel     one lane per instance: the tight bounds from the extents ((0, 0, -1, -1) when no word was non-zero) and
-//                      the words of its rows; scan_launch (scan.h) turns the counts into the offsets.
-//   wp_fill_kernel     a wave per block of the TIGHT frame (the grid is sized for the loose one; waves past the tight blocks
-//                      leave): wp_block again at the tight position, every word stored once; the popcounts are summed over the
-//                      wave and added to the instance's area by one integer atomic.
-// Five launches whatever the data, nothing read back in between; the tight bounds and the areas come back first, the host derives
-// the offsets from the bounds exactly as the scan did, and copies exactly the bytes of the result.  The only atomics are integer
-// min, max and add: the same input gives the same bytes on every run.
+// The result is tight and its size depends on the data: the protocol, its five launches and its driver are mask_tight.h's.  Here
+// the unit of work is a wave per block -- the algebra's passes with a wave, not a lane, as the unit:
+//   wp_extent_kernel   a wave per block of the loose frame: wp_block, then tight_join with each lane's row.
+//   wp_fill_kernel     a wave per block of the TIGHT frame: wp_block again at the tight position, every word stored once, then
+//                      tight_count.
 //
 // Bound: latency.  100 instances of an image are a few hundred KB of words that sit in L2; an isometry reads at most two words per
 // result word; the gather reads one word per pixel and pass, a wave walking the 64 rows of its block eight at a time with their
 // loads in flight together (one at a time the chain of L2 latencies was the kernels' time).  Measured at 100 instances of a
-// 600 x 1000 image, call with its copies / kernels alone: fliplr 0.15 ms / 18 us, rot90 0.15 ms / 20 us, resize to half 0.17 ms /
-// 34 us, to 1.5 times 0.21 ms / 43 us, warp_affine by 30 degrees 0.20 ms / 42 us (profiles/mask_warp_bench.txt).  62 and 63 VGPRs in
+// 600 x 1000 image, call with its copies / kernels alone: fliplr 0.16 ms / 18 us, rot90 0.16 ms / 20 us, resize to half 0.17 ms /
+// 35 us, to 1.5 times 0.21 ms / 43 us, warp_affine by 30 degrees 0.21 ms / 43 us (profiles/mask_warp_bench.txt).  62 and 63 VGPRs in
 // the two block kernels, no LDS and no scratch in any kernel.
 #include <algorithm>
 #include <climits>
 #include <vector>
 
-#include "mask_set.h"
-#include "scan.h"
+#include "mask_tight.h"
 
 namespace mnc {
 
 constexpr int kWpThreads = 256;
 constexpr int kWpWaves = kWpThreads / 64;
-constexpr int kWpMaxN = 2048;                  // instances of a set (mnc_mask_combine's limit)
-constexpr int kWpMaxCoord = 1 << 24;
-constexpr long long kWpMaxPixels = 1ll << 27;  // pixels of the loose frames of one call
 constexpr long long kWpMaxDen = 1ll << 32;
 constexpr long long kWpMaxLinear = 1ll << 32;  // |c0|, |c1|, |c3|, |c4|
 constexpr long long kWpMaxOffset = 1ll << 60;  // |c2|, |c5|: with the other limits every numerator stays below 2^62
 
 enum WpForm { kWpRows = 0, kWpTranspose = 1, kWpGather = 2 };
-
-// One output instance: the loose frame (fw or fh 0: no pixel, skipped by every kernel).
-struct WpJob {
-  int fx, fy, fw, fh;
-};
-
-// Extents relative to the frame (wp_extent_kernel; x2 < 0: no pixel), then the tight bounds in image coordinates (wp_size_kernel).
-struct WpBox {
-  int x1, y1, x2, y2;
-};
 
 // The map of one call.  Isometries: negx / negy say whether the source x / y falls as the result coordinate it depends on rises,
 // tx, ty the translation.  Gather: sx = floor((c[0] x + c[1] y + c[2]) / den), sy alike with c[3 .. 5]; shift >= 0: den == 1 << shift.
@@ -73,14 +53,6 @@ struct WpMap {
   int form, negx, negy, tx, ty, shift;
   long long c[6], den;
 };
-
-// The 64 bits of instance m from image column x on, in image row y: 0 outside its bounds.
-__device__ __forceinline__ u64 wp_read(const mnc_mask_info& m, const u64* __restrict__ bits, int x, int y) {
-  const int x1 = m.x1, y1 = m.y1, w = m.x2 - x1 + 1;
-  if (w < 1 || y < y1 || y > m.y2) return 0ull;
-  const int strips = mask_strips(w);
-  return mask_word_at(bits + m.offset / 8 + (long long)(y - y1) * strips, x - x1, strips, w);
-}
 
 // floor(a / d) for d > 0: C++'s quotient rounds towards zero, one too high for a negative a that d does not divide.
 __device__ __forceinline__ long long wp_floor_div(long long a, long long d, int shift) {
@@ -100,16 +72,16 @@ __device__ __forceinline__ bool wp_pixel(const mnc_mask_info& m, const u64* __re
 
 // The 64 result bits of job j from image column x0 >= j.fx on, in image row y0 + lane; `rows` <= 64 rows of the block are wanted
 // (the other lanes' words are not used by the caller).  Every lane of the wave comes here.  Both passes call it.
-__device__ __forceinline__ u64 wp_block(const WpJob& j, const mnc_mask_info& m, const u64* __restrict__ bits, const WpMap& p, int x0,
-                                        int y0, int rows, int lane) {
+__device__ __forceinline__ u64 wp_block(const TightFrame& j, const mnc_mask_info& m, const u64* __restrict__ bits, const WpMap& p,
+                                        int x0, int y0, int rows, int lane) {
   u64 v = 0ull;
   if (p.form == kWpRows) {
     const int y = y0 + lane - p.ty, sy = p.negy ? -y : y;
-    v = p.negx ? __brevll(wp_read(m, bits, p.tx - x0 - 63, sy)) : wp_read(m, bits, x0 - p.tx, sy);
+    v = p.negx ? __brevll(mask_read(m, bits, p.tx - x0 - 63, sy)) : mask_read(m, bits, x0 - p.tx, sy);
   } else if (p.form == kWpTranspose) {
     // result column x0 + lane is source row sy; its bit k is the result pixel of row y0 + k
     const int x = x0 + lane - p.tx, sy = p.negy ? -x : x;
-    const u64 col = p.negx ? __brevll(wp_read(m, bits, p.ty - y0 - 63, sy)) : wp_read(m, bits, y0 - p.ty, sy);
+    const u64 col = p.negx ? __brevll(mask_read(m, bits, p.ty - y0 - 63, sy)) : mask_read(m, bits, y0 - p.ty, sy);
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
       const u64 b = __ballot((col >> k) & 1ull);
@@ -150,192 +122,69 @@ __device__ __forceinline__ u64 wp_block(const WpJob& j, const mnc_mask_info& m, 
 }
 
 // grid (ceil(most loose-frame blocks / 4), jobs), block 256: a wave per 64 x 64 block of the loose frame.
-__global__ __launch_bounds__(kWpThreads) void wp_extent_kernel(const WpJob* __restrict__ jobs, MaskSet A, WpMap p,
-                                                               WpBox* __restrict__ ext) {
+__global__ __launch_bounds__(kWpThreads) void wp_extent_kernel(const TightFrame* __restrict__ jobs, MaskSet A, WpMap p,
+                                                               TightBox* __restrict__ ext) {
   const int o = blockIdx.y;
-  const WpJob j = jobs[o];
+  const TightFrame j = jobs[o];
   if (j.fw < 1 || j.fh < 1) return;
   const int strips = mask_strips(j.fw), lane = threadIdx.x & 63;
   const long long w = (long long)blockIdx.x * kWpWaves + (threadIdx.x >> 6);
   if (w >= (long long)((j.fh + 63) >> 6) * strips) return;  // (the whole wave)
   const int g = (int)(w / strips), c = (int)(w - (long long)g * strips);
   const u64 v = wp_block(j, A.info[o], A.bits, p, j.fx + c * 64, j.fy + g * 64, min(64, j.fh - g * 64), lane);
-  int minx = INT_MAX, miny = INT_MAX, maxx = -1, maxy = -1;
-  if (v) {
-    minx = c * 64 + (__ffsll((long long)v) - 1);
-    maxx = c * 64 + 63 - __clzll((long long)v);
-    miny = maxy = g * 64 + lane;
-  }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    minx = min(minx, __shfl_xor(minx, s));
-    miny = min(miny, __shfl_xor(miny, s));
-    maxx = max(maxx, __shfl_xor(maxx, s));
-    maxy = max(maxy, __shfl_xor(maxy, s));
-  }
-  if (lane == 0 && maxx >= 0) {
-    atomicMin(&ext[o].x1, minx);
-    atomicMin(&ext[o].y1, miny);
-    atomicMax(&ext[o].x2, maxx);
-    atomicMax(&ext[o].y2, maxy);
-  }
-}
-
-// grid ceil(jobs / 256), block 256: the extents in place into the tight bounds, and the words of their rows.
-__global__ __launch_bounds__(kWpThreads) void wp_size_kernel(const WpJob* __restrict__ jobs, int n, WpBox* __restrict__ box,
-                                                             int* __restrict__ words) {
-  const int o = blockIdx.x * kWpThreads + threadIdx.x;
-  if (o >= n) return;
-  const WpJob j = jobs[o];
-  const WpBox e = box[o];
-  WpBox b = {0, 0, -1, -1};
-  int count = 0;
-  if (j.fw >= 1 && j.fh >= 1 && e.x2 >= 0) {
-    b.x1 = j.fx + e.x1; b.y1 = j.fy + e.y1; b.x2 = j.fx + e.x2; b.y2 = j.fy + e.y2;
-    count = (e.y2 - e.y1 + 1) * mask_strips(e.x2 - e.x1 + 1);      // (at most the 2^27 words of the call's loose frames)
-  }
-  box[o] = b;
-  words[o] = count;
+  tight_join(ext + o, v, c * 64, g * 64 + lane);
 }
 
 // grid (ceil(most loose-frame blocks / 4), jobs), block 256: a wave per 64 x 64 block of the tight frame.
-__global__ __launch_bounds__(kWpThreads) void wp_fill_kernel(const WpJob* __restrict__ jobs, MaskSet A, WpMap p,
-                                                             const WpBox* __restrict__ box, Scanned first, u64* __restrict__ out,
+__global__ __launch_bounds__(kWpThreads) void wp_fill_kernel(const TightFrame* __restrict__ jobs, MaskSet A, WpMap p,
+                                                             const TightBox* __restrict__ box, Scanned first, u64* __restrict__ out,
                                                              u64* __restrict__ area) {
   const int o = blockIdx.y;
-  const WpBox b = box[o];
+  const TightBox b = box[o];
   if (b.x2 < b.x1) return;
-  const WpJob j = jobs[o];
+  const TightFrame j = jobs[o];
   const int th = b.y2 - b.y1 + 1, strips = mask_strips(b.x2 - b.x1 + 1), lane = threadIdx.x & 63;
   const long long w = (long long)blockIdx.x * kWpWaves + (threadIdx.x >> 6);
   if (w >= (long long)((th + 63) >> 6) * strips) return;   // (the whole wave)
   const int g = (int)(w / strips), c = (int)(w - (long long)g * strips), rows = min(64, th - g * 64);
   const u64 v = wp_block(j, A.info[o], A.bits, p, b.x1 + c * 64, b.y1 + g * 64, rows, lane);
-  int set = 0;
-  if (lane < rows) {
-    out[(long long)first.at(o) + (long long)(g * 64 + lane) * strips + c] = v;
-    set = __popcll(v);
-  }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) set += __shfl_xor(set, s);
-  if (lane == 0 && set) atomicAdd(&area[o], (u64)set);
+  if (lane < rows) out[(long long)first.at(o) + (long long)(g * 64 + lane) * strips + c] = v;
+  tight_count(area + o, lane < rows ? v : 0ull);
 }
 
 namespace {
 
 typedef __int128 i128;
 
-inline bool wp_rows(const mnc_mask_info& a) { return a.x2 >= a.x1 && a.y2 >= a.y1; }
-
 inline i128 wp_floor(i128 a, i128 d) {                      // d > 0
   const i128 q = a / d;
   return a - q * d < 0 ? q - 1 : q;
 }
 
-// The jobs of one call and what its launches need.
-struct WpCall {
-  std::vector<WpJob> jobs;
+// One call (mask_tight.h): the jobs are the frames themselves; beside them the set and the map.
+struct WpCall : TightCall<TightFrame> {
+  HostMaskSet& A;
   WpMap map;
-  long long most_blocks = 0, bound_words = 0, pixels = 0;
-  // The job of the next output instance: the frame (x1, y1, x2, y2), inclusive; x2 < x1 or y2 < y1: none.
-  void add(int x1, int y1, int x2, int y2) {
-    WpJob j = {0, 0, 0, 0};
-    if (x2 >= x1 && y2 >= y1) {
-      j.fx = x1; j.fy = y1; j.fw = x2 - x1 + 1; j.fh = y2 - y1 + 1;
-      pixels += (long long)j.fw * j.fh;
-      bound_words += (long long)j.fh * mask_strips(j.fw);
-      most_blocks = std::max(most_blocks, (long long)((j.fh + 63) >> 6) * mask_strips(j.fw));
-    }
-    jobs.push_back(j);
+  explicit WpCall(HostMaskSet& a) : A(a) {}
+  void take(WsLayout& l) { A.take(l); }
+  hipError_t upload(const HostScope& hs) const { return A.upload(hs); }
+  dim3 grid() const { return dim3((unsigned)((most_blocks + kWpWaves - 1) / kWpWaves), (unsigned)jobs.size()); }
+  void extent(hipStream_t s, const TightFrame* d_jobs, TightBox* d_ext) const {
+    hipLaunchKernelGGL(wp_extent_kernel, grid(), dim3(kWpThreads), 0, s, d_jobs, A.view(), map, d_ext);
   }
-  void add_empty() { add(0, 0, -1, -1); }
+  void fill(hipStream_t s, const TightFrame* d_jobs, const TightBox* d_box, Scanned first, u64* d_out, u64* d_area) const {
+    hipLaunchKernelGGL(wp_fill_kernel, grid(), dim3(kWpThreads), 0, s, d_jobs, A.view(), map, d_box, first, d_out, d_area);
+  }
 };
 
 // What both entries refuse about a set, as mnc_mask_combine does.
 int wp_check_set(const char* who, HostMaskSet* set, const int* bounds, const long long* offsets, const void* bits, size_t bytes,
                  int n) {
-  MNC_REQUIRE(n >= 0 && n <= kWpMaxN, "%s: n=%d not in [0, %d]", who, n, kWpMaxN);
-  std::vector<long long> areas((size_t)n, 0);
-  return set->check(who, "masks", bounds, offsets, areas.data(), bits, bytes, n, nullptr, nullptr);
+  MNC_REQUIRE(n >= 0 && n <= kTightMaxN, "%s: n=%d not in [0, %d]", who, n, kTightMaxN);
+  return set->check(who, "masks", bounds, offsets, bits, bytes, n, nullptr, nullptr);
 }
 
 CallTimer g_wp_timer;
-
-// The rest of both entries once the jobs are made: the protocol of the sizes, the answers of the host, the launches, the copies.
-int wp_run(const char* who, const WpCall& c, HostMaskSet& a, int* out_bounds, long long* out_offsets, long long* out_areas,
-           void* out_bits, size_t bits_cap, size_t* bits_bound, size_t* bits_bytes, int device_id) {
-  const int n = (int)c.jobs.size();
-  MNC_REQUIRE(c.pixels <= kWpMaxPixels, "%s: %lld pixels of loose-frame rows in the call (limit %lld)", who, c.pixels, kWpMaxPixels);
-  MNC_REQUIRE(!out_bits || bits_bytes, "%s: null bits_bytes", who);
-  MNC_REQUIRE(!out_bits || n == 0 || (out_bounds && out_offsets && out_areas), "%s: null output pointer", who);
-  const size_t bound = (size_t)c.bound_words * 8;
-  *bits_bound = bound;
-  if (!out_bits) { clear_error(); return MNC_OK; }
-  MNC_REQUIRE(bits_cap >= bound, "%s: bits_cap %zu is below the %zu bytes of the loose frames", who, bits_cap, bound);
-  for (int o = 0; o < n; ++o) {
-    int* q = out_bounds + 4 * (size_t)o;
-    q[0] = 0; q[1] = 0; q[2] = -1; q[3] = -1;
-    out_offsets[o] = 0;
-    out_areas[o] = 0;
-  }
-  *bits_bytes = 0;
-  if (bound == 0) { clear_error(); return MNC_OK; }        // no frame has a row
-  WpJob* d_jobs; int *d_words, *d_tile; WpBox* d_box; u64 *d_out, *d_area;
-  auto layout = [&](WsLayout l) {
-    a.take(l);
-    d_jobs = l.take<WpJob>(n);
-    d_box = l.take<WpBox>(n);
-    d_words = l.take<int>(n);
-    d_tile = l.take<int>((size_t)scan_tiles(n) + 1);
-    d_out = l.take<u64>((size_t)c.bound_words);
-    d_area = l.take<u64>(n);
-    return l.bytes();
-  };
-  HostScope hs;
-  int rc = hs.open(device_id, layout(WsLayout()));
-  if (rc) return rc;
-  layout(WsLayout(hs.buf));
-  std::vector<WpBox> box((size_t)n, WpBox{INT_MAX, INT_MAX, -1, -1});
-  std::vector<u64> area((size_t)n, 0ull);
-  MNC_HIP_TRY(a.upload(hs));
-  MNC_HIP_TRY(hs.up(d_jobs, c.jobs.data(), (size_t)n * sizeof(WpJob)));
-  MNC_HIP_TRY(hs.up(d_box, box.data(), (size_t)n * sizeof(WpBox)));
-  MNC_HIP_TRY(hs.up(d_area, area.data(), (size_t)n * sizeof(u64)));
-  const MaskSet va = a.view();
-  const dim3 grid((unsigned)((c.most_blocks + kWpWaves - 1) / kWpWaves), (unsigned)n);
-  TimedSpan span(g_wp_timer);
-  span.begin(hs.stream);
-  hipLaunchKernelGGL(wp_extent_kernel, grid, dim3(kWpThreads), 0, hs.stream, d_jobs, va, c.map, d_box);
-  hipLaunchKernelGGL(wp_size_kernel, dim3((unsigned)((n + kWpThreads - 1) / kWpThreads)), dim3(kWpThreads), 0, hs.stream, d_jobs, n,
-                     d_box, d_words);
-  const Scanned first = scan_launch(hs.stream, d_words, n, d_tile);
-  hipLaunchKernelGGL(wp_fill_kernel, grid, dim3(kWpThreads), 0, hs.stream, d_jobs, va, c.map, d_box, first, d_out, d_area);
-  span.end(hs.stream);
-  MNC_HIP_TRY(hipGetLastError());
-  MNC_HIP_TRY(hs.down(box.data(), d_box, (size_t)n * sizeof(WpBox)));
-  MNC_HIP_TRY(hs.down(area.data(), d_area, (size_t)n * sizeof(u64)));
-  MNC_HIP_TRY(hs.sync());
-  span.keep();
-  long long at = 0;                                        // the offsets as the scan placed them: the bytes of the tight rows
-  for (int o = 0; o < n; ++o) at += mask_bytes(box[o].x2 - box[o].x1 + 1, box[o].y2 - box[o].y1 + 1);
-  if (at < 0 || (size_t)at > bound) {                      // (cannot be: a tight frame lies inside its loose one)
-    set_error("%s: the result's %lld bytes exceed the bound %zu", who, at, bound);
-    return MNC_ERR_HIP;
-  }
-  MNC_HIP_TRY(hs.down(out_bits, d_out, (size_t)at));
-  MNC_HIP_TRY(hs.sync());
-  at = 0;
-  for (int o = 0; o < n; ++o) {
-    int* q = out_bounds + 4 * (size_t)o;
-    q[0] = box[o].x1; q[1] = box[o].y1; q[2] = box[o].x2; q[3] = box[o].y2;
-    out_offsets[o] = at;
-    out_areas[o] = (long long)area[o];
-    at += mask_bytes(box[o].x2 - box[o].x1 + 1, box[o].y2 - box[o].y1 + 1);
-  }
-  *bits_bytes = (size_t)at;
-  clear_error();
-  return MNC_OK;
-}
 
 }  // namespace
 
@@ -350,12 +199,12 @@ int mnc_mask_isometry(const int* bounds, const long long* offsets, const void* b
   const char* who = "mnc_mask_isometry";
   MNC_REQUIRE(bits_bound, "%s: null bits_bound", who);
   MNC_REQUIRE(code >= 0 && code <= 7, "%s: code=%d not in [0, 7]", who, code);
-  MNC_REQUIRE(tx > -kWpMaxCoord && tx < kWpMaxCoord && ty > -kWpMaxCoord && ty < kWpMaxCoord, "%s: translation (%d, %d) out of range",
+  MNC_REQUIRE(tx > -kTightMaxCoord && tx < kTightMaxCoord && ty > -kTightMaxCoord && ty < kTightMaxCoord, "%s: translation (%d, %d) out of range",
               who, tx, ty);
   HostMaskSet A;
   int rc = wp_check_set(who, &A, bounds, offsets, bits, bytes, n);
   if (rc) return rc;
-  WpCall c;
+  WpCall c(A);
   // a result coordinate depends on the source y (code & 1) or x; the kernels ask the other way round: which sign the source x
   // (the new y for the transposing codes, code & 4; else the new x, code & 2) and the source y take
   c.map = WpMap{(code & 1) ? kWpTranspose : kWpRows, 0, 0, tx, ty, -1, {0, 0, 0, 0, 0, 0}, 1};
@@ -363,16 +212,16 @@ int mnc_mask_isometry(const int* bounds, const long long* offsets, const void* b
   c.map.negy = (code & 1) ? (code >> 1) & 1 : (code >> 2) & 1;
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = A.info[i];
-    if (!wp_rows(a)) { c.add_empty(); continue; }
+    if (!mask_has_rows(a)) { c.add_empty(); continue; }
     long long u1 = (code & 1) ? a.y1 : a.x1, u2 = (code & 1) ? a.y2 : a.x2, v1 = (code & 1) ? a.x1 : a.y1, v2 = (code & 1) ? a.x2 : a.y2;
     if (code & 2) { const long long t = -u2; u2 = -u1; u1 = t; }
     if (code & 4) { const long long t = -v2; v2 = -v1; v1 = t; }
     u1 += tx; u2 += tx; v1 += ty; v2 += ty;
-    MNC_REQUIRE(u1 > -kWpMaxCoord && u2 < kWpMaxCoord && v1 > -kWpMaxCoord && v2 < kWpMaxCoord,
+    MNC_REQUIRE(u1 > -kTightMaxCoord && u2 < kTightMaxCoord && v1 > -kTightMaxCoord && v2 < kTightMaxCoord,
                 "%s: the image of instance %d, (%lld, %lld, %lld, %lld), leaves the coordinate range", who, i, u1, v1, u2, v2);
     c.add((int)u1, (int)v1, (int)u2, (int)v2);
   }
-  return wp_run(who, c, A, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
+  return tight_run(who, c, g_wp_timer, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
 }
 
 // see include/mnc_hip.h
@@ -387,16 +236,14 @@ int mnc_mask_warp(const int* bounds, const long long* offsets, const void* bits,
     const long long lim = k % 3 == 2 ? kWpMaxOffset : kWpMaxLinear;
     MNC_REQUIRE(coef[k] >= -lim && coef[k] <= lim, "%s: coef[%d]=%lld exceeds 2^%d in magnitude", who, k, coef[k], k % 3 == 2 ? 60 : 32);
   }
-  for (int k = 0; k < 4; ++k)
-    MNC_REQUIRE(window[k] > -kWpMaxCoord && window[k] < kWpMaxCoord, "%s: window coordinate %d out of range", who, window[k]);
-  MNC_REQUIRE(window[2] >= window[0] && window[3] >= window[1], "%s: the window (%d, %d, %d, %d) is empty", who, window[0], window[1],
-              window[2], window[3]);
+  int rc = tight_check_window(who, window);
+  if (rc) return rc;
   i128 det = (i128)coef[0] * coef[4] - (i128)coef[1] * coef[3];
   MNC_REQUIRE(det != 0, "%s: the map is singular (c0 c4 == c1 c3)", who);
   HostMaskSet A;
-  int rc = wp_check_set(who, &A, bounds, offsets, bits, bytes, n);
+  rc = wp_check_set(who, &A, bounds, offsets, bits, bytes, n);
   if (rc) return rc;
-  WpCall c;
+  WpCall c(A);
   c.map = WpMap{kWpGather, 0, 0, 0, 0, -1, {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]}, den};
   for (int s = 0; s <= 32; ++s)
     if (den == 1ll << s) c.map.shift = s;
@@ -404,7 +251,7 @@ int mnc_mask_warp(const int* bounds, const long long* offsets, const void* bits,
   det *= sign;
   for (int i = 0; i < n; ++i) {
     const mnc_mask_info& a = A.info[i];
-    if (!wp_rows(a)) { c.add_empty(); continue; }
+    if (!mask_has_rows(a)) { c.add_empty(); continue; }
     // the destination pixels whose source lies in the bounds: P[0] <= c0 x + c1 y <= P[1], Q[0] <= c3 x + c4 y <= Q[1] -- a
     // parallelogram whose corners are rationals over det
     const i128 P[2] = {(i128)a.x1 * den - coef[2], ((i128)a.x2 + 1) * den - 1 - coef[2]};
@@ -422,7 +269,7 @@ int mnc_mask_warp(const int* bounds, const long long* offsets, const void* bits,
     if (x2 >= x1 && y2 >= y1) c.add((int)x1, (int)y1, (int)x2, (int)y2);
     else c.add_empty();
   }
-  return wp_run(who, c, A, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
+  return tight_run(who, c, g_wp_timer, out_bounds, out_offsets, out_areas, out_bits, bits_cap, bits_bound, bits_bytes, device_id);
 }
 
 // see include/mnc_hip.h

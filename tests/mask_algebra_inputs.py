@@ -2,8 +2,8 @@
 placed where csrc/mask_algebra.hip can go wrong -- widths around the 64-column word crossed with column offsets between the operands
 that make the funnel shift 0, non-zero and negative, row offsets that overlap and miss, bounds that are disjoint, nested, touching,
 without rows or without a pixel, windows that cut at and inside a word, groups of 0 to 200 members, a stack of 65 nested
-rectangles, and 300 overlapping blobs.  Every set is seeded; every reference (the numpy statements of mnc_amd.algebra) is computed
-once per key and left unchanged."""
+rectangles, 300 overlapping blobs, and 1025 instances of a few words each.  Every set is seeded; every reference (the numpy
+statements of mnc_amd.algebra) is computed once per key and left unchanged."""
 import os
 import sys
 
@@ -172,13 +172,31 @@ def equal_scores_set():
     return _pack(bounds, [BI.blob(rng, 30, 100) for _ in bounds], True, np.full(8, 0.5, np.float32))
 
 
+def edge_pair():
+    """(a, b) with len(a) == 1025 and len(b) == 1, for what is sized by the instances and not by their words: one instance past the
+    1024 entries of a scan tile (csrc/scan.h) and past four blocks of 256 lanes of the size kernel (csrc/mask_tight.hip).  a's
+    instances have 1 to 3 rows of 1 to 65 columns -- one word a row, two for every fifth -- between x = -30 and x = 235; every
+    seventh has no rows, every eleventh of the others no pixel.  b is one blob of 2 x 65."""
+    rng = np.random.default_rng(1708)
+    bounds, dense = [], []
+    for k in range(1025):
+        h, w = int(rng.integers(1, 4)), 65 if k % 5 == 4 else int(rng.integers(1, 66))
+        x, y = int(rng.integers(-30, 171)), int(rng.integers(-5, 30))
+        if k % 7 == 6:
+            h, w = (0, 0) if k % 2 else (h, 0)
+            x, y = (0, 0) if k % 2 else (x, y)
+        bounds.append([x, y, x + w - 1, y + h - 1])
+        dense.append(np.zeros((h, w), bool) if k % 7 == 6 or k % 11 == 10 else rng.random((h, w)) < 0.5)
+    return _pack(bounds, dense, True), _pack([[40, 8, 104, 9]], [BI.blob(rng, 2, 65)], True)
+
+
 def empty_set():
     return PackedMasks(np.zeros((0, 4), np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), None, None, np.zeros(0, np.uint64))
 
 
 SETS = {"word": word_pairs, "word_dirty": lambda: word_pairs(True), "relation": relation_pairs, "broadcast": broadcast_pair,
         "window": window_set, "crowd": crowd_set, "nested_up": lambda: nested_set(True), "nested_down": lambda: nested_set(False),
-        "blobs": blobs_set, "equal": equal_scores_set, "empty": empty_set}
+        "blobs": blobs_set, "equal": equal_scores_set, "edge": edge_pair, "empty": empty_set}
 _SETS, _REFERENCE = {}, {}
 
 

@@ -92,7 +92,8 @@ RESIZES = {(37, 70): [(74, 140), (111, 210), (37, 70), (13, 24), (8, 14), (36, 6
            (33, 63): [(66, 126), (11, 21), (33, 63), (49, 94), (20, 100)]}
 
 SETS = {"word": word_set, "word_dirty": lambda: word_set(True), "image0": lambda: image_set(*IMAGES[0]),
-        "image1": lambda: image_set(*IMAGES[1]), "negative": negative_set, "rectangle": rectangle_set, "empty": empty_set}
+        "image1": lambda: image_set(*IMAGES[1]), "negative": negative_set, "rectangle": rectangle_set, "empty": empty_set,
+        "edge": lambda: AI.get("edge")[0]}                   # 1025 instances of a few words each
 _SETS = {}
 
 

@@ -152,6 +152,20 @@ def test_layering_three_hundred_blobs():
     assert (got.areas < pm.areas).sum() > 100 and (got.areas == 0).sum() > 5
 
 
+# ---- more instances than a scan tile ----
+
+def test_1025_instances_cross_the_size_kernels_blocks_and_the_scans_tile():
+    a, b = AI.get("edge")
+    assert len(a) == 1025 and len(b) == 1
+    sizes = [a.size(i) for i in range(len(a))]
+    assert sum(h * w == 0 for h, w in sizes) == 146 and max(sizes) == (3, 65) and sum(w == 65 for h, w in sizes) > 100
+    tight = _combine("edge", "copy")
+    assert AI.canonical(tight) and (tight.areas[[h * w > 0 for h, w in sizes]] == 0).sum() > 50           # rows, and no pixel
+    assert tight.areas[1024] > 0 and tight.offsets[1024] > tight.offsets[1023] > 0           # the second tile begins behind the first
+    both = _combine("edge", "or")
+    assert AI.canonical(both) and (both.areas >= b.areas[0]).all()
+
+
 # ---- the C ABI ----
 
 def _combine_call(a, b, op, window, bits, bounds=None, cap=None):

@@ -56,6 +56,17 @@ def test_loose_bounds_and_set_padding_bits_change_nothing(code):
     assert WI.same_masks(WP.warp(dirty, coef, den, BIG), want)               # the other kernel
 
 
+# ---- more instances than a scan tile ----
+
+def test_1025_instances_cross_the_size_kernels_blocks_and_the_scans_tile():
+    pm = WI.get("edge")
+    assert len(pm) == 1025 and sum(h * w == 0 for h, w in (pm.size(i) for i in range(len(pm)))) == 146
+    for code, tx, ty in ((2, 19, -3), (1, -40, 7)):                          # rows stay rows; rows become columns of up to 65 rows
+        got = WP.isometry(pm, code, tx, ty)
+        assert WI.same_masks(got, WI.isometry_ref("edge", code, tx, ty)) and WI.canonical(got)
+        assert got.areas.sum() == pm.areas.sum() and got.areas[1024] > 0 and got.offsets[1024] > got.offsets[1023] > 0
+
+
 # ---- the empty cases ----
 
 def test_empty_cases():

@@ -1,6 +1,7 @@
 """The check every host-array entry of the mask files makes of a set of packed masks (csrc/mask_set.h: HostMaskSet::check), at each
-of the host sets that go through it: mnc_mask_overlaps a and b, mnc_mask_nms, mnc_mask_rle, mnc_mask_boundary, and dt and gt of
-mnc_mask_match and mnc_mask_match_boundary.  A set with a coordinate of 2^24, with an offset of 4, or with rows that reach past the
+of the host sets that go through it: mnc_mask_overlaps a and b, mnc_mask_nms, mnc_mask_rle, mnc_mask_boundary, dt and gt of
+mnc_mask_match and mnc_mask_match_boundary, and the sets of the tight-result entries (csrc/mask_tight.h): mnc_mask_combine a and b,
+mnc_mask_merge, mnc_mask_layer, mnc_mask_isometry and mnc_mask_warp.  A set with a coordinate of 2^24, with an offset of 4, or with rows that reach past the
 bytes given comes back as MNC_ERR_INVALID with the message that names the entry point, the set and the index, no output array
 written -- without a GPU: nothing of this may open a device.  The same for one refused parameter of each matching entry."""
 import os
@@ -100,8 +101,46 @@ def match_boundary(dt, gt, T=2, d=2):
     return _match("mnc_mask_match_boundary", dt, gt, T, (20, 30, d))
 
 
+def _tight(name, sets, middle):
+    """An entry of csrc/mask_tight.h's protocol: its sets, its own arguments, then bounds, offsets, areas, bits with their room, the
+    bound, the bytes and the device."""
+    outs = [out((2, 4), np.int32), out(2, np.int64), out(2, np.int64), out(20, np.uint64), out(1, np.uint64), out(1, np.uint64)]
+    p = _lib.ptr
+    return name, sets + tuple(p(m) for m in middle) + tuple(p(o) for o in outs[:4]) + (outs[3].nbytes, p(outs[4]), p(outs[5]), 0), outs
+
+
+TIGHT = {"group_ptr": np.array([0, 2], np.int64), "members": np.array([0, 1], np.int32), "coef": np.array([1, 0, 0, 0, 1, 0], np.int64),
+         "window": np.array([0, 0, 19, 29], np.int32)}
+
+
+def combine(a, b):
+    return _tight("mnc_mask_combine", a.args(areas=False) + b.args(areas=False), (1, None))          # a | b, no window
+
+
+def merge(s):
+    return _tight("mnc_mask_merge", s.args(areas=False), (TIGHT["group_ptr"], TIGHT["members"], 1, 0))
+
+
+def layer(s):
+    return _tight("mnc_mask_layer", s.args(areas=False), (s.scores, None))
+
+
+def isometry(s):
+    return _tight("mnc_mask_isometry", s.args(areas=False), (2, 19, 0))                              # fliplr of a 20-wide image
+
+
+def warp(s):
+    return _tight("mnc_mask_warp", s.args(areas=False), (TIGHT["coef"], 1, TIGHT["window"]))
+
+
 # set name in the messages -> the call with that set flawed and every other one good
 SETS = {
+    "combine a": ("a", lambda bad: combine(bad, Set())),
+    "combine b": ("b", lambda bad: combine(Set(), bad)),
+    "merge": ("masks", merge),
+    "layer": ("masks", layer),
+    "isometry": ("masks", isometry),
+    "warp": ("masks", warp),
     "overlaps a": ("a", lambda bad: overlaps(bad, Set())),
     "overlaps b": ("b", lambda bad: overlaps(Set(), bad)),
     "nms": ("masks", nms),
