@@ -133,23 +133,27 @@ def warp(s):
     return _tight("mnc_mask_warp", s.args(areas=False), (TIGHT["coef"], 1, TIGHT["window"]))
 
 
+# the good set beside a flawed one: the calls hold addresses alone, so it must outlive them (a Set() made in the lambda would be
+# freed before the call reads it)
+GOOD = Set()
+
 # set name in the messages -> the call with that set flawed and every other one good
 SETS = {
-    "combine a": ("a", lambda bad: combine(bad, Set())),
-    "combine b": ("b", lambda bad: combine(Set(), bad)),
+    "combine a": ("a", lambda bad: combine(bad, GOOD)),
+    "combine b": ("b", lambda bad: combine(GOOD, bad)),
     "merge": ("masks", merge),
     "layer": ("masks", layer),
     "isometry": ("masks", isometry),
     "warp": ("masks", warp),
-    "overlaps a": ("a", lambda bad: overlaps(bad, Set())),
-    "overlaps b": ("b", lambda bad: overlaps(Set(), bad)),
+    "overlaps a": ("a", lambda bad: overlaps(bad, GOOD)),
+    "overlaps b": ("b", lambda bad: overlaps(GOOD, bad)),
     "nms": ("masks", nms),
     "rle": ("masks", rle),
     "boundary": ("masks", boundary),
-    "match dt": ("dt", lambda bad: match(bad, Set())),
-    "match gt": ("gt", lambda bad: match(Set(), bad)),
-    "match_boundary dt": ("dt", lambda bad: match_boundary(bad, Set())),
-    "match_boundary gt": ("gt", lambda bad: match_boundary(Set(), bad)),
+    "match dt": ("dt", lambda bad: match(bad, GOOD)),
+    "match gt": ("gt", lambda bad: match(GOOD, bad)),
+    "match_boundary dt": ("dt", lambda bad: match_boundary(bad, GOOD)),
+    "match_boundary gt": ("gt", lambda bad: match_boundary(GOOD, bad)),
 }
 
 
