@@ -1342,7 +1342,10 @@ MNC_API int mnc_copy2d(mnc_ctx* ctx, float* d_dst, int dst_ld, const float* d_sr
  * Writes d_rois [post_nms_topn][5] (rows >= the row count are zero) and returns the row count in *num_rois_host (one 4-byte
  * D2H + stream sync).  num_rois_host == NULL: fully asynchronous, the count stays on the device until mnc_proposal_count
  * (the engine launches the heads on all post_nms_topn rows meanwhile and checks the count with the outputs).
- * Candidate order is score descending, anchor index ascending (the reference leaves tie order to numpy's sort). */
+ * Candidate order is score descending by value, anchor index ascending (the reference leaves tie order to numpy's sort); +0.0
+ * and -0.0 are one value and tie.  pre_nms_topn <= 0 keeps every box that passes the size filter; more than 16384 after the
+ * clamp to the anchor count is MNC_ERR_INVALID.  A NaN score cannot be seen from the host: it is ordered by its bit pattern
+ * (memory-safe) and the result is then unspecified. */
 MNC_API int mnc_proposal(mnc_ctx* ctx, const float* d_cls_prob, const float* d_bbox_pred, int A, int H, int W,
                          const float* anchors_host, int feat_stride, float im_h, float im_w, float im_scale,
                          int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* d_rois,

@@ -34,8 +34,10 @@ typedef unsigned long long u64;
 struct Anchors { float v[16][4]; int count; };
 
 __device__ __forceinline__ unsigned desc_key(float s) {
-  // ascending order of the result == descending order of s
+  // ascending order of the result == descending order of s; -0.0 is keyed as +0.0, so the two zeros tie and the anchor index
+  // in the low half of the key decides between them (the order is by value, not by bit pattern)
   unsigned b = __float_as_uint(s);
+  if ((b & 0x7FFFFFFFu) == 0u) b = 0u;
   unsigned asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
   return ~asc;
 }
