@@ -848,6 +848,59 @@ MNC_API int mnc_mask_warp(const int* bounds, const long long* offsets, const voi
 MNC_API int mnc_mask_warp_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n19 Label maps in and out of packed masks: the instances of an integer label map -- SBD's inst / cls arrays, Cityscapes'
+ *     instanceIds, the ids of a COCO panoptic PNG, a superpixel map -- as a set in the layout of n5, and the label map of a
+ *     set (csrc/mask_labels.hip).  The statements of the rules are mnc_amd/labels.py:from_labels_numpy and to_labels_numpy.
+ *     Integer arithmetic only; integer atomics only (or, min, max, add), all of which commute: the same input gives the same
+ *     bytes on every run.  A label map is int [H][W], row-major, with H and W in [1, 32768] and H * W <= 2^26.
+ *     From a map, two calls: mnc_label_table gives the instances -- the distinct values that are not skipped, ascending --
+ *     with their tight boxes, pixel counts and the bytes of their rows; mnc_label_masks, with room for those bytes, writes the
+ *     rows (offsets in order without gaps, as the host derives them from the boxes; padding bits 0).  Each call uploads the
+ *     map.  MNC_ERR_INVALID is checked on the host before anything is launched, with nothing written, except where an entry
+ *     says otherwise.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* label [H][W] with every value in [0, 2^24) (the host walks the map for this check and learns the largest id, which sizes
+ * the presence bitmap); cls NULL or [H][W], any int; skip [n_skip], n_skip <= 8: the values that are no instance (a skip value
+ * that does not occur, or lies outside the range, changes nothing).  Outputs, each [cap] with the first *n entries written:
+ * ids ascending, bounds [cap][4] = (x1, y1, x2, y2) inclusive, areas, cls_lo / cls_hi = the least and greatest value of cls on
+ * the instance's pixels (0 without cls; the caller decides what cls_lo != cls_hi means), *bits_bytes = the bytes of the rows
+ * of the boxes.  Six launches whatever the data: presence bits of the values by integer atomicOr, the skip values cleared
+ * and the words' popcounts, their prefix sum (two launches; at most 2^19 words of 32 bits, the largest count this file hands
+ * the scan), the boxes / areas / class ranges by one set of integer atomics per run of equal values of a row, the ids
+ * compacted by the prefix.  MNC_ERR_INVALID: a null label, n or bits_bytes; n_skip outside [0, 8]; cap < 0, or cap > 0 with a
+ * null output; H, W or H * W outside the limits; a value outside [0, 2^24).  A map with more than min(cap, 2048) instances is
+ * MNC_ERR_INVALID after the device work, with *n set to their number and nothing else written. */
+MNC_API int mnc_label_table(const int* label, const int* cls, int H, int W, const int* skip, int n_skip, int cap, int* n, int* ids,
+                            int* bounds, long long* areas, int* cls_lo, int* cls_hi, size_t* bits_bytes, int device_id);
+/* The rows of the n instances of the table (ids [n] strictly ascending in [0, 2^24), bounds [n][4] non-empty and inside the
+ * image) into out_bits: instance i is set where label == ids[i] inside bounds[i].  *bits_bytes = the bytes of the boxes; bytes
+ * past them are never written.  One launch over the zeroed output: a wave per 64 pixels of a row ballots the lanes of each
+ * distinct value, finds the value in ids by binary search and ORs the ballot, shifted by the box's x1, into one or two words by
+ * a 64-bit integer atomicOr.  The label values are not range-checked again: a value that is not in ids is no instance, and
+ * pixels of an id outside its box are dropped.  Areas are not recomputed.  n == 0 is answered on the host.  MNC_ERR_INVALID: a
+ * null label or bits_bytes; n outside [0, 2048]; n > 0 with null ids, bounds or out_bits; H, W or H * W outside the limits;
+ * ids out of range or not ascending; a box that is empty or leaves the image; bits_cap below the bytes of the boxes. */
+MNC_API int mnc_label_masks(const int* label, int H, int W, const int* ids, const int* bounds, int n, void* out_bits, size_t bits_cap,
+                            size_t* bits_bytes, int device_id);
+/* The label map out [H][W] of a set given as mnc_mask_rle takes one (bounds [n][4], offsets [n], bits, bytes): a pixel gets
+ * values[i] (NULL: i + 1) of the first instance i in the order that has it set, background where none has -- the painting loop
+ * run over the order backwards.  order [n]: a permutation, first the instance that is on top; NULL: by scores [n] descending,
+ * the lower index first on equal scores (mnc_mask_layer's order, made on the host the same way).  A mask is empty outside its
+ * bounds, bounds may be negative or unclipped (what lies outside the image is dropped), padding bits are not trusted, an
+ * instance without rows paints nothing.  One launch, no atomics, every pixel stored exactly once: a wave per 64-pixel strip
+ * of a row tests the bounds of 64 instances at a time, walks those that meet the strip in order and leaves when every pixel
+ * of the strip is taken.  n == 0 fills out with background on the host.  MNC_ERR_INVALID: a null out; everything
+ * mnc_mask_combine refuses about a set; H, W or H * W outside the limits; neither order nor scores (n > 0); order that is not a
+ * permutation; a NaN score when the order comes from the scores. */
+MNC_API int mnc_mask_to_labels(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, const float* scores,
+                               const int* order, const int* values, int background, int H, int W, int* out, int device_id);
+/* For tools/mask_labels_bench.py.  on = 1: the following calls of the three entries above put a HIP event pair around their
+ * launches (without the copies of the map, the set and the results) and keep the last call's time in milliseconds; on = 0:
+ * they do not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none;
+ * switching on forgets it. */
+MNC_API int mnc_mask_labels_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

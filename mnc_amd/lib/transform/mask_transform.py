@@ -226,6 +226,31 @@ def mask_overlaps(a, b=None):
     return device_overlaps(a, b, cfg.GPU_ID)
 
 
+def masks_from_labels(label, cls=None, background=0, classes=None):
+    """The instances of an integer label map (SBD's inst / cls arrays, Cityscapes' instanceIds, panoptic ids, superpixels) on the
+    GPU (mnc_label_table + mnc_label_masks, csrc/mask_labels.hip) -> (mnc_amd.masks.PackedMasks, ids int32 [n])."""
+    from mnc_amd.labels import from_labels as device_from_labels
+    return device_from_labels(label, cls, background, classes, cfg.GPU_ID)
+
+
+def masks_from_labels_numpy(label, cls=None, background=0, classes=None):
+    """masks_from_labels as plain numpy on the host: the CPU statement of the rule."""
+    from mnc_amd.labels import from_labels_numpy as host_from_labels
+    return host_from_labels(label, cls, background, classes)
+
+
+def mask_labels(pm, H, W, values=None, order=None, background=0):
+    """The label map int32 [H, W] of a PackedMasks on the GPU (mnc_mask_to_labels): every pixel gets the value of the first
+    instance in `order` (None: descending score) that covers it."""
+    return pm.to_labels(H, W, values, order, background, device_id=cfg.GPU_ID)
+
+
+def mask_labels_numpy(pm, H, W, values=None, order=None, background=0):
+    """mask_labels as the plain painting loop on the host: the CPU statement of the rule."""
+    from mnc_amd.labels import to_labels_numpy as host_to_labels
+    return host_to_labels(pm, H, W, values, order, background)
+
+
 def mask_overlaps_numpy(a, b=None):
     """mask_overlaps as the plain double loop over mask_overlap on the host: the CPU statement of the rule."""
     from mnc_amd.masks import mask_overlaps_numpy as host_overlaps

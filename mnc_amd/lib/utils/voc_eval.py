@@ -139,6 +139,18 @@ def parse_inst(image_name, devkit_path):
     return record
 
 
+def parse_inst_maps(inst, cls, on_device=False):
+    """The records of parse_inst from the two arrays themselves (GTinst's and GTcls's Segmentation): the same keys, dtypes, bounds
+    as float64 and order, made through mnc_amd.labels -- from_labels_numpy, or with on_device the GPU (mnc_label_table +
+    mnc_label_masks) -- in place of one np.where per instance.  An instance of mixed class raises ValueError where parse_inst
+    asserts."""
+    from mnc_amd import labels
+    inst, cls = np.asarray(inst), np.asarray(cls)
+    pm, _ = (labels.from_labels if on_device else labels.from_labels_numpy)(inst, cls, 0)
+    return [{'mask': pm.dense(k), 'mask_cls': cls.dtype.type(pm.classes[k]), 'mask_bound': pm.bounds[k].astype(np.float64)}
+            for k in range(len(pm))]
+
+
 def check_voc_sds_cache(cache_dir, devkit_path, image_names, class_names):
     """Builds <cache_dir>/<class>_mask_gt.pkl ({image: [instances]}) once."""
     if not os.path.isdir(cache_dir):

@@ -26,6 +26,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        instance, groups united or intersected, a set made disjoint (mnc_amd/algebra.py, n17)
     PackedMasks.translate / .fliplr / .flipud / .transpose / .rot90 / .isometry / .resize / .warp_affine / .warp   the geometric
                                        transforms: flips, quarter turns, and nearest-neighbour affine maps (mnc_amd/warp.py, n18)
+    PackedMasks.from_labels / .to_labels   the instances of an integer label map as a set, and the label map of a set
+                                       (mnc_amd/labels.py, n19)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -471,6 +473,22 @@ class PackedMasks(object):
         -> PackedMasks in the entries' order: one device call per kind, merged on the host."""
         from . import polygons
         return polygons.masks_from_segmentations(segs, H, W, classes, scores)
+
+    @classmethod
+    def from_labels(klass, label, cls=None, background=0, classes=None, device_id=None):
+        """The instances of an integer label map [H, W] with values in [0, 2^24) -- the distinct values that are not `background`
+        (one value, up to 8, or None), ascending -- -> (a host PackedMasks with tight bounds, ids int32 [n]), on the GPU by the
+        rule of mnc_amd.labels.from_labels_numpy (include/mnc_hip.h n19, csrc/mask_labels.hip).  Classes: cls, a map of the same
+        shape (an instance of mixed class raises ValueError), or classes, a dict or array looked up by id; else 0."""
+        from . import labels
+        return labels.from_labels(label, cls, background, classes, device_id)
+
+    def to_labels(self, H, W, values=None, order=None, background=0, device_id=None):
+        """The label map int32 [H, W] of these masks: a pixel gets values[i] (None: i + 1) of the first instance i in `order`
+        (None: layered()'s, descending score) that has it set, `background` where none has, on the GPU by the rule of
+        mnc_amd.labels.to_labels_numpy (mnc_mask_to_labels).  A device-resident result is fetched to the host first."""
+        from . import labels
+        return labels.to_labels(self, H, W, values, order, background, device_id)
 
     @classmethod
     def from_dense(cls, bounds, dense, classes=None, scores=None):

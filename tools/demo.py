@@ -6,7 +6,7 @@ optional visualisation.
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
                          [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes]]
                          [--min-component-area A [--largest-component]] [--smooth-radius R] [--exclusive]
-                         [--flip-tta [--tta-nms T]]
+                         [--flip-tta [--tta-nms T]] [--save-panoptic DIR]
 
 Differences that are deliberate: weights come from an .npz (h5py is optional); without --net seeded synthetic weights
 are used (the trained model cannot be fetched here), and --def defaults to the graph emitted by mnc_amd.models.
@@ -33,7 +33,11 @@ object PNG want.  It runs after --smooth-radius and before the component selecti
 --flip-tta is test-time augmentation by the mirror image: every image is also run mirrored (im[:, ::-1]), the mirrored run's packed
 masks are flipped back into the image's frame (PackedMasks.fliplr, csrc/mask_warp.hip; with --cpu mnc_amd.warp.isometry_numpy), the
 two sets are concatenated and reduced by the class-aware mask NMS at IoU --tta-nms (default 0.5), before everything above.  Off by
-default; without the flag the output is what it was."""
+default; without the flag the output is what it was.  --save-panoptic DIR writes, for every image, the label map of the masks the
+other writers would write -- after --smooth-radius, --exclusive and the component selection -- as DIR/<name>.png in the COCO
+panoptic encoding (PackedMasks.to_labels, csrc/mask_labels.hip; with --cpu mnc_amd.labels.to_labels_numpy; id = index + 1 through
+mnc_amd.labels.id_to_rgb, Pillow writes the file), and one DIR/panoptic.json with every image's segments_info; without the flag
+every output is what it was."""
 import argparse
 import os
 import time
@@ -91,6 +95,9 @@ def parse_args(argv=None):
     p.add_argument("--exclusive", dest="exclusive", action="store_true",
                    help="make the masks --save-masks / --save-coco / --save-annotations write pairwise disjoint: each pixel goes to "
                         "the best-scoring instance that covers it; after --smooth-radius, before the component selection")
+    p.add_argument("--save-panoptic", dest="save_panoptic", default=None, metavar="DIR",
+                   help="write every image's instances as one COCO panoptic PNG (the label map of the written masks, id = R + 256 G "
+                        "+ 65536 B) into DIR, and DIR/panoptic.json with their segments_info")
     p.add_argument("--flip-tta", dest="flip_tta", action="store_true",
                    help="also run every image mirrored, flip its masks back and merge the two sets by class-aware mask NMS, before "
                         "--smooth-radius, --exclusive and the component selection")
@@ -317,6 +324,23 @@ def _save_masks(out_dir, name, im_shape, result_mask, result_box, view=None, sco
     return out, packed
 
 
+def _save_panoptic(out_dir, name, im_shape, packed, cpu=False):
+    """The label map of one image's PackedMasks -- every pixel the index + 1 of the best-scoring instance that covers it, 0 where
+    none does (on the GPU, csrc/mask_labels.hip; cpu=True: the numpy statement) -> <out_dir>/<name>.png by the panoptic id rule
+    (id = R + 256 G + 65536 B) and the annotation entry {image_id, file_name, segments_info} of the segments that kept a pixel.
+    A device-resident result is fetched first."""
+    from PIL import Image
+    from mnc_amd import labels
+    h, w = im_shape[:2]
+    packed = packed.fetch()
+    seg = labels.to_labels_numpy(packed, h, w) if cpu else packed.to_labels(h, w)
+    os.makedirs(out_dir, exist_ok=True)
+    Image.fromarray(labels.id_to_rgb(seg), "RGB").save(os.path.join(out_dir, name + ".png"))
+    area = np.bincount(seg.reshape(-1), minlength=len(packed) + 1)[1:]
+    info = [dict(s, area=int(area[k])) for k, s in enumerate(labels.segments_info(packed, np.arange(1, len(packed) + 1))) if area[k]]
+    return {"image_id": name, "file_name": name + ".png", "segments_info": info}
+
+
 def build_net(args):
     from mnc_amd import models, synth
     prototxt = args.prototxt or models.write_mnc_5stage_test_prototxt()
@@ -346,7 +370,7 @@ def main(argv=None):
     if not images:
         print("no images given; running one synthetic 600x1000 image")
         images = [None]
-    coco, annotations, image_entries = [], [], []
+    coco, annotations, image_entries, panoptic = [], [], [], []
     for path in images:
         print("~" * 35)
         print("Demo for {}".format(path or "<synthetic 600x1000>"))
@@ -359,7 +383,7 @@ def main(argv=None):
         print("mask voting time %f" % (time.time() - start))
         pred = get_vis_dict(result_box, result_mask, path or "synthetic", CLASSES, args.vis_thresh)
         print("%d instances with score >= %g" % (len(pred["boxes"]), args.vis_thresh))
-        if args.save_masks or args.save_coco or args.save_annotations:
+        if args.save_masks or args.save_coco or args.save_annotations or args.save_panoptic:
             from mnc_amd.devarray import DeviceArray
             blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
             name = os.path.splitext(os.path.basename(path))[0] if path else "synthetic"
@@ -387,6 +411,9 @@ def main(argv=None):
                                       "width": int(im.shape[1])})
                 annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode, args.polygon_epsilon,
                                                      args.oriented_boxes))
+            if args.save_panoptic:
+                panoptic.append(_save_panoptic(args.save_panoptic, name, im.shape, packed, args.cpu_mode))
+                print("wrote %s.png (%d segments)" % (os.path.join(args.save_panoptic, name), len(panoptic[-1]["segments_info"])))
             if args.save_masks:
                 out, packed = _save_masks(args.save_masks, name, im.shape, result_mask, result_box, packed=packed)
                 print("wrote %s (%d masks, %d bytes of bits)" % (out, len(packed), packed.bits.nbytes))
@@ -400,7 +427,7 @@ def main(argv=None):
             from mnc_amd.devarray import DeviceArray
             blk = getattr(boxes._net, "_inst", None) if isinstance(boxes, DeviceArray) else None
             # (after --flip-tta's mirrored run the block holds the mirror image's records: the overlay then is the host's)
-            flipped = args.flip_tta and (args.save_masks or args.save_coco or args.save_annotations)
+            flipped = args.flip_tta and (args.save_masks or args.save_coco or args.save_annotations or args.save_panoptic)
             view = blk.view() if cfg.TEST.USE_GPU_VIS and blk is not None and im.dtype == np.uint8 and not flipped else None
             _visualise(im, pred, out, view, args.vis_thresh)
             print("wrote", out)
@@ -409,6 +436,11 @@ def main(argv=None):
         with open(args.save_coco, "w") as f:
             json.dump(coco, f)
         print("wrote %s (%d instances)" % (args.save_coco, len(coco)))
+    if args.save_panoptic:
+        import json
+        with open(os.path.join(args.save_panoptic, "panoptic.json"), "w") as f:
+            json.dump({"annotations": panoptic, "categories": [{"id": k + 1, "name": c, "isthing": 1} for k, c in enumerate(CLASSES)]}, f)
+        print("wrote %s (%d images)" % (os.path.join(args.save_panoptic, "panoptic.json"), len(panoptic)))
     if args.save_annotations:
         import json
         with open(args.save_annotations, "w") as f:
