@@ -901,6 +901,42 @@ MNC_API int mnc_mask_to_labels(const int* bounds, const long long* offsets, cons
 MNC_API int mnc_mask_labels_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n20 The contingency table of two label maps: for every pair of values (a, b) that occurs at the same pixel, the number of
+ *     such pixels (csrc/label_pairs.hip) -- the table panoptic quality matches segments on, and the confusion matrix of a
+ *     semantic result.  The statement of the rule is mnc_amd/pairs.py:label_pairs_numpy.  Integer arithmetic only; integer
+ *     atomics only (or, add), which commute, and the order of the output comes from prefix sums, never from the arrival order
+ *     of an atomic: the same input gives the same bytes on every run.  The maps are int [H][W], row-major, of one shape, with
+ *     H and W in [1, 32768] and H * W <= 2^26, every value in [0, 2^24); no value is background.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Host pointers; one call uploads each map once.  Outputs: *na / *nb = the number of distinct values of a / b, at most 65536
+ * each with na * nb <= 2^22 cells; a_ids / b_ids [cap_ids] with the first *na / *nb entries written, ascending; *n_pairs = m, the
+ * number of pairs that occur; ia, ib, count [cap_pairs] with the first m entries written: the ranks of the pair's values in
+ * a_ids / b_ids and its pixels (positive, summing to H * W), sorted by (ia, ib) ascending.  The launches: the presence bits of
+ * both maps by integer atomicOr into one bitmap (a value outside the range sets none and joins a flag word instead: the host
+ * does not walk the maps), the words' popcounts, their prefix sum; after a read-back of *na, *nb and the flag, the counts of the
+ * pairs' runs by integer atomicAdd into a zeroed int32 table [na][nb] -- tables of at most 16384 cells are counted per workgroup
+ * in LDS and added to it once, the others, and every size after mnc_label_pairs_plan(1), in device memory; both give the
+ * same integers --, the non-zero cells per 64 by ballot, their prefix sum, the pairs written at
+ * prefix plus rank, the ids at their ranks.  MNC_ERR_INVALID, checked on the host before anything is launched, with nothing
+ * written: a null a, b, na, nb or n_pairs; a negative cap; a positive cap with a null output of its kind; H, W or H * W outside
+ * the limits.  MNC_ERR_INVALID after the device work: a value outside [0, 2^24), with nothing written (mnc_last_error names the
+ * first one as "a[y][x]=v not in [0, 16777216)"); more than min(cap_ids, 65536) values in a map or more than 2^22 cells, with
+ * *na and *nb set and nothing else written; more than cap_pairs pairs, with *na, *nb and *n_pairs set and nothing else
+ * written. */
+MNC_API int mnc_label_pairs(const int* a, const int* b, int H, int W, int cap_ids, long long cap_pairs, int* na, int* a_ids, int* nb,
+                            int* b_ids, long long* n_pairs, int* ia, int* ib, long long* count, int device_id);
+/* For tools/label_pairs_bench.py and the tests.  plan = 1: the following calls of mnc_label_pairs, on every device and thread of the
+ * process, count every table in device memory (the global plan); plan = 0: tables of at most 16384 cells in LDS (the default).
+ * MNC_ERR_INVALID: any other value. */
+MNC_API int mnc_label_pairs_plan(int plan);
+/* For tools/label_pairs_bench.py.  on = 1: the following calls of mnc_label_pairs put HIP event pairs around their two groups of
+ * launches (without the copies of the maps and of the results, and without the read-back between the groups) and keep the last
+ * call's summed time in milliseconds; on = 2: the pair is put around the counting launch alone; on = 0: they do not (the
+ * default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is none; switching on forgets
+ * it. */
+MNC_API int mnc_label_pairs_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

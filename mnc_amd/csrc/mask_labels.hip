@@ -3,7 +3,8 @@
 // map of a set of packed masks (mnc_mask_to_labels).  The statements of the rules are mnc_amd/labels.py:from_labels_numpy and
 // to_labels_numpy; this file computes the same tables, words and maps exactly.  All arithmetic is integer.
 //
-// mnc_label_table, one pass over the map per step and six launches whatever the data:
+// mnc_label_table, one pass over the map per step and six launches whatever the data (lb_presence_kernel, lb_count_kernel, lb_rank
+// and lb_ids_kernel are label_bits.h's, shared with label_pairs.hip):
 //   lb_presence_kernel   a lane owns kLbRun consecutive pixels of the flat map (one 16-byte load); a value's bit is ORed into a
 //                        presence bitmap of 32-bit words sized to the largest id once per change of value inside the lanes' runs,
 //                        by one lane of the wave for all that have the value, and only where a relaxed look does not show the
@@ -35,22 +36,10 @@
 #include <climits>
 #include <vector>
 
+#include "label_bits.h"
 #include "mask_tight.h"
 
 namespace mnc {
-
-constexpr int kLbThreads = 256;
-constexpr int kLbRun = 4;                          // pixels of one lane in the table passes
-constexpr int kLbMaxId = 1 << 24;                  // label values lie in [0, kLbMaxId)
-constexpr int kLbMaxWords = kLbMaxId / 32;         // 2^19 words of the presence bitmap: the scan's largest count
-constexpr int kLbMaxSide = 32768;
-constexpr long long kLbMaxPixels = 1ll << 26;
-constexpr int kLbMaxSkip = 8;
-
-struct LbSkip {
-  int v[kLbMaxSkip];
-  int n;
-};
 
 // One instance of mnc_label_masks: its value, its box, the words of a row and its first word in the output.
 struct LbInst {
@@ -62,71 +51,6 @@ struct LbInst {
 struct LbSeq {
   int idx, value;
 };
-
-// The (at most kLbRun) values of the flat array from p on -> how many there are.
-__device__ __forceinline__ int lb_load(const int* __restrict__ a, long long p, long long total, int& v0, int& v1, int& v2, int& v3) {
-  if (p + kLbRun <= total) {
-    const int4 q = *reinterpret_cast<const int4*>(a + p);  // p is a multiple of 4 and the map starts on a 256-byte boundary
-    v0 = q.x; v1 = q.y; v2 = q.z; v3 = q.w;
-    return kLbRun;
-  }
-  const int count = (int)(total - p);
-  v0 = a[p];
-  v1 = count > 1 ? a[p + 1] : 0;
-  v2 = count > 2 ? a[p + 2] : 0;
-  v3 = 0;
-  return count;
-}
-
-// A relaxed look at a word that others join atomically.  The joins are monotone (bits are only set, a minimum only falls, a maximum
-// only rises), so a stale value can only make the caller issue an atomic it did not need, never skip one it did.
-template <class T>
-__device__ __forceinline__ T lb_peek(T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// grid ceil(total / 1024), block 256.  The wave shares its atomics: for each of the lanes' kLbRun positions, the lanes whose value
-// changes there are balloted value by value and the first lane of each value sets its bit.
-__global__ __launch_bounds__(kLbThreads) void lb_presence_kernel(const int* __restrict__ label, long long total, int words,
-                                                                 unsigned* present) {
-  const long long p = ((long long)blockIdx.x * kLbThreads + threadIdx.x) * kLbRun;
-  const int lane = threadIdx.x & 63;
-  int v[kLbRun] = {-1, -1, -1, -1};
-  const int count = p < total ? lb_load(label, p, total, v[0], v[1], v[2], v[3]) : 0;
-  int prev = -1;
-#pragma unroll
-  for (int e = 0; e < kLbRun; ++e) {
-    const bool fresh = e < count && v[e] != prev && (unsigned)(v[e] >> 5) < (unsigned)words;
-    u64 rest = __ballot(fresh);
-    while (rest) {
-      const int first = __ffsll((long long)rest) - 1;
-      const int lv = __shfl(v[e], first);
-      rest &= ~__ballot(fresh && v[e] == lv);
-      const unsigned bit = 1u << (lv & 31);
-      if (lane == first && !(lb_peek(present + (lv >> 5)) & bit)) atomicOr(present + (lv >> 5), bit);
-    }
-    prev = e < count ? v[e] : prev;
-  }
-}
-
-// grid ceil(words / 256), block 256.
-__global__ __launch_bounds__(kLbThreads) void lb_count_kernel(unsigned* __restrict__ present, int words, LbSkip skip,
-                                                              int* __restrict__ cnt) {
-  const int w = blockIdx.x * kLbThreads + threadIdx.x;
-  if (w >= words) return;
-  unsigned m = present[w];
-#pragma unroll
-  for (int k = 0; k < kLbMaxSkip; ++k)
-    if (k < skip.n && (skip.v[k] >> 5) == w) m &= ~(1u << (skip.v[k] & 31));
-  present[w] = m;
-  cnt[w] = __popc(m);
-}
-
-// The rank of value v among the instances, -1 when it is none.
-__device__ __forceinline__ int lb_rank(const unsigned* __restrict__ present, int words, const Scanned& pre, int v) {
-  const int w = v >> 5;
-  if ((unsigned)w >= (unsigned)words) return -1;
-  const unsigned m = present[w], bit = 1u << (v & 31);
-  return (m & bit) ? pre.at(w) + __popc(m & (bit - 1u)) : -1;
-}
 
 struct LbStats {
   int* box;      // [cap][4], (INT_MAX, INT_MAX, INT_MIN, INT_MIN) before
@@ -202,18 +126,6 @@ __global__ __launch_bounds__(kLbThreads) void lb_stats_kernel(const int* __restr
   if (live && !joins) {
     const int k = lb_rank(present, words, pre, rv);
     if (k >= 0 && k < cap) lb_join(st, cls != nullptr, k, rx1, rx2, ry, rclo, rchi);
-  }
-}
-
-// grid ceil(words / 256), block 256.
-__global__ __launch_bounds__(kLbThreads) void lb_ids_kernel(const unsigned* __restrict__ present, int words, Scanned pre, int cap,
-                                                            int* __restrict__ ids) {
-  const int w = blockIdx.x * kLbThreads + threadIdx.x;
-  if (w >= words) return;
-  unsigned m = present[w];
-  for (int k = pre.at(w); m && k < cap; ++k) {
-    ids[k] = w * 32 + (__ffs((int)m) - 1);
-    m &= m - 1u;
   }
 }
 
@@ -350,7 +262,7 @@ int mnc_label_table(const int* label, const int* cls, int H, int W, const int* s
   TimedSpan span(g_lb_timer);
   span.begin(hs.stream);
   const unsigned px_blocks = lb_blocks((total + kLbRun - 1) / kLbRun);
-  hipLaunchKernelGGL(lb_presence_kernel, dim3(px_blocks), dim3(kLbThreads), 0, hs.stream, d_label, total, words, d_present);
+  hipLaunchKernelGGL(lb_presence_kernel, dim3(px_blocks), dim3(kLbThreads), 0, hs.stream, d_label, total, words, d_present, nullptr);
   hipLaunchKernelGGL(lb_count_kernel, dim3(lb_blocks(words)), dim3(kLbThreads), 0, hs.stream, d_present, words, sk, d_cnt);
   const Scanned pre = scan_launch(hs.stream, d_cnt, words, d_tile);
   hipLaunchKernelGGL(lb_stats_kernel, dim3(px_blocks), dim3(kLbThreads), 0, hs.stream, d_label, cls ? d_cls : nullptr, W, total,
