@@ -964,11 +964,35 @@ MNC_API int mnc_bbox_overlaps(const double* boxes, int n, const double* query_bo
  * Engine context: one per process per GPU (b5: `caffe.set_device`, one `caffe.Net` per process).  Owns a HIP
  * stream and all device scratch.  Not thread-safe; use one context per thread.
  * Hosts that keep several images in flight use one context (stream) per image.  The HIP runtime maps streams onto
- * GPU_MAX_HW_QUEUES hardware queues (default 4; streams that share a queue serialise): when this library is loaded it sets
- * GPU_MAX_HW_QUEUES=16 in the process environment unless the variable is already set -- effective when that happens before the
- * process's first HIP call (round 6; profiles/r06_streams.txt).
+ * GPU_MAX_HW_QUEUES hardware queues (default 4; streams that share a queue serialise; round 6, profiles/r06_streams.txt), and
+ * reads that variable once, at the process's first HIP call.  When this library is loaded it therefore makes a REQUEST
+ * (profiles/hw_queues.txt): the environment variable MNC_HW_QUEUES -- unset: 16; "0": leave GPU_MAX_HW_QUEUES alone; any other
+ * integer, clamped to 4 .. 32 (text that is no integer counts as unset).  A GPU_MAX_HW_QUEUES that is absent, no positive integer
+ * or LOWER than the request is set to the request; an equal or higher one is kept: the library never lowers it, and MNC_HW_QUEUES
+ * is the one way to opt out or to choose (raising a value the host exported prints one line on stderr).  The request is void when HIP was initialised before the library was loaded (another
+ * library's import came first): mnc_stream_concurrency measures what the process really has.  The load-time hook uses getenv /
+ * setenv, which are not safe against other threads using the environment at that moment: a host that dlopen()s the library late,
+ * beside running threads, exports GPU_MAX_HW_QUEUES itself beforehand and sets MNC_HW_QUEUES=0.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct mnc_ctx mnc_ctx;
+
+/* What the request did to GPU_MAX_HW_QUEUES. */
+#define MNC_HWQ_UNTOUCHED 0   /* MNC_HW_QUEUES=0: the variable was left as it was */
+#define MNC_HWQ_KEPT 1        /* the exported value was already the request or more */
+#define MNC_HWQ_RAISED 2      /* the variable was absent, unusable or lower: set to the request */
+/* The policy itself, a pure function of two strings (either may be NULL = not in the environment): exported = GPU_MAX_HW_QUEUES,
+ * setting = MNC_HW_QUEUES.  *value = what GPU_MAX_HW_QUEUES holds afterwards (0: still absent / unusable), *action = MNC_HWQ_*.
+ * Reads and changes nothing; no HIP call. */
+MNC_API int mnc_hw_queue_policy(const char* exported, const char* setting, int* value, int* action);
+/* What the load-time hook did in this process: *requested = the request (0 = MNC_HW_QUEUES=0), *exported_before = the value
+ * GPU_MAX_HW_QUEUES had when the library was loaded (-1: absent or no positive integer), *action = MNC_HWQ_*.  No HIP call. */
+MNC_API int mnc_hw_queue_request(int* requested, int* exported_before, int* action);
+/* The number of hardware queues n_streams streams really get in this process, measured (csrc/queue_probe.hip): n_streams
+ * (1 .. 32) non-blocking streams are created, each runs one 64-thread workgroup that spins for 1 ms of the device's wall clock
+ * (an iteration cap bounds it whatever the clock does), and *concurrent = the largest number of those intervals that overlap --
+ * kernels of streams that share a queue run one after the other.  A few milliseconds; the streams are destroyed again.  The
+ * figure is a lower bound when other work keeps the device's CUs full meanwhile.  MNC_ERR_INVALID: n_streams out of range. */
+MNC_API int mnc_stream_concurrency(int device, int n_streams, int* concurrent);
 
 MNC_API int mnc_ctx_create(mnc_ctx** out, int device_id);
 MNC_API int mnc_ctx_destroy(mnc_ctx* ctx);

@@ -107,6 +107,81 @@ def device_mem_info(device_id=0):
     return fr.value, tot.value
 
 
+HWQ_ACTIONS = ("untouched", "kept", "raised")      # MNC_HWQ_UNTOUCHED / _KEPT / _RAISED (include/mnc_hip.h)
+
+
+def _cstr(s):
+    return None if s is None else ctypes.cast(ctypes.c_char_p(s.encode()), ctypes.c_void_p)
+
+
+def hw_queue_policy(exported, setting):
+    """The library's request for hardware queues as a pure function (mnc_hw_queue_policy): exported = GPU_MAX_HW_QUEUES, setting =
+    MNC_HW_QUEUES, each a str or None (not in the environment) -> (value of GPU_MAX_HW_QUEUES afterwards, 0 = still absent;
+    "untouched" | "kept" | "raised").  No HIP call."""
+    value, action = ctypes.c_int(0), ctypes.c_int(0)
+    e, s = _cstr(exported), _cstr(setting)
+    call("mnc_hw_queue_policy", e, s, ctypes.addressof(value), ctypes.addressof(action))
+    return value.value, HWQ_ACTIONS[action.value]
+
+
+def hw_queue_request():
+    """What the library's load-time hook did in this process -> {"requested": n (0: MNC_HW_QUEUES=0), "exported_before": the
+    GPU_MAX_HW_QUEUES it found (None: absent or unusable), "action": "untouched" | "kept" | "raised"}.  No HIP call."""
+    r, b, a = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    call("mnc_hw_queue_request", ctypes.addressof(r), ctypes.addressof(b), ctypes.addressof(a))
+    return {"requested": r.value, "exported_before": None if b.value < 0 else b.value, "action": HWQ_ACTIONS[a.value]}
+
+
+def stream_concurrency(n_streams, device_id=0):
+    """How many of n_streams (1 .. 32) fresh streams run side by side on the device = the hardware queues they got, measured
+    (mnc_stream_concurrency; a few milliseconds)."""
+    n = ctypes.c_int(0)
+    call("mnc_stream_concurrency", int(device_id), int(n_streams), ctypes.addressof(n))
+    return n.value
+
+
+_hw_queues = {}            # device -> stream_concurrency(32), NativeNet.hw_queues()
+_family_probe = {}         # device -> (streams probed, concurrent) of check_hw_queues' last measurement
+_hw_queues_warned = False
+
+
+def hw_queues(device_id=0):
+    """The hardware queues this process's streams get on the device: stream_concurrency(32), measured once per device and kept.
+    Measure while the device is idle: a probe stream that shares a queue with a busy stream waits behind it, and the figure is
+    then a lower bound."""
+    if device_id not in _hw_queues:
+        _hw_queues[device_id] = stream_concurrency(32, device_id)
+    return _hw_queues[device_id]
+
+
+def check_hw_queues(n_nets, device_id=0, who="nets"):
+    """Warn, once per process, when n_nets streams of images in flight have fewer hardware queues than that: streams that share a
+    queue serialise (profiles/hw_queues.txt: twelve images on four queues cost 5-6 %).  Changes nothing.  The measurement uses as many
+    streams as the family has nets, not more, and is repeated as the family grows until one comes out short (that figure is the
+    queue count and is kept).  Nets are added before images run, so the device is idle then; on a busy device the figure is a lower
+    bound and the warning may be early.  -> the measured figure, or None for up to four nets: four queues are the runtime's own
+    default and the floor of the library's request, only a host that exported fewer itself and set MNC_HW_QUEUES=0 has less, so
+    nothing is measured for them."""
+    global _hw_queues_warned
+    if n_nets <= 4:
+        return None
+    probed, q = _family_probe.get(device_id, (0, 0))
+    if q == probed and n_nets > probed:                       # (never short so far, and more nets than were ever tried)
+        probed, q = min(n_nets, 32), stream_concurrency(min(n_nets, 32), device_id)
+        _family_probe[device_id] = (probed, q)
+    if q < probed and n_nets > q and not _hw_queues_warned:      # (a measurement that came out short: q is the queue count)
+        _hw_queues_warned = True
+        import warnings
+        r = hw_queue_request()
+        why = ("MNC_HW_QUEUES=0 left GPU_MAX_HW_QUEUES at %s" % r["exported_before"] if r["action"] == "untouched" else
+               "the library asked for %d (GPU_MAX_HW_QUEUES %s), but the HIP runtime was initialised before libmnc_hip.so was loaded "
+               "or grants fewer" % (max(r["requested"], r["exported_before"] or 0), r["action"]))
+        warnings.warn("%d %s on GPU %d share %d hardware queue(s): streams on one queue run one after the other (%s); call "
+                      "mnc_amd._lib.load() before anything else in the process uses HIP, or set MNC_HW_QUEUES / GPU_MAX_HW_QUEUES"
+                      % (n_nets, who, device_id, q, why), RuntimeWarning, stacklevel=3)
+    return q
+
+
 def timing(entry_name, on):
     """One of the mnc_*_timing entries (boundary, polygons, accumulate, components): switch its event pair on or off -> the
     kernels' milliseconds of the last timed call before the switch (-1.0: none)."""

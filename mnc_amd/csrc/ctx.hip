@@ -1,5 +1,6 @@
 // Context, device memory, error reporting and HIP-event profiling for libmnc_hip.so.
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 
 #include "mnc_internal.h"
@@ -135,10 +136,85 @@ int mnc_device_count(int* count) {
 // Round 6: the HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); a host that keeps more images in flight
 // than that has streams sharing a queue, and a shared queue serialises them (profiles/r06_streams.txt: the dip at the fifth stream).
 // With 16 queues twelve images in flight measure 280.6 images/s against 270.0 with four (fp32, one box, two runs each; 8 queues / 8
-// images: 278.2).  The variable is read when the runtime initialises -- at the process's first HIP call -- so the library sets a
-// default when it is loaded, before it makes any (an already exported value wins; a process that initialised HIP earlier keeps its
-// own setting).
-__attribute__((constructor)) static void mnc_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", /*overwrite=*/0); }
+// images: 278.2; twelve images on four queues: 264.9).  The variable is read when the runtime initialises -- at the process's first
+// HIP call -- so the library makes its request when it is loaded, before it makes any.
+//
+// The request (profiles/hw_queues.txt): MNC_HW_QUEUES unset = 16, "0" = leave the runtime's variable alone, any other integer clamped
+// to 4 .. 32 (below 4 the runtime can crash replaying a captured graph with parallel branches; 32 is the most a shared machine
+// grants); text that is no integer counts as unset.  An exported GPU_MAX_HW_QUEUES that is absent, no positive integer, or LOWER
+// than the request is raised to the request; one that is equal or higher is kept -- the library never lowers it.  (Until this
+// change an exported value always won: a machine that exports the runtime's own default of 4 in front of every command ran twelve
+// streams on four queues without a word.)  MNC_HW_QUEUES is the one way to opt out or to choose.
+static int parse_int(const char* s, long* out) {      // the whole string is one integer (blanks around it allowed)
+  if (!s) return 0;
+  char* end = nullptr;
+  const long v = strtol(s, &end, 10);                 // (an integer too large for a long comes back as LONG_MAX / LONG_MIN: clamped like any other)
+  if (end == s) return 0;
+  while (*end == ' ' || *end == '\t' || *end == '\n') ++end;
+  if (*end) return 0;
+  *out = v;
+  return 1;
+}
+
+// MNC_HW_QUEUES -> the request: 0 = leave the variable alone, else 4 .. 32
+static int hw_queue_want(const char* setting) {
+  long want = 16;
+  if (!parse_int(setting, &want)) return 16;
+  return want == 0 ? 0 : want < 4 ? 4 : want > 32 ? 32 : (int)want;
+}
+
+// GPU_MAX_HW_QUEUES as exported -> its value, 0 when absent or no positive integer
+static int hw_queue_exported(const char* exported) {
+  long have = 0;
+  if (!parse_int(exported, &have) || have <= 0) return 0;
+  return have > INT_MAX ? INT_MAX : (int)have;
+}
+
+static int hw_queue_decide(int have, int want, int* value) {
+  *value = want != 0 && have < want ? want : have;
+  return want == 0 ? MNC_HWQ_UNTOUCHED : have >= want ? MNC_HWQ_KEPT : MNC_HWQ_RAISED;
+}
+
+static int g_hwq_requested = 0, g_hwq_exported_before = -1, g_hwq_action = MNC_HWQ_UNTOUCHED;
+
+int mnc_hw_queue_policy(const char* exported, const char* setting, int* value, int* action) {
+  MNC_REQUIRE(value && action, "mnc_hw_queue_policy: null pointer");
+  *action = hw_queue_decide(hw_queue_exported(exported), hw_queue_want(setting), value);
+  clear_error();
+  return MNC_OK;
+}
+
+// The hook.  A constructor, because the request only counts before the process's first HIP call and the library cannot know which of
+// its entries that will be.  getenv / setenv are not safe against other threads using the environment at the same moment: a host that
+// dlopen()s the library late, while other threads may call getenv, exports GPU_MAX_HW_QUEUES itself before it starts them (and sets
+// MNC_HW_QUEUES=0).  No other variable of the runtime is touched.  Overriding a value the host exported prints one line on stderr.  mnc_hw_queue_request reports what happened here;
+// mnc_stream_concurrency (queue_probe.hip) measures what the runtime really gave -- the request is void when something else
+// initialised HIP before the library was loaded.
+__attribute__((constructor)) static void mnc_request_hw_queues() {
+  const int have = hw_queue_exported(getenv("GPU_MAX_HW_QUEUES"));
+  int value = 0;
+  g_hwq_requested = hw_queue_want(getenv("MNC_HW_QUEUES"));
+  g_hwq_exported_before = have > 0 ? have : -1;
+  g_hwq_action = hw_queue_decide(have, g_hwq_requested, &value);
+  if (g_hwq_action == MNC_HWQ_RAISED) {
+    char buf[16];
+    snprintf(buf, sizeof(buf), "%d", value);
+    setenv("GPU_MAX_HW_QUEUES", buf, /*overwrite=*/1);
+    // a value the host exported itself is overridden: say so, once per process, where an operator looks
+    if (have > 0)
+      fprintf(stderr, "libmnc_hip: GPU_MAX_HW_QUEUES raised from %d to %d for this process (MNC_HW_QUEUES=0 keeps the exported value)\n",
+              have, value);
+  }
+}
+
+int mnc_hw_queue_request(int* requested, int* exported_before, int* action) {
+  MNC_REQUIRE(requested && exported_before && action, "mnc_hw_queue_request: null pointer");
+  *requested = g_hwq_requested;
+  *exported_before = g_hwq_exported_before;
+  *action = g_hwq_action;
+  clear_error();
+  return MNC_OK;
+}
 
 int mnc_ctx_create(mnc_ctx** out, int device_id) {
   MNC_REQUIRE(out, "mnc_ctx_create: null out pointer");

@@ -104,6 +104,8 @@ class NativeNet(object):
             _lib.call("mnc_net_create_shared", self._ctx.h, parent.h, ctypes.addressof(h))
             self.h = h.value
             parent._sharers = getattr(parent, "_sharers", 0) + 1
+            # the family's nets run side by side, one stream each: say so when the process has fewer hardware queues than that
+            _lib.check_hw_queues(parent._sharers + 1, self._ctx.device_id, "nets sharing one weight set")
             self.S = parent.S
             self.rec_dim = parent.rec_dim
             self.rows_cap = parent.rows_cap
@@ -253,6 +255,11 @@ class NativeNet(object):
     def sync(self):
         _lib.call("mnc_ctx_sync", self._ctx.h)
 
+    def hw_queues(self):
+        """The hardware queues this process's streams get on the net's device, measured (mnc_stream_concurrency, once per device):
+        more nets in flight than this share queues, and streams on one queue run one after the other."""
+        return _lib.hw_queues(self._ctx.device_id)
+
     def arena_generation(self):
         """How often the context re-allocated one of its internal device arenas (a captured graph is dropped when it moves)."""
         g = ctypes.c_ulong(0)
@@ -282,8 +289,11 @@ class ImageStream(object):
     """Throughput form of NativeNet: `in_flight` nets (own context, stream and buffers each; ONE set of device weights, shared:
     mnc_net_create_shared) on ONE GPU, images
     submitted round-robin -- image k+1 is launched before image k is fetched, so the stretches of an image that occupy one or a
-    few workgroups (proposal top-k, NMS scans, voting) run beside another image's convolutions.  Every image in flight has a
-    hardware queue of its own (the library asks the runtime for 16: GPU_MAX_HW_QUEUES) and 1.2 GB of activation buffers; round 6,
+    few workgroups (proposal top-k, NMS scans, voting) run beside another image's convolutions.  Every image in flight needs a
+    hardware queue of its own and 1.2 GB of activation buffers.  The library asks the runtime for 16 queues when it is loaded
+    (MNC_HW_QUEUES: 0 = do not ask, else 4 .. 32; a lower exported GPU_MAX_HW_QUEUES is raised, a higher one kept), which is void
+    when HIP was initialised earlier: hw_queues() is the measured count, and a stream with more nets than queues warns once (twelve
+    images on four queues cost 5-6 %, profiles/hw_queues.txt).  Round 6,
     profiles/r06_streams.txt: 270 / 278 / 281 images/s at 600x1000 in fp32 with 4 / 8 / 12 in flight, 239 one at a time (the
     library's launch plans are made for this form -- least CU time per launch, MNC_PLAN=1 for the latency plans).  Results come back
     in submission order and equal NativeNet.forward_image's.
@@ -307,6 +317,11 @@ class ImageStream(object):
         self.nets = [first] + [NativeNet(first, **vote) for _ in range(int(in_flight) - 1)]
         self._pending = []                      # indices of the nets holding an unfetched image, oldest first
         self._next = 0
+        # (NativeNet(first) has compared the family with the measured hardware queues as each net joined, and warned if they are short)
+
+    def hw_queues(self):
+        """The measured hardware queues of the stream's device (NativeNet.hw_queues)."""
+        return self.nets[0].hw_queues()
 
     def _take(self, net, record_cap):
         res = net.fetch(record_cap)
