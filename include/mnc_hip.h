@@ -937,6 +937,47 @@ MNC_API int mnc_label_pairs_plan(int plan);
 MNC_API int mnc_label_pairs_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n21 The picture under the masks: per instance and channel the pixel count, the sums of v, v^2, x v and y v, the least and
+ *     the greatest value with their positions, and the histogram of the values of an image under packed masks
+ *     (csrc/mask_pixels.hip) -- on the layout of n5.  The statements of the rules are mnc_amd/pixels.py:pixel_stats_numpy and
+ *     histogram_numpy.  Every result is an integer; the floats a caller wants (mean, variance, weighted centroid, percentiles)
+ *     follow from them on the host.
+ *     Image: row-major [H][W][C] with H and W in [1, 32768], H * W <= 2^26 (n19's limits) and C in [1, 32], of dtype 0 uint8,
+ *     1 uint16, 2 int16 or 3 int32; an int32 image has every value in [-2^18, 2^18], so that every sum fits 64 signed bits
+ *     (sum v^2 < 2^62, sum x v < 2^59).  It is uploaded once per call, in its own dtype.
+ *     Pixels: those of an instance are its set bits inside its bounds that also lie inside [0, W) x [0, H).  Bounds may be
+ *     negative, unclipped or wholly outside the image; padding bits are not trusted.  x and y are image coordinates.
+ *     Every entry takes the set as mnc_mask_moments takes it.  n == 0 and sets without a row inside the image are answered on
+ *     the host (the values of the image are not looked at then).  MNC_ERR_INVALID, checked on the host before anything is
+ *     launched and with nothing written: everything mnc_mask_moments refuses about a set; H, W, H * W or C outside the limits;
+ *     an unknown dtype; a null pointer where one is needed.  MNC_ERR_INVALID after the device work, with nothing written: a
+ *     value of an int32 image outside the range -- a kernel ORs it into a flag word; the host does not walk the image.
+ *     One or two launches for the statistics (tiles of 4, 3 or 1 channels), one for the histogram, one more for an int32 image,
+ *     whatever the data.  The only atomics are 64-bit integer add, min and max and 32-bit integer LDS adds, which commute:
+ *     the same input gives the same bytes on every run.
+ *     (There are no forms that read a device-resident mnc_mask_records result: the PackedMasks methods fetch such a result
+ *     first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* dtype: 0 uint8, 1 uint16, 2 int16, 3 int32.  sums [n][C][4] = sum, sumsq, sum x v, sum y v;  extrema [n][C][6] = min, min_x, min_y, max, max_x, max_y */
+/* count [n].  On equal values the position that is lowest in (y, x) order is given.  An instance without a pixel inside the
+ * image has count 0, sums 0 and extrema (0, -1, -1, 0, -1, -1). */
+MNC_API int mnc_mask_pixel_stats(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
+                                 const void* image, int dtype, int H, int W, int C,
+                                 long long* count, long long* sums, int* extrema, int device_id);
+/* hist [n][C][bins], count [n] (the instance's pixels inside the image, counted or dropped).  A pixel of value v is counted in
+ * bin (v - lo) >> shift when that lies in [0, bins), and dropped otherwise.  Each workgroup counts a group of channels of at most
+ * 16384 cells in LDS and adds its non-zero cells to the table once.  MNC_ERR_INVALID as above, and: bins outside [1, 4096];
+ * shift outside [0, 31]; n * C * bins above 2^24. */
+MNC_API int mnc_mask_histogram(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n,
+                               const void* image, int dtype, int H, int W, int C, int lo, int shift, int bins,
+                               long long* count, long long* hist, int device_id);
+/* For tools/pixel_stats_bench.py.  on = 1: the following calls of the two entries above put a HIP event pair around their
+ * launches (without the copies of the set, of the image and of the results) and keep the last call's time in milliseconds;
+ * on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this call, -1.0 when there is
+ * none; switching on forgets it. */
+MNC_API int mnc_mask_pixels_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -343,6 +343,18 @@ def mask_oriented_boxes(pm):
     return pm.oriented_boxes(device_id=cfg.GPU_ID)
 
 
+def mask_pixel_stats(pm, image):
+    """The pixel count, sums, extremes and their positions of an integer image [H, W] or [H, W, C] under every instance of a
+    PackedMasks on the GPU (mnc_mask_pixel_stats, csrc/mask_pixels.hip) -> mnc_amd.pixels.PixelStats."""
+    return pm.pixel_stats(image, device_id=cfg.GPU_ID)
+
+
+def mask_histogram(pm, image, bins=256, lo=0, shift=0):
+    """The histogram of an integer image's values under every instance of a PackedMasks on the GPU (mnc_mask_histogram) ->
+    mnc_amd.pixels.MaskHistograms(hist int64 [n, C, bins], count, lo, shift, bins)."""
+    return pm.histogram(image, bins, lo, shift, device_id=cfg.GPU_ID)
+
+
 def mask_combine(a, b, op, window=None):
     """Two PackedMasks combined instance by instance on the GPU (mnc_mask_combine, csrc/mask_algebra.hip): op "and", "or",
     "xor", "minus", "copy" or "not", an optional window (x1, y1, x2, y2) -> a host PackedMasks with tight bounds."""

@@ -28,6 +28,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        transforms: flips, quarter turns, and nearest-neighbour affine maps (mnc_amd/warp.py, n18)
     PackedMasks.from_labels / .to_labels   the instances of an integer label map as a set, and the label map of a set
                                        (mnc_amd/labels.py, n19)
+    PackedMasks.pixel_stats / .histogram   what an image holds under every instance: count, sums, extremes with their positions,
+                                       and the histogram of the values (mnc_amd/pixels.py, n21)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -324,6 +326,21 @@ class PackedMasks(object):
         mnc_mask_oriented (hull and calipers in one call).  A device-resident result is fetched to the host first."""
         from . import shape
         return shape.oriented(self, device_id)
+
+    def pixel_stats(self, image, device_id=None):
+        """What an integer image [H, W] or [H, W, C] (uint8, uint16, int16, or int32 within +-2^18) holds under every instance ->
+        mnc_amd.pixels.PixelStats(count, sum, sumsq, sum_xv, sum_yv, min, max, argmin, argmax) per instance and channel, with
+        .mean(), .var(), .std() and .weighted_centroid() on the host, by the rule of mnc_amd.pixels.pixel_stats_numpy
+        (include/mnc_hip.h n21, csrc/mask_pixels.hip) on the GPU.  A device-resident result is fetched to the host first."""
+        from . import pixels
+        return pixels.pixel_stats(self, image, device_id)
+
+    def histogram(self, image, bins=256, lo=0, shift=0, device_id=None):
+        """The histogram of such an image's values under every instance, bin (v - lo) >> shift -> mnc_amd.pixels.MaskHistograms(hist
+        int64 [n, C, bins], count, lo, shift, bins) with .percentile(q), .median() and .mode() on the host, by the rule of
+        mnc_amd.pixels.histogram_numpy through mnc_mask_histogram.  A device-resident result is fetched to the host first."""
+        from . import pixels
+        return pixels.histogram(self, image, bins, lo, shift, device_id)
 
     def combine(self, other, op, window=None, device_id=None):
         """These masks combined with `other` instance by instance (len(other) == len(self), or 1: that instance against every

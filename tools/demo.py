@@ -4,7 +4,7 @@ build the net, warm up twice on a grey image, then per image: im_detect (timed "
 optional visualisation.
 
     python tools/demo.py [--gpu 0] [--def test.prototxt] [--net weights.npz] [--images a.jpg b.jpg ...] [--no-vis] [--device-vis]
-                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes]]
+                         [--save-masks DIR] [--save-coco FILE] [--save-annotations FILE [--polygon-epsilon E] [--oriented-boxes] [--pixel-stats]]
                          [--min-component-area A [--largest-component]] [--smooth-radius R] [--exclusive]
                          [--flip-tta [--tta-nms T]] [--save-panoptic DIR]
 
@@ -37,7 +37,10 @@ default; without the flag the output is what it was.  --save-panoptic DIR writes
 other writers would write -- after --smooth-radius, --exclusive and the component selection -- as DIR/<name>.png in the COCO
 panoptic encoding (PackedMasks.to_labels, csrc/mask_labels.hip; with --cpu mnc_amd.labels.to_labels_numpy; id = index + 1 through
 mnc_amd.labels.id_to_rgb, Pillow writes the file), and one DIR/panoptic.json with every image's segments_info; without the flag
-every output is what it was."""
+every output is what it was.  --pixel-stats adds to every annotation of --save-annotations "mean_color": [R, G, B] and "std_color",
+the mean and the standard deviation of the image's colours under the written mask (PixelStats.mean / .std of
+PackedMasks.pixel_stats, csrc/mask_pixels.hip; with --cpu mnc_amd.pixels.pixel_stats_numpy; both null for a mask without a pixel);
+without the flag the file is byte for byte what it was."""
 import argparse
 import os
 import time
@@ -84,6 +87,9 @@ def parse_args(argv=None):
     p.add_argument("--oriented-boxes", dest="oriented_boxes", action="store_true",
                    help="add \"rbox\": [cx, cy, w, h, angle in degrees] (the rectangle of least area) and \"solidity\" (pixels over "
                         "convex hull area) to every annotation --save-annotations writes, after the smoothing and the selection")
+    p.add_argument("--pixel-stats", dest="pixel_stats", action="store_true",
+                   help="add \"mean_color\": [R, G, B] and \"std_color\" (the image's colours under the written mask) to every "
+                        "annotation --save-annotations writes")
     p.add_argument("--min-component-area", dest="min_component_area", default=0, type=int, metavar="A",
                    help="drop the 8-connected components of fewer than A pixels from the masks --save-masks / --save-coco / "
                         "--save-annotations write")
@@ -280,14 +286,16 @@ def _coco_results(image_id, im_shape, packed, cpu=False):
     return out
 
 
-def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0, oriented=False):
+def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0, oriented=False, image=None):
     """-> COCO annotation entries of one image's PackedMasks: segmentation = the outer loops of the 8-connected outline as polygons
     (on the GPU, csrc/mask_contours.hip; cpu=True: the numpy statement), bbox = [x, y, w, h] of the polygons' extent (the tight box
     of the mask's pixels; with epsilon > 0 the extent of the polygons written), area = the mask's pixel count, iscrowd 0.  An
     instance without a set pixel has no polygons.  epsilon > 0 simplifies the loops to that many pixels (csrc/contour_simplify.hip;
     cpu=True: simplify_numpy).  oriented: "rbox" = [cx, cy, w, h, angle] of the rectangle of least area (null for an instance
     without a set pixel) and "solidity" = area over convex hull area as well (csrc/mask_shape.hip; cpu=True: the numpy statements
-    of mnc_amd.shape).  A device-resident result is fetched first."""
+    of mnc_amd.shape).  image, the uint8 BGR image [H, W, 3]: "mean_color" = [R, G, B] and "std_color", the mean and the standard
+    deviation of its colours under the mask (csrc/mask_pixels.hip; cpu=True: pixel_stats_numpy), both null for an instance
+    without a pixel.  A device-resident result is fetched first."""
     from mnc_amd import contours
     packed = packed.fetch()
     c = contours.contours_numpy(packed, 8) if cpu else packed.contours(8)
@@ -310,6 +318,13 @@ def _coco_annotations(image_id, packed, first_id=1, cpu=False, epsilon=0.0, orie
         for i, solidity in enumerate(hulls.solidity(packed.areas)):
             out[i]["rbox"] = [float(v) for v in rbox[i]] if hulls.area2[i] else None
             out[i]["solidity"] = float(solidity)
+    if image is not None:
+        from mnc_amd import pixels
+        stats = pixels.pixel_stats_numpy(packed, image) if cpu else packed.pixel_stats(image)
+        mean, std = stats.mean()[:, ::-1], stats.std()[:, ::-1]               # (BGR -> RGB)
+        for i in range(len(packed)):
+            out[i]["mean_color"] = [float(v) for v in mean[i]] if stats.count[i] else None
+            out[i]["std_color"] = [float(v) for v in std[i]] if stats.count[i] else None
     return out
 
 
@@ -410,7 +425,7 @@ def main(argv=None):
                 image_entries.append({"id": name, "file_name": os.path.basename(path) if path else name, "height": int(im.shape[0]),
                                       "width": int(im.shape[1])})
                 annotations.extend(_coco_annotations(name, packed, len(annotations) + 1, args.cpu_mode, args.polygon_epsilon,
-                                                     args.oriented_boxes))
+                                                     args.oriented_boxes, im if args.pixel_stats else None))
             if args.save_panoptic:
                 panoptic.append(_save_panoptic(args.save_panoptic, name, im.shape, packed, args.cpu_mode))
                 print("wrote %s.png (%d segments)" % (os.path.join(args.save_panoptic, name), len(panoptic[-1]["segments_info"])))
