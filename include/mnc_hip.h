@@ -978,6 +978,71 @@ MNC_API int mnc_mask_histogram(const int* bounds, const long long* offsets, cons
 MNC_API int mnc_mask_pixels_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n22 The distance between outlines: the surfaces of packed masks and, for pairs of instances of two sets, the squared
+ *     distances from the surface pixels of the one to the surface of the other -- what the Hausdorff distance, its 95th
+ *     percentile, the average symmetric surface distance, the boundary F-measure (the F of DAVIS's J&F) and the normalised
+ *     surface Dice are made of (csrc/mask_surface.hip) -- on the layout of n5.  The statements of the rules are
+ *     mnc_amd/surface.py:surface_numpy, surface_stats_numpy and surface_distances_numpy.
+ *     All arithmetic is integer and all rules are frame-free, by the conventions of n15 and n17: a mask M is a set of
+ *     lattice pixels that is empty outside its bounds, bounds may be negative or unclipped, padding bits are not trusted.
+ *     Surface: S(M) = the pixels of M with at least one of their four edge neighbours outside M = M & ~erode(M, R2 = 1).
+ *     Distances: for a pair (i, j) of instances of the sets A and B and a direction -- 0: A_i -> B_j, 1: B_j -> A_i -- and every
+ *     pixel p of S(src), d2(p) = min over q in S(dst) of |p - q|^2 in image coordinates.  pairs [P][2] int = (i, j), in any
+ *     order, repeats allowed; slot 2 k + d is pair k in direction d.
+ *     The surface words are made by one lane per word from its four neighbours and kept in a scratch plane; every instance
+ *     some pair measures against gets, per pixel of its bounds, the distance along the row to its nearest surface pixel
+ *     (uint16, 0xffff for a row without one: n15's first pass on the surface words); a lane with a source surface pixel clamps
+ *     its x into the destination's columns, where dx = |x - clamp(x)| + that distance, and walks the destination's rows
+ *     outward from clamp(y) while dy^2 is below the best so far.  The workgroups are listed on the host from the bounds, so the
+ *     launch count is fixed whatever the data.  Integer add and max atomics only: the same input gives the same bytes on
+ *     every run.
+ *     Every entry takes a set as mnc_mask_rle takes it: bounds [n][4] int, offsets [n], bits, bytes = the bytes bits holds.
+ *     n == 0, m == 0, P == 0 and sets without a single row are answered on the host.  MNC_ERR_INVALID, checked on the host
+ *     before anything is launched and with nothing written, for every entry: everything mnc_mask_boundary refuses about
+ *     either set (n outside [0, 2048], |coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is negative or
+ *     not a multiple of 8, rows that reach past bytes); P outside [0, 65536]; a pair index out of range; T outside [0, 8]; a
+ *     tau2 outside [0, 2^31); a hull of the bounds of all instances with rows of both sets that spans 32768 or more pixels in
+ *     either axis (below it every d2 < 2^31 and every sum fits 64 signed bits); more than 2^27 pixels of rows in the call
+ *     (n15's limit); a null pointer where one is needed.  (There are no forms that read a device-resident mnc_mask_records
+ *     result: the PackedMasks methods fetch such a result first.)
+ * ------------------------------------------------------------------------------------------------------------- */
+/* The surfaces as a set.  The result has the layout of n5 as mnc_mask_boundary writes it and the input's bounds (an instance
+ * without rows keeps them and gets no rows): out_offsets [n] are multiples of 8, in order without gaps; out_areas [n] are the
+ * surface pixel counts; padding bits are 0.  out_bounds, out_offsets and *bits_bytes follow from the bounds alone and are
+ * computed on the host: with out_bits == NULL the call returns them and launches nothing (out_areas may be NULL then);
+ * bits_cap < *bits_bytes is MNC_ERR_INVALID with the three set and nothing else written.  Bytes past *bits_bytes are never
+ * written.  One launch. */
+MNC_API int mnc_mask_surface(const int* bounds, const long long* offsets, const void* bits, size_t bytes, int n, int* out_bounds,
+                             long long* out_offsets, long long* out_areas, void* out_bits, size_t bits_cap, size_t* bits_bytes,
+                             int device_id);
+/* The distances reduced.  Outputs, every one indexed by slot: count [P][2] = |S(src)|; max_d2 [P][2] the greatest d2;
+ * argmax [P][2][2] the (x, y) of the source pixel that attains it, the lowest (y, x) on ties; sum_d2 [P][2] the sum of d2;
+ * within [P][2][T] the source pixels with d2 <= tau2[t].  Where S(src) or S(dst) is empty: max_d2 -1, argmax (-1, -1), sum_d2 0,
+ * within 0, count as it is.  The kernel reduces the sum, the counts and the 64-bit key (d2 << 32) | (0xffffffff - raster index
+ * in the source's bounds) by shuffles, then LDS, then one 64-bit atomic add resp. max per workgroup and figure.  Three launches,
+ * no read-back between them. */
+MNC_API int mnc_mask_surface_stats(const int* a_bounds, const long long* a_offsets, const void* a_bits, size_t a_bytes, int n,
+                                   const int* b_bounds, const long long* b_offsets, const void* b_bits, size_t b_bytes, int m,
+                                   const int* pairs, int P, const int* tau2, int T, long long* count, long long* max_d2,
+                                   int* argmax, long long* sum_d2, long long* within, int device_id);
+/* The distances themselves.  Outputs: ptr [2 P + 1] (ptr[0] = 0; slot s owns the entries ptr[s] .. ptr[s + 1] - 1: the d2 of
+ * the source's surface pixels in raster (y, x) order), *total = ptr[2 P], d2 [*total]; a slot whose destination has no surface
+ * pixel holds 0xffffffff.  The protocol is mnc_mask_distance's: d2 == NULL gives ptr and *total only and launches nothing more
+ * than the surfaces and their counts need; otherwise cap is the room of d2 in entries, and cap < *total is MNC_ERR_INVALID with
+ * ptr and *total set and nothing else written.  Entries past *total are never written.  One read-back, of the instances'
+ * surface pixel counts, from which the host makes ptr; a pixel's place is ptr[s] plus its rank, the prefix sum of the surface
+ * words' popcounts before its word plus the popcount below its bit.  MNC_ERR_INVALID after that read-back, with nothing
+ * written: more than 2^28 entries. */
+MNC_API int mnc_mask_surface_dist(const int* a_bounds, const long long* a_offsets, const void* a_bits, size_t a_bytes, int n,
+                                  const int* b_bounds, const long long* b_offsets, const void* b_bits, size_t b_bytes, int m,
+                                  const int* pairs, int P, long long* ptr, unsigned* d2, size_t cap, size_t* total, int device_id);
+/* For tools/surface_dist_bench.py.  on = 1: the following calls of the three entries above put HIP event pairs around their
+ * launches (without the copies of the sets and of the results, and without the raw entry's read-back) and keep the last call's
+ * summed time in milliseconds; on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this
+ * call, -1.0 when there is none; switching on forgets it. */
+MNC_API int mnc_mask_surface_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libmnc_hip.so")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 ARCH = "gfx950"
 # (mcg_maskdb.hip is not listed: its only float64 product, dx * ifx, is followed by floor -- there is nothing to contract it with;
-# mask_rle.hip, mask_boundary.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip, mask_labels.hip, mask_pixels.hip, mask_tight.hip and scan.hip are not listed: they have no floating-point arithmetic at all; mask_poly.hip is: the doubles of rleFrPoly's walk keep
+# mask_rle.hip, mask_boundary.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip, mask_labels.hip, mask_pixels.hip, mask_surface.hip, mask_tight.hip and scan.hip are not listed: they have no floating-point arithmetic at all; mask_poly.hip is: the doubles of rleFrPoly's walk keep
 # their published order, on the host side of the file (the rounding of the vertices) as in its kernels)
 NO_CONTRACT = {"nms.hip", "mv.hip", "mv_image.hip", "sds_eval.hip", "render.hip", "inst_masks.hip", "mask_overlaps.hip", "mask_match.hip", "mask_poly.hip", "coco_accum.hip", "bbox.hip", "roi.hip", "proposal.hip", "prep.hip"}
 # conv_wino4.hip: the transform arithmetic runs beside MFMAs as one-lane fma / add; hipcc's SLP pass would pair scalar operations of

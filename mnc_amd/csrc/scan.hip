@@ -1,5 +1,6 @@
 // The two-level exclusive scan of scan.h for gfx950: one workgroup per tile of 1024 entries, then one workgroup over the tiles'
-// sums.  Integer sums only.  mask_components.hip, mask_contours.hip and contour_simplify.hip launch it.
+// sums.  Integer sums only.  mask_components.hip, mask_contours.hip, contour_simplify.hip
+// and mask_surface.hip, among others, launch it.
 #include "scan.h"
 
 namespace mnc {

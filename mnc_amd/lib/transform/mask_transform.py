@@ -355,6 +355,24 @@ def mask_histogram(pm, image, bins=256, lo=0, shift=0):
     return pm.histogram(image, bins, lo, shift, device_id=cfg.GPU_ID)
 
 
+def mask_surface(pm):
+    """The surfaces of a PackedMasks -- the pixels with an edge neighbour outside the mask -- on the GPU (mnc_mask_surface,
+    csrc/mask_surface.hip) -> a host PackedMasks in the input's frames."""
+    return pm.surface(device_id=cfg.GPU_ID)
+
+
+def mask_surface_stats(a, b, pairs=None, tau2=()):
+    """The distances between the surfaces of pairs (i, j) of instances of two PackedMasks, reduced, on the GPU
+    (mnc_mask_surface_stats) -> mnc_amd.surface.SurfaceStats with .hausdorff(), .boundary_f(t) and .nsd(t)."""
+    return a.surface_stats(b, pairs, tau2, device_id=cfg.GPU_ID)
+
+
+def mask_surface_distances(a, b, pairs=None):
+    """Those distances themselves on the GPU (mnc_mask_surface_dist) -> mnc_amd.surface.SurfaceDistances with .hd95() and
+    .assd()."""
+    return a.surface_distances(b, pairs, device_id=cfg.GPU_ID)
+
+
 def mask_combine(a, b, op, window=None):
     """Two PackedMasks combined instance by instance on the GPU (mnc_mask_combine, csrc/mask_algebra.hip): op "and", "or",
     "xor", "minus", "copy" or "not", an optional window (x1, y1, x2, y2) -> a host PackedMasks with tight bounds."""

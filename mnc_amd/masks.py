@@ -30,6 +30,8 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        (mnc_amd/labels.py, n19)
     PackedMasks.pixel_stats / .histogram   what an image holds under every instance: count, sums, extremes with their positions,
                                        and the histogram of the values (mnc_amd/pixels.py, n21)
+    PackedMasks.surface / .surface_stats / .surface_distances   the surfaces, and the distances between the surfaces of pairs of
+                                       instances of two sets: Hausdorff, HD95, ASSD, boundary F (mnc_amd/surface.py, n22)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -341,6 +343,32 @@ class PackedMasks(object):
         mnc_amd.pixels.histogram_numpy through mnc_mask_histogram.  A device-resident result is fetched to the host first."""
         from . import pixels
         return pixels.histogram(self, image, bins, lo, shift, device_id)
+
+    def surface(self, device_id=None):
+        """The surfaces of these masks -- the pixels with one of their four edge neighbours outside the mask, M & ~erode(M, r2=1)
+        -- as a host PackedMasks in this one's frames: its bounds, areas the surface pixel counts, classes and scores carried
+        over, by the rule of mnc_amd.surface.surface_numpy (include/mnc_hip.h n22, csrc/mask_surface.hip) on the GPU.  A
+        device-resident result is fetched to the host first."""
+        from . import surface
+        return surface.surface(self, device_id)
+
+    def surface_stats(self, other, pairs=None, tau2=(), device_id=None):
+        """The squared distances from the surface pixels of instance i of these masks to the surface of instance j of `other` and
+        back, reduced, for the pairs (i, j) of `pairs` (int [P, 2]; None: all pairs in row-major order) -> mnc_amd.surface.
+        SurfaceStats(count, max_d2, argmax, sum_d2, within, tau2), every field [P, 2] over the two directions, with .hausdorff(),
+        .precision(t), .recall(t), .boundary_f(t) and .nsd(t) on the host, by the rule of mnc_amd.surface.surface_stats_numpy
+        through mnc_mask_surface_stats.  tau2: up to 8 squared tolerances (surface.tolerance_sq gives DAVIS's).  Device-resident
+        results are fetched to the host first."""
+        from . import surface
+        return surface.surface_stats(self, other, pairs, tau2, device_id)
+
+    def surface_distances(self, other, pairs=None, device_id=None):
+        """Those squared distances themselves -> mnc_amd.surface.SurfaceDistances(ptr, d2): pair k in direction d owns d2[ptr[2 k +
+        d]:ptr[2 k + d + 1]], in raster order of the source's surface, with .slot(k, d), .percentile(q), .hd95() and .assd() on the
+        host, by the rule of mnc_amd.surface.surface_distances_numpy through mnc_mask_surface_dist.  Device-resident results are
+        fetched to the host first."""
+        from . import surface
+        return surface.surface_distances(self, other, pairs, device_id)
 
     def combine(self, other, op, window=None, device_id=None):
         """These masks combined with `other` instance by instance (len(other) == len(self), or 1: that instance against every
