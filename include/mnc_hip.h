@@ -1043,6 +1043,47 @@ MNC_API int mnc_mask_surface_dist(const int* a_bounds, const long long* a_offset
 MNC_API int mnc_mask_surface_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n23 Training targets on packed ground-truth masks: the two per-RoI loops of the reference's training step
+ *     (csrc/mask_targets.hip) -- the mask regression target of a box (lib/transform/mask_transform.py:49-80 intersect_mask,
+ *     called per foreground RoI by ProposalTargetLayer and StageBridgeLayer) and the overlap of a predicted mask with its
+ *     ground truth (lib/pylayer/mask_layer.py:68-83) -- on the layout of n5.  The statements of the rules are
+ *     mnc_amd/targets.py:mask_targets_numpy and mask_pred_overlaps_numpy.
+ *     Both entries take the ground truth as mnc_mask_overlaps takes a set: bounds [G][4] int (the rounded, unscaled
+ *     ground-truth boxes), offsets [G], areas [G], bits, bytes = the bytes bits holds.  Padding bits are not trusted.  Each
+ *     is one launch and one read-back; the counters are integer atomics: two calls give the same bytes.
+ *     MNC_ERR_INVALID, checked on the host before anything is launched and with nothing written, for both: everything
+ *     mnc_mask_overlaps refuses about a set (|coordinate| >= 2^24, more than 2^26 pixels in one bound, an offset that is
+ *     negative or not a multiple of 8, rows that reach past bytes); K outside [0, 65536]; mask_size outside [1, 32]; a null
+ *     pointer where one is needed.  K == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* ex_boxes [K][4] int (x1, y1, x2, y2, inclusive), gt_index [K] -> out [K][mask_size][mask_size] bytes 0 / 1.  Row k, with e
+ * its box, g the bounds of instance gt_index[k] and M that instance's mask: all zeros when e and g do not intersect (an
+ * instance without rows intersects nothing); else (cv2.resize(C, (S, S)) >= (float)thresh), C the float32 canvas of e's size
+ * that is M on e & g and 0 elsewhere, INTER_LINEAR as in n5 (source coordinate in float64 rounded to float32, horizontal pass
+ * then vertical in float32).  The canvas is not made: one lane per output cell reads four bits.
+ * MNC_ERR_INVALID also for: a box with x2 < x1 or y2 < y1; a coordinate with |c| >= 2^24; a box of more than 2^26 pixels;
+ * gt_index[k] outside [0, G); a NaN thresh. */
+MNC_API int mnc_mask_targets(const int* gt_bounds, const long long* gt_offsets, const long long* gt_areas, const void* gt_bits,
+                             size_t gt_bytes, int G, const int* ex_boxes, const int* gt_index, int K, int mask_size, double thresh,
+                             unsigned char* out, int device_id);
+/* boxes [K][4] float64, preds [K][mask_size][mask_size] float32, gt_index [K] (-1: a background row, skipped) -> inter [K],
+ * area_pred [K].  The mask of row k is mnc_instance_masks's with clip = 0: the box rounded half to even and not clipped, the
+ * prediction resized to it and binarised with >= (float)thresh; area_pred[k] = its set pixels, inter[k] = those also set in
+ * instance gt_index[k] (what mnc_mask_overlaps counts for that pair).  A row with gt_index -1 gets 0 and 0.  No mask bit is
+ * written anywhere: the ballots are counted as they are made.
+ * MNC_ERR_INVALID also for what mnc_instance_masks refuses with clip = 0, in any row (a rounded coordinate with |c| >= 2^24,
+ * a box that is empty once rounded, more than 2^26 pixels), and gt_index[k] outside [-1, G). */
+MNC_API int mnc_mask_pred_overlaps(const int* gt_bounds, const long long* gt_offsets, const long long* gt_areas,
+                                   const void* gt_bits, size_t gt_bytes, int G, const double* boxes, const float* preds,
+                                   const int* gt_index, int K, int mask_size, double thresh, long long* inter,
+                                   long long* area_pred, int device_id);
+/* For tools/train_targets_bench.py.  on = 1: the following calls of the two entries above put a HIP event pair around their
+ * launch (and the clearing of the counters; without the copies of the set, of the rows and of the results) and keep the last
+ * call's time in milliseconds; on = 0: they do not (the default).  *last_ms (may be NULL) receives the figure kept before this
+ * call, -1.0 when there is none; switching on forgets it. */
+MNC_API int mnc_mask_targets_timing(int on, double* last_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

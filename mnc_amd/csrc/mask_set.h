@@ -1,5 +1,5 @@
 // One set of packed instance masks (include/mnc_hip.h n5), as the mask files share it: inst_masks.hip, mask_overlaps.hip, mask_rle.hip,
-// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip, mask_labels.hip, mask_pixels.hip, mask_surface.hip and, through mask_tight.h, mask_tight.hip.  Internal to libmnc_hip.so; nothing else includes it.
+// mask_match.hip, mask_boundary.hip, mask_poly.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip, mask_labels.hip, mask_pixels.hip, mask_surface.hip, mask_targets.hip and, through mask_tight.h, mask_tight.hip.  Internal to libmnc_hip.so; nothing else includes it.
 #pragma once
 #include <vector>
 

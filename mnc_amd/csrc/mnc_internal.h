@@ -230,7 +230,7 @@ struct CallBuf {
 
 // Scope of a host-array entry point (_nms, _mv, mnc_mask_voting*, mnc_sds_best_overlap, mnc_mcg_maskdb, mnc_render_instances,
 // mnc_instance_masks, mnc_mask_overlaps, mnc_mask_nms, mnc_mask_rle, mnc_mask_from_rle, mnc_mask_match, mnc_mask_match_boundary,
-// mnc_mask_boundary, mnc_mask_from_polygons, mnc_coco_accumulate, mnc_mask_components / _select / _fill_holes / _split, mnc_mask_contours, mnc_contours_simplify, mnc_mask_distance / _inscribed / _morph, mnc_mask_moments / _hull / _oriented, mnc_mask_combine / _merge / _layer, mnc_mask_isometry, mnc_mask_warp, mnc_label_table / _masks, mnc_mask_to_labels, mnc_mask_pixel_stats, mnc_mask_histogram, mnc_mask_surface / _surface_stats / _surface_dist): the device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
+// mnc_mask_boundary, mnc_mask_from_polygons, mnc_coco_accumulate, mnc_mask_components / _select / _fill_holes / _split, mnc_mask_contours, mnc_contours_simplify, mnc_mask_distance / _inscribed / _morph, mnc_mask_moments / _hull / _oriented, mnc_mask_combine / _merge / _layer, mnc_mask_isometry, mnc_mask_warp, mnc_label_table / _masks, mnc_mask_to_labels, mnc_mask_pixel_stats, mnc_mask_histogram, mnc_mask_surface / _surface_stats / _surface_dist, mnc_mask_targets, mnc_mask_pred_overlaps): the device's stream and growable workspace (the reference cudaMalloc/cudaFree's its scratch on every call: nms_kernel.cu:99-143,
 // mv_kernel.cu:250-347) with the workspace's mutex HELD until the scope ends -- taken before the buffer may be re-allocated:
 // ctypes releases the GIL, so two host threads may be inside such entry points on one device.
 struct HostScope {
@@ -248,7 +248,7 @@ struct HostScope {
   hipError_t sync() const { return hipStreamSynchronize(stream); }
 };
 
-// The switch and the kept figure behind one mnc_*_timing entry (boundary, polygons, accumulate, components, contours, simplify, distance, shape, algebra, warp, labels, pixels, surface): off and -1.0 until
+// The switch and the kept figure behind one mnc_*_timing entry (boundary, polygons, accumulate, components, contours, simplify, distance, shape, algebra, warp, labels, pixels, surface, targets): off and -1.0 until
 // the entry is called.
 struct CallTimer {
   std::atomic<int> on{0};

@@ -1,7 +1,7 @@
 """Global configuration of the MNC inference path -- same surface as the reference's `mnc_config`
 (lib/mnc_config.py:8-206): a mutable attribute-dict `cfg` plus `cfg_from_file(yaml)`; `easydict` is not required.
-Every key of the reference is declared (so that its experiment yml files merge); only the TEST keys and a handful of TRAIN
-keys are read by the inference path (demo.py:59 passes cfg.TRAIN.MAX_SIZE to prep_im_for_blob)."""
+Every key of the reference is declared (so that its experiment yml files merge); the inference path reads the TEST keys and a
+handful of TRAIN keys (demo.py:59 passes cfg.TRAIN.MAX_SIZE to prep_im_for_blob), the target layers read the TRAIN sampling keys."""
 import os
 
 import numpy as np
@@ -47,10 +47,12 @@ cfg.MASK_SIZE = 21                          # mnc_config.py:28
 # experiment .yml.  Empty = oracle/SPEC.md (PARITY UNPINNED either way; SPEC.md section 6 lists the alternatives).
 cfg.LAYER_CONVENTIONS = AttrDict()
 
-# TRAIN: no training code exists in this package, but the reference's experiment files (experiments/cfgs/VGG16/*.yml) set
-# TRAIN keys next to the TEST ones and cfg_from_file rejects unknown keys (mnc_config.py:174-176) -- so every key of
-# mnc_config.py:31-108 is declared, with the reference's default.  Test-time readers: TRAIN.MAX_SIZE (demo.py:59,
-# TesterWrapper.py:271), TRAIN.MIX_INDEX, TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED.
+# TRAIN: every key of mnc_config.py:31-108 is declared, with the reference's default -- its experiment files
+# (experiments/cfgs/VGG16/*.yml) set TRAIN keys next to the TEST ones and cfg_from_file rejects unknown keys (mnc_config.py:174-176).
+# Test-time readers: TRAIN.MAX_SIZE (demo.py:59, TesterWrapper.py:271), TRAIN.MIX_INDEX, TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED.
+# The forward passes of the target layers (pylayer/proposal_target_layer.py, anchor_target_layer.py, the TRAIN phase of
+# mask_layer.py and stage_bridge_layer.py; mnc_amd/targets.py) read the sampling keys: BATCH_SIZE, FG_* / BG_*, BBOX_*, RPN_*,
+# MIX_INDEX, FG_SEG_THRESH.  Backward passes, the solver and the data layers are not in this package.
 cfg.TRAIN = AttrDict(
     IMS_PER_BATCH=1, BATCH_SIZE=64, ASPECT_GROUPING=True, USE_FLIPPED=True, SCALES=(600,), MAX_SIZE=1000,
     SNAPSHOT_ITERS=5000, SNAPSHOT_INFIX='',

@@ -79,6 +79,23 @@ def mask_overlap(box1, box2, mask1, mask2):
     return float(inter) / float(union)
 
 
+def intersect_mask(ex_box, gt_box, gt_mask):
+    """The mask regression target of one box (mask_transform.py:49-80): gt_mask, the ground-truth mask inside the integer box
+    gt_box, pasted where it meets ex_box on a float32 canvas of ex_box's size, resized to cfg.MASK_SIZE x cfg.MASK_SIZE and
+    binarised with >= cfg.BINARIZE_THRESH -> bool [S, S]; zeros (21 x 21 in the reference) when the boxes do not meet.  A thin
+    host statement: mnc_amd.targets.mask_targets does all rows of a layer in one device call."""
+    from utils.blob import resize_to
+    x1, y1 = max(ex_box[0], gt_box[0]), max(ex_box[1], gt_box[1])
+    x2, y2 = min(ex_box[2], gt_box[2]), min(ex_box[3], gt_box[3])
+    if x1 > x2 or y1 > y2:
+        return np.zeros((cfg.MASK_SIZE, cfg.MASK_SIZE), dtype=bool)
+    w, h = x2 - x1 + 1, y2 - y1 + 1
+    ey, ex, gy, gx = y1 - ex_box[1], x1 - ex_box[0], y1 - gt_box[1], x1 - gt_box[0]
+    canvas = np.zeros((ex_box[3] - ex_box[1] + 1, ex_box[2] - ex_box[0] + 1))
+    canvas[ey: ey + h, ex: ex + w] = gt_mask[gy: gy + h, gx: gx + w]
+    return resize_to(canvas.astype(np.float32), cfg.MASK_SIZE, cfg.MASK_SIZE) >= cfg.BINARIZE_THRESH
+
+
 def _fused_mask_voting(masks, boxes, scores, num_classes, max_per_image, im_width, im_height):
     """The whole of gpu_mask_voting in one C-ABI call (mnc_mask_voting): per-class score order, batched per-class NMS,
     candidate sets and the fused voting kernels, all on the device with no Python between the steps.  The per-class

@@ -32,6 +32,10 @@ consumer of a voted instance makes first -- round the box, resize the S x S mask
                                        and the histogram of the values (mnc_amd/pixels.py, n21)
     PackedMasks.surface / .surface_stats / .surface_distances   the surfaces, and the distances between the surfaces of pairs of
                                        instances of two sets: Hausdorff, HD95, ASSD, boundary F (mnc_amd/surface.py, n22)
+    PackedMasks.targets(ex_boxes, gt_index)   the S x S mask regression targets of boxes against these ground-truth masks: the
+                                       reference's intersect_mask for all rows at once (mnc_amd/targets.py, n23)
+    PackedMasks.pred_overlaps(boxes, preds, gt_index)   the overlap of predicted S x S masks, resized to their boxes, with these
+                                       ground-truth masks: what MaskLayer's TRAIN phase counts (mnc_amd/targets.py, n23)
 
 Bit layout: instance i is h rows of ceil(w / 64) little-endian 64-bit words at byte offsets[i]; bit dx % 64 of word dx / 64 is
 pixel dx, padding bits are 0 -- utils.voc_eval.pack_sds_gt's bit order with the row stride rounded up to 8 bytes.  There is no
@@ -369,6 +373,24 @@ class PackedMasks(object):
         fetched to the host first."""
         from . import surface
         return surface.surface_distances(self, other, pairs, device_id)
+
+    def targets(self, ex_boxes, gt_index, S=None, thresh=None, device_id=None):
+        """The mask regression targets of the boxes ex_boxes int [K, 4] (x1, y1, x2, y2 inclusive) against these ground-truth
+        masks, row k against instance gt_index[k] -> uint8 [K, S, S] of 0 / 1: the ground truth pasted on a canvas of the box's
+        size, resized to S x S (None: cfg.MASK_SIZE) by cv2's rule and binarised with >= float32(thresh) (None:
+        cfg.BINARIZE_THRESH), zeros where box and bounds do not meet -- the reference's intersect_mask, by the rule of
+        mnc_amd.targets.mask_targets_numpy (include/mnc_hip.h n23, csrc/mask_targets.hip) on the GPU.  A device-resident result is
+        fetched to the host first."""
+        from . import targets
+        return targets.mask_targets(self, ex_boxes, gt_index, S, thresh, device_id)
+
+    def pred_overlaps(self, boxes, preds, gt_index, thresh=None, device_id=None):
+        """The overlap of the predictions preds float32 [K, S, S], each resized to its box of boxes float64 [K, 4] (rounded half to
+        even, not clipped) and binarised, with instance gt_index[k] of these ground-truth masks (-1: a background row, zeros) ->
+        (inter int64 [K], area_pred int64 [K], iou float64 [K]), by the rule of mnc_amd.targets.mask_pred_overlaps_numpy through
+        mnc_mask_pred_overlaps: no mask bit leaves the device.  A device-resident result is fetched to the host first."""
+        from . import targets
+        return targets.mask_pred_overlaps(self, boxes, preds, gt_index, thresh, device_id)
 
     def combine(self, other, op, window=None, device_id=None):
         """These masks combined with `other` instance by instance (len(other) == len(self), or 1: that instance against every

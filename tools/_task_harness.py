@@ -1,5 +1,5 @@
 """What the bench tools of the packed-mask tasks share (mask_overlap / mask_rle / mask_match / mask_boundary / mask_components / mask_contours /
-contours_simplify / mask_algebra / mask_warp / mask_labels / pixel_stats / surface_dist _bench.py; mask_poly_bench.py and coco_accum_bench.py take the timers and emit alone): the timers, the instances of the two
+contours_simplify / mask_algebra / mask_warp / mask_labels / pixel_stats / surface_dist _bench.py; mask_poly_bench.py, coco_accum_bench.py and train_targets_bench.py take the timers and emit alone): the timers, the instances of the two
 synthetic images, the output line."""
 import argparse
 import json
