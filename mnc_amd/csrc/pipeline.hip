@@ -192,7 +192,7 @@ static inline int fc_math(const mnc_net_config& c) { return c.math == 3 ? 2 : c.
 
 // One InnerProduct's weights: [N][K] in Caffe order; geo = (C, PH, PW) when the bottom is a per-RoI feature (the engine's
 // rows are (h, w, c): permute the columns once), then the math mode's packed form when the product is large enough
-// (engine.py: 2*M*N*K >= 2e9 with M = post_nms_topn; f16 needs K % 64 == 0, bf16x3 K % 32 == 0).
+// (engine.py, _fc_kind: 2*M*N*K >= 2e9 with M = post_nms_topn; f16 needs K % 64 == 0, bf16x3 K % 32 == 0).
 int prepare_fc(mnc_net* n, const char* layer, int N, int K, int C, int PH, int PW, mnc_net::Fc* fc) {
   const HostBlob *w, *b;
   NET_TRY(need(n, layer, 0, (size_t)N * K, &w));
@@ -210,7 +210,7 @@ int prepare_fc(mnc_net* n, const char* layer, int N, int K, int C, int PH, int P
   }
   const bool big = 2.0 * n->cfg.post_nms_topn * (double)N * (double)K >= 2.0e9;
   // mixed: an InnerProduct over more than 50 000 inputs (fc6_maskest: 100 352) stays split-bf16 -- fp16 operands leave the sigmoid
-  // masks behind it at 1.0-1.2e-3, the only head output of the f16 mode on the wrong side of the bar (engine.py: the same rule)
+  // masks behind it at 1.0-1.2e-3, the only head output of the f16 mode on the wrong side of the bar (engine.py, _fc_kind: the same rule)
   int fm = (n->cfg.math == 3 && K > 50000) ? 1 : fc_math(n->cfg);
   if (fm == 5) {
     // f8: e4m3 codes + one exponent per row when the product is large and K holds whole 128-value stages; otherwise the f16 rules

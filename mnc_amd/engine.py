@@ -18,7 +18,7 @@ There is no CPU execution path: constructing a Net without a working libmnc_hip.
 import ctypes
 import importlib
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from collections.abc import Mapping
 
 import numpy as np
@@ -60,6 +60,67 @@ def winograd_mode(value):
 
 # bf16x3 mode: InnerProducts below this many flops stay on the fp32 kernel (its small-tile variant is as fast there)
 _X3_MIN_FLOPS = 2.0e9
+
+# What an InnerProduct kernel family needs, per kind (_fc_kind): the single-call entry point; the entry point that packs the weights
+# and the bytes per packed value; the stage-major 2-byte form its rows arrive in (Blob._sm; 0 none, 1 f16, 2 bf16x3, 3 bf16) with the
+# multiples of K and of the producer's channel count C that form needs; mnc_fc_lowp_pair's mode (None: no paired launch); and whether
+# the packed weights are e4m3 codes (mnc_pack_fc_f8_bytes of them) with the rows' exponents behind them -- that kernel takes the
+# exponent array as one more argument and writes no second output but the fp16 panel.
+_FcKind = namedtuple("_FcKind", "entry pack bytes sm sm_k sm_c pair wexp")
+_FC_KINDS = {"fp32": _FcKind("mnc_fc", None, 4, 0, 1, 1, None, False),
+             "x3": _FcKind("mnc_fc_bf16x3_ex", "mnc_pack_fc_bf16x3", 4, 2, 32, 32, 0, False),
+             "f16": _FcKind("mnc_fc_f16_ex", "mnc_pack_fc_f16", 2, 1, 64, 64, 1, False),
+             "bf16": _FcKind("mnc_fc_bf16_ex", "mnc_pack_fc_bf16", 2, 3, 64, 64, 2, False),
+             "f8": _FcKind("mnc_fc_f8_ex", "mnc_pack_fc_f8", None, 1, 128, 64, None, True)}      # (bytes: mnc_pack_fc_f8_bytes says)
+
+
+def _fc_kind(math, fc_math, M, n_out, K):
+    """The kernel family ('fp32', 'x3' = split bf16, 'f16', 'bf16', 'f8': a key of _FC_KINDS) of an InnerProduct of M rows, n_out
+    outputs and K inputs in a math mode (math_modes).  csrc/pipeline.hip's prepare_fc states the same rule for the native pipeline."""
+    if 2.0 * M * n_out * K < _X3_MIN_FLOPS:               # small products stay on the fp32 kernel
+        return "fp32"
+    # mixed: an InnerProduct over more than 50 000 inputs (fc6_maskest: 100 352) stays split-bf16
+    fm = "bf16x3" if (math == "mixed" and K > 50000) else fc_math
+    if fm == "f8":                                        # e4m3 over whole 128-value stages only; otherwise the f16 rules
+        if K % 128 == 0:
+            return "f8"
+        fm = "f16"
+    if fm in ("f16", "bf16") and K % 64 == 0:             # (plain bf16: the fp16 kernel's layout and launcher)
+        return fm
+    if fm in ("f16", "bf16x3") and K % 32 == 0:
+        return "x3"
+    return "fp32"
+
+
+def _fc_sm_format(kind, K, C):
+    """Stage-major format a producer with C channels writes rows of length K in for an InnerProduct of `kind`; 0: it cannot."""
+    fk = _FC_KINDS[kind]
+    return fk.sm if (fk.sm and K % fk.sm_k == 0 and C % fk.sm_c == 0) else 0
+
+
+# The tuned 3x3 kernels, per reduced-precision conv math and, in fp32, per Winograd mode (the direct implicit GEMM, or F(2x2,3x3) /
+# F(4x4,3x3) on the same fp32 matrix pipe: fewer multiplies, equal to the direct form up to fp32 rounding; MNC_CONV_WINOGRAD /
+# Net(winograd=)): (floats of packed weights per 8 input channels and output channel; planes per 16-channel block of the reduced-
+# precision form, include/mnc_hip.h: mnc_conv3x3_lowp_weight_bytes -- the buffer holds the larger of the two; pack entry; conv entry)
+_CONV3X3 = {"f16": (84, 2, "mnc_pack_conv3x3_f16", "mnc_conv3x3_f16"),
+            "bf16": (84, 2, "mnc_pack_conv3x3_bf16", "mnc_conv3x3_bf16"),
+            "bf16x3": (84, 4, "mnc_pack_conv3x3_bf16x3", "mnc_conv3x3_bf16x3"),
+            4: (288, 0, "mnc_pack_conv3x3_wino4", "mnc_conv3x3_wino4"),
+            2: (136, 0, "mnc_pack_conv3x3_wino", "mnc_conv3x3_wino"),
+            0: (76, 0, "mnc_pack_conv3x3_weights", "mnc_conv3x3")}
+
+
+def _images(N, src, sstride, dst, dstride):
+    """(src_n, dst_n) of each of the N images of a batch: the base pointers stepped by the bytes per image."""
+    for n in range(N):
+        yield src + n * sstride, dst + n * dstride
+
+
+def _images_res(N, src, sstride, res, rstride, dst, dstride):
+    """(src_n, res_n, dst_n): the same with a residual input between them, None where the layer has none."""
+    for n in range(N):
+        yield src + n * sstride, None if res is None else res + n * rstride, dst + n * dstride
+
 
 install_paths()
 
@@ -567,10 +628,26 @@ class Net(object):
         _lib.call("mnc_h2d", self._ctx.h, p, _lib.ptr(arr), arr.nbytes)
         return p
 
+    def _pack(self, raw, nbytes, entry, *dims, second=None):
+        """One weight-packing step: `entry` packs the device array `raw` into a new buffer of nbytes, `raw` is freed -> the packed
+        buffer.  Chained: permute, then precision-pack.  (second: byte offset of a second output array inside the buffer.)"""
+        packed = self._ctx.alloc(nbytes)
+        if second is None:
+            _lib.call(entry, self._h(), raw, packed, *dims)
+        else:
+            _lib.call(entry, self._h(), raw, packed, packed + second, *dims)
+        self._ctx.free(raw)
+        return packed
+
     def _dev_param(self, key, builder):
         if key not in self._dev_params:
             self._dev_params[key] = builder()
         return self._dev_params[key]
+
+    @staticmethod
+    def _param_key(L):
+        """What a layer's device parameters are filed under: Caffe's shared `param { name }`s where all are given, else its own name."""
+        return tuple(L.param_names) if L.param_names and all(L.param_names) else (L.name,)
 
     # ------------------------------------------------------------------------------------------------ planning
     def _sole_consumer(self, blob, typ):
@@ -849,179 +926,152 @@ class Net(object):
         return Wf, bf
 
     def _bind_Convolution(self, L, i):
-        k, pad, stride, cout, _ = self._conv_geometry(L)
-        kind = self._conv_kind(L)
+        """What every kernel family shares: folded parameters, the bias on the device, the blobs, the ReLU flag; the family's own
+        binder (_conv_kind names it) packs the weights and returns the layer's run()."""
         W, b = self._folded_conv_params(L)
-        cin = W.shape[1]
-        key = tuple(L.param_names) if all(L.param_names) and L.param_names else (L.name,)
+        key = self._param_key(L)
         d_b = self._dev_param(key + ("b",), lambda: self._upload(b))
         bot, top = self.blobs[L.bottoms[0]], self.blobs[L.out_name or L.tops[0]]
-        relu = 1 if L.relu else 0
-        if kind == "c3":
+        return getattr(self, "_bind_conv_" + self._conv_kind(L))(L, W, d_b, key, bot, top, 1 if L.relu else 0)
+
+    @staticmethod
+    def _check_residual(L, res, shape):
+        if res is not None and tuple(res.shape) != shape:
+            raise ValueError("Convolution %s: residual %r has shape %r, expected %r" % (L.name, res.name, res.shape, shape))
+
+    def _bind_conv_c3(self, L, W, d_b, key, bot, top, relu):
+        cout = self._conv_geometry(L)[3]
+        d_w = self._dev_param(key + ("w",), lambda: self._upload(W))
+
+        def run():
+            N, _, H, Wd = bot.shape
+            src = bot.dev_in("plain")
+            top.reshape(N, cout, H, Wd)
+            pk = _PACKED_OF.get(self.conv_math, "c8h")
+            dst = top.dev_out(pk if L.out_h else "c8")
+            ob = _PACKED[pk][0] if L.out_h else 4
+            for s, d in _images(N, src, 3 * H * Wd * 4, dst, cout * H * Wd * ob):     # one launch sequence per image of the batch
+                if L.out_h:                              # (out_fmt of mnc_conv3x3_c3_fmt: 1 split bf16, 2 fp16, 3 bf16)
+                    _lib.call("mnc_conv3x3_c3_fmt", self._h(), s, d_w, d_b, d, H, Wd, cout, relu, _PACKED[pk][1] + 1)
+                else:
+                    _lib.call("mnc_conv3x3_c3", self._h(), s, d_w, d_b, d, H, Wd, cout, relu)
+        return run
+
+    def _bind_conv_stem(self, L, W, d_b, key, bot, top, relu):
+        k, pad, stride, cout, _ = self._conv_geometry(L)
+        if W.shape[1] != 3 or W.shape[2] != W.shape[3]:
+            raise NotImplementedError("Convolution %s on the input blob: 3 channels, square kernel" % L.name)
+        # "f16" mode: the stem on the fp16 matrix pipe like every other convolution of the mode (kernel rows padded to 8 taps,
+        # weights in registers; csrc/conv_gen.hip) -- MNC_STEM_F16=0 keeps the fp32 VALU kernel
+        mfma = (self.conv_math == "f16" and k in (3, 5, 7) and cout % 32 == 0 and os.environ.get("MNC_STEM_F16", "1") != "0")
+        if mfma:
+            d_w = self._dev_param(key + ("w", "stem_f16"), lambda: self._pack(
+                self._upload(W), ((3 * k + 1) // 2) * (cout // 32) * 1024, "mnc_pack_conv_stem_f16", cout, k))
+        else:
             d_w = self._dev_param(key + ("w",), lambda: self._upload(W))
+        conv = "mnc_conv_stem_f16" if mfma else "mnc_conv_stem_c3_fmt"
 
-            def run():
-                N, _, H, Wd = bot.shape
-                src = bot.dev_in("plain")
-                top.reshape(N, cout, H, Wd)
-                pk = _PACKED_OF.get(self.conv_math, "c8h")
-                dst = top.dev_out(pk if L.out_h else "c8")
-                ob = _PACKED[pk][0] if L.out_h else 4
-                for n in range(N):                       # one launch sequence per image of the batch
-                    if L.out_h:                          # (out_fmt of mnc_conv3x3_c3_fmt: 1 split bf16, 2 fp16, 3 bf16)
-                        _lib.call("mnc_conv3x3_c3_fmt", self._h(), src + n * 3 * H * Wd * 4, d_w, d_b,
-                                  dst + n * cout * H * Wd * ob, H, Wd, cout, relu, _PACKED[pk][1] + 1)
-                    else:
-                        _lib.call("mnc_conv3x3_c3", self._h(), src + n * 3 * H * Wd * 4, d_w, d_b, dst + n * cout * H * Wd * 4,
-                                  H, Wd, cout, relu)
-            return run
-        if kind == "stem":
-            if cin != 3 or W.shape[2] != W.shape[3]:
-                raise NotImplementedError("Convolution %s on the input blob: 3 channels, square kernel" % L.name)
-            # "f16" mode: the stem on the fp16 matrix pipe like every other convolution of the mode (kernel rows padded to 8 taps,
-            # weights in registers; csrc/conv_gen.hip) -- MNC_STEM_F16=0 keeps the fp32 VALU kernel
-            mfma = (self.conv_math == "f16" and k in (3, 5, 7) and cout % 32 == 0 and os.environ.get("MNC_STEM_F16", "1") != "0")
-            if mfma:
-                def build_stem():
-                    raw = self._upload(W)
-                    packed = self._ctx.alloc(((3 * k + 1) // 2) * (cout // 32) * 1024)
-                    _lib.call("mnc_pack_conv_stem_f16", self._h(), raw, packed, cout, k)
-                    self._ctx.free(raw)
-                    return packed
-                d_w = self._dev_param(key + ("w", "stem_f16"), build_stem)
-            else:
-                d_w = self._dev_param(key + ("w",), lambda: self._upload(W))
+        def run():
+            N, _, H, Wd = bot.shape
+            OH, OW = (H + 2 * pad - k) // stride + 1, (Wd + 2 * pad - k) // stride + 1
+            src = bot.dev_in("plain")
+            top.reshape(N, cout, OH, OW)
+            dst = top.dev_out("c8h" if L.out_h else "c8")
+            for s, d in _images(N, src, 3 * H * Wd * 4, dst, cout * OH * OW * (2 if L.out_h else 4)):
+                _lib.call(conv, self._h(), s, d_w, d_b, d, H, Wd, cout, k, stride, pad, relu, 1 if L.out_h else 0)
+        return run
 
-            def run():
-                N, _, H, Wd = bot.shape
-                OH, OW = (H + 2 * pad - k) // stride + 1, (Wd + 2 * pad - k) // stride + 1
-                src = bot.dev_in("plain")
+    def _bind_conv_fast3x3(self, L, W, d_b, key, bot, top, relu):
+        cout, cin = self._conv_geometry(L)[3], W.shape[1]
+        x3 = self.conv_math in ("bf16x3", "f16", "bf16")
+        pitch, planes, pack, conv = _CONV3X3[self.conv_math if x3 else self._wino]
+        nbytes = max((cin // 8) * cout * pitch * 4, ((cin + 15) // 16) * (cout // 32) * planes * 4608)
+        d_w = self._dev_param(key + ("w", self.conv_math, ("wino%d" % self._wino) if (self._winograd and not x3) else "direct"),
+                              lambda: self._pack(self._upload(W), nbytes, pack, cout, cin))
+        conv_pk, wino_pool = conv + "_pk", "mnc_conv3x3_wino4_pool" if self._wino == 4 else "mnc_conv3x3_wino_pool"
+
+        def split_form(H, Wd):
+            """(weights, workspace) of the unfused F(4x4) form where the context's WINO_SPLIT value moves this layer there (the
+            native pipeline asks the same question, so both run the same kernels), else None."""
+            selected = getattr(_lib.load(), "mnc_conv3x3_wino4_split_selected", None)     # (None: a backend without the split form)
+            if x3 or self._wino != 4 or selected is None or not selected(self._h(), H, Wd, cin, cout):
+                return None
+            need = int(_lib.load().mnc_conv3x3_wino4_split_ws_bytes(H, Wd, cin, cout))
+            have = max([k[1] for k in self._dev_params if k[0] == "wino4_split_ws"] or [0])
+            if have < need:       # (grow-only; a smaller one stays allocated until close: launches in flight may still use it)
+                have = need
+                self._dev_params[("wino4_split_ws", have)] = self._ctx.alloc(have)
+            d_split = self._dev_param(key + ("w", "wino4split"), lambda: self._pack(
+                self._upload(W), 36 * cout * cin * 4, "mnc_pack_conv3x3_wino4_split", cout, cin))
+            return d_split, self._dev_params[("wino4_split_ws", have)]
+
+        def run():
+            N, _, H, Wd = bot.shape
+            pk = _PACKED_OF.get(self.conv_math)
+            in_h = pk is not None and bot._dev_valid and bot.layout == pk
+            src = bot.dev_in(pk if in_h else "c8")
+            if L.fused_pool and pk is not None:        # reduced precision: packed in, pooled packed out (a fp32 consumer widens it)
+                if not in_h:
+                    src = bot.dev_in(pk)
+                OH, OW = _pool_out(H), _pool_out(Wd)
                 top.reshape(N, cout, OH, OW)
-                dst = top.dev_out("c8h" if L.out_h else "c8")
-                ob = 2 if L.out_h else 4
-                for n in range(N):
-                    _lib.call("mnc_conv_stem_f16" if mfma else "mnc_conv_stem_c3_fmt", self._h(), src + n * 3 * H * Wd * 4, d_w, d_b,
-                              dst + n * cout * OH * OW * ob, H, Wd, cout, k, stride, pad, relu, 1 if L.out_h else 0)
-            return run
-        if kind == "fast3x3":
-            x3 = self.conv_math in ("bf16x3", "f16", "bf16")
-            # fp32 mode: the direct implicit GEMM, or Winograd F(2x2,3x3) on the same fp32 matrix pipe (2.25x fewer multiplies,
-            # equal to the direct form up to fp32 rounding; MNC_CONV_WINOGRAD / Net(winograd=))
-            pitch, pack, conv = (84, "mnc_pack_conv3x3_f16", "mnc_conv3x3_f16") if self.conv_math == "f16" else \
-                                (84, "mnc_pack_conv3x3_bf16", "mnc_conv3x3_bf16") if self.conv_math == "bf16" else \
-                                (84, "mnc_pack_conv3x3_bf16x3", "mnc_conv3x3_bf16x3") if x3 else \
-                                (288, "mnc_pack_conv3x3_wino4", "mnc_conv3x3_wino4") if self._wino == 4 else \
-                                (136, "mnc_pack_conv3x3_wino", "mnc_conv3x3_wino") if self._wino == 2 else \
-                                (76, "mnc_pack_conv3x3_weights", "mnc_conv3x3")
-
-            def build():
-                raw = self._upload(W)
-                nbytes = (cin // 8) * cout * pitch * 4
-                if x3:     # include/mnc_hip.h: mnc_conv3x3_lowp_weight_bytes (bf16x3: four planes per 16-channel block, else two)
-                    nbytes = max(nbytes, ((cin + 15) // 16) * (cout // 32) * (4 if self.conv_math == "bf16x3" else 2) * 4608)
-                packed = self._ctx.alloc(nbytes)
-                _lib.call(pack, self._h(), raw, packed, cout, cin)
-                self._ctx.free(raw)
-                return packed
-            d_w = self._dev_param(key + ("w", self.conv_math, ("wino%d" % self._wino) if (self._winograd and not x3) else "direct"), build)
-
-            def split_form(H, Wd):
-                """(weights, workspace) of the unfused F(4x4) form where the context's WINO_SPLIT value moves this layer there (the
-                native pipeline asks the same question, so both run the same kernels), else None."""
-                selected = getattr(_lib.load(), "mnc_conv3x3_wino4_split_selected", None)     # (None: a backend without the split form)
-                if x3 or self._wino != 4 or selected is None or not selected(self._h(), H, Wd, cin, cout):
-                    return None
-
-                def build_split():
-                    raw = self._upload(W)
-                    packed = self._ctx.alloc(36 * cout * cin * 4)
-                    _lib.call("mnc_pack_conv3x3_wino4_split", self._h(), raw, packed, cout, cin)
-                    self._ctx.free(raw)
-                    return packed
-                need = int(_lib.load().mnc_conv3x3_wino4_split_ws_bytes(H, Wd, cin, cout))
-                have = max([k[1] for k in self._dev_params if k[0] == "wino4_split_ws"] or [0])
-                if have < need:       # (grow-only; a smaller one stays allocated until close: launches in flight may still use it)
-                    have = need
-                    self._dev_params[("wino4_split_ws", have)] = self._ctx.alloc(have)
-                return self._dev_param(key + ("w", "wino4split"), build_split), self._dev_params[("wino4_split_ws", have)]
-
-            def run():
-                N, _, H, Wd = bot.shape
-                pk = _PACKED_OF.get(self.conv_math)
-                in_h = pk is not None and bot._dev_valid and bot.layout == pk
-                src = bot.dev_in(pk if in_h else "c8")
-                if L.fused_pool and pk is not None:        # reduced precision: packed in, pooled packed out (a fp32 consumer widens it)
-                    if not in_h:
-                        src = bot.dev_in(pk)
-                    OH, OW = _pool_out(H), _pool_out(Wd)
-                    top.reshape(N, cout, OH, OW)
-                    dst = top.dev_out(pk)
-                    eb, mode = _PACKED[pk]
-                    for n in range(N):
-                        _lib.call("mnc_conv3x3_lowp_pool", self._h(), mode, src + n * cin * H * Wd * eb, d_w, d_b,
-                                  dst + n * cout * OH * OW * eb, H, Wd, cin, cout, relu)
-                    return
-                if L.fused_pool:                           # top is the Pooling layer's blob
-                    OH, OW = _pool_out(H), _pool_out(Wd)
-                    top.reshape(N, cout, OH, OW)
-                    dst = top.dev_out("c8")
-                    sp = split_form(H, Wd)
-                    for n in range(N):
-                        if sp:
-                            _lib.call("mnc_conv3x3_wino4_split_pool", self._h(), src + n * cin * H * Wd * 4, sp[0], d_b,
-                                      dst + n * cout * OH * OW * 4, sp[1], H, Wd, cin, cout, relu)
-                            continue
-                        _lib.call("mnc_conv3x3_wino4_pool" if self._wino == 4 else "mnc_conv3x3_wino_pool", self._h(), src + n * cin * H * Wd * 4, d_w, d_b,
-                                  dst + n * cout * OH * OW * 4, H, Wd, cin, cout, relu)
-                    return
-                top.reshape(N, cout, H, Wd)
-                if in_h or L.out_h:                        # packed activation tensors on either side (the mode's own form)
-                    dst = top.dev_out(pk if L.out_h else "c8")
-                    eb = _PACKED[pk][0]
-                    ib, ob = (eb if in_h else 4), (eb if L.out_h else 4)
-                    for n in range(N):
-                        _lib.call(conv + "_pk", self._h(), src + n * cin * H * Wd * ib, d_w, d_b,
-                                  dst + n * cout * H * Wd * ob, H, Wd, cin, cout, relu, 1 if in_h else 0, 1 if L.out_h else 0)
-                    return
+                dst = top.dev_out(pk)
+                eb, mode = _PACKED[pk]
+                for s, d in _images(N, src, cin * H * Wd * eb, dst, cout * OH * OW * eb):
+                    _lib.call("mnc_conv3x3_lowp_pool", self._h(), mode, s, d_w, d_b, d, H, Wd, cin, cout, relu)
+                return
+            if L.fused_pool:                           # top is the Pooling layer's blob
+                OH, OW = _pool_out(H), _pool_out(Wd)
+                top.reshape(N, cout, OH, OW)
                 dst = top.dev_out("c8")
                 sp = split_form(H, Wd)
-                for n in range(N):
+                for s, d in _images(N, src, cin * H * Wd * 4, dst, cout * OH * OW * 4):
                     if sp:
-                        _lib.call("mnc_conv3x3_wino4_split", self._h(), src + n * cin * H * Wd * 4, sp[0], d_b,
-                                  dst + n * cout * H * Wd * 4, sp[1], H, Wd, cin, cout, relu)
-                        continue
-                    _lib.call(conv, self._h(), src + n * cin * H * Wd * 4, d_w, d_b, dst + n * cout * H * Wd * 4, H, Wd, cin,
-                              cout, relu)
-            return run
-        if kind == "nchw1x1":
-            d_w = self._dev_param(key + ("w",), lambda: self._upload(W.reshape(cout, cin)))
+                        _lib.call("mnc_conv3x3_wino4_split_pool", self._h(), s, sp[0], d_b, d, sp[1], H, Wd, cin, cout, relu)
+                    else:
+                        _lib.call(wino_pool, self._h(), s, d_w, d_b, d, H, Wd, cin, cout, relu)
+                return
+            top.reshape(N, cout, H, Wd)
+            if in_h or L.out_h:                        # packed activation tensors on either side (the mode's own form)
+                dst = top.dev_out(pk if L.out_h else "c8")
+                eb = _PACKED[pk][0]
+                ib, ob = (eb if in_h else 4), (eb if L.out_h else 4)
+                for s, d in _images(N, src, cin * H * Wd * ib, dst, cout * H * Wd * ob):
+                    _lib.call(conv_pk, self._h(), s, d_w, d_b, d, H, Wd, cin, cout, relu, 1 if in_h else 0, 1 if L.out_h else 0)
+                return
+            dst = top.dev_out("c8")
+            sp = split_form(H, Wd)
+            for s, d in _images(N, src, cin * H * Wd * 4, dst, cout * H * Wd * 4):
+                if sp:
+                    _lib.call("mnc_conv3x3_wino4_split", self._h(), s, sp[0], d_b, d, sp[1], H, Wd, cin, cout, relu)
+                else:
+                    _lib.call(conv, self._h(), s, d_w, d_b, d, H, Wd, cin, cout, relu)
+        return run
 
-            def run():
-                N, _, H, Wd = bot.shape
-                src = bot.dev_in("c8")
-                top.reshape(N, cout, H, Wd)
-                dst = top.dev_out("plain")
-                for n in range(N):
-                    _lib.call("mnc_conv1x1_to_nchw", self._h(), src + n * cin * H * Wd * 4, d_w, d_b,
-                              dst + n * cout * H * Wd * 4, H, Wd, cin, cout)
-            return run
-        # general: any kernel / stride / pad on the fp32 matrix pipe (fp16 pipe in the f16 mode), residual add and ReLU in the epilogue
+    def _bind_conv_nchw1x1(self, L, W, d_b, key, bot, top, relu):
+        cout, cin = self._conv_geometry(L)[3], W.shape[1]
+        d_w = self._dev_param(key + ("w",), lambda: self._upload(W.reshape(cout, cin)))
+
+        def run():
+            N, _, H, Wd = bot.shape
+            src = bot.dev_in("c8")
+            top.reshape(N, cout, H, Wd)
+            dst = top.dev_out("plain")
+            for s, d in _images(N, src, cin * H * Wd * 4, dst, cout * H * Wd * 4):
+                _lib.call("mnc_conv1x1_to_nchw", self._h(), s, d_w, d_b, d, H, Wd, cin, cout)
+        return run
+
+    def _bind_conv_general(self, L, W, d_b, key, bot, top, relu):
+        """Any kernel / stride / pad on the fp32 matrix pipe (fp16 pipe in the f16 mode), residual add and ReLU in the epilogue."""
+        _, pad, stride, cout, _ = self._conv_geometry(L)
+        cin, kh, kw = W.shape[1:]
         if cin % 8 or cout % 8:
             raise NotImplementedError("Convolution %s: channel counts must be multiples of 8 (got %d -> %d)" % (L.name, cin, cout))
-        kh, kw = W.shape[2], W.shape[3]
-
-        f16 = self.conv_math == "f16"
-        conv2d = "mnc_conv2d_f16" if f16 else "mnc_conv2d"
         if self._conv_fast1x1(L):
-            return self._bind_conv1x1(L, W, d_b, key, bot, top, stride, relu)
-
-        def build_general():
-            raw = self._upload(W)
-            packed = self._ctx.alloc(kh * kw * ((cin + 31) // 32) * 32 * cout * 2 if f16 else W.nbytes)
-            _lib.call("mnc_pack_conv_weights_f16" if f16 else "mnc_pack_conv_weights", self._h(), raw, packed, cout, cin, kh, kw)
-            self._ctx.free(raw)
-            return packed
-        d_w = self._dev_param(key + ("w", "general", "f16" if f16 else "fp32"), build_general)
+            return self._bind_conv1x1(L, W, d_b, key, bot, top, relu)
+        nbytes, pack, conv2d, tag = (kh * kw * ((cin + 31) // 32) * 32 * cout * 2, "mnc_pack_conv_weights_f16", "mnc_conv2d_f16", "f16") \
+            if self.conv_math == "f16" else (W.nbytes, "mnc_pack_conv_weights", "mnc_conv2d", "fp32")
+        d_w = self._dev_param(key + ("w", "general", tag), lambda: self._pack(self._upload(W), nbytes, pack, cout, cin, kh, kw))
         res = self.blobs[L.residual] if L.residual else None
 
         def run():
@@ -1029,48 +1079,36 @@ class Net(object):
             OH, OW = (H + 2 * pad - kh) // stride + 1, (Wd + 2 * pad - kw) // stride + 1
             src = bot.dev_in("c8")
             rsrc = res.dev_in("c8") if res is not None else None
-            if res is not None and tuple(res.shape) != (N, cout, OH, OW):
-                raise ValueError("Convolution %s: residual %r has shape %r, expected %r" % (L.name, res.name, res.shape,
-                                                                                            (N, cout, OH, OW)))
+            self._check_residual(L, res, (N, cout, OH, OW))
             top.reshape(N, cout, OH, OW)
             dst = top.dev_out("c8")
-            for n in range(N):
-                _lib.call(conv2d, self._h(), src + n * cin * H * Wd * 4, d_w, d_b,
-                          (rsrc + n * cout * OH * OW * 4) if rsrc is not None else None, dst + n * cout * OH * OW * 4, H, Wd, cin,
-                          cout, kh, kw, stride, pad, relu)
+            for s, r, d in _images_res(N, src, cin * H * Wd * 4, rsrc, cout * OH * OW * 4, dst, cout * OH * OW * 4):
+                _lib.call(conv2d, self._h(), s, d_w, d_b, r, d, H, Wd, cin, cout, kh, kw, stride, pad, relu)
         return run
 
-    def _bind_conv1x1(self, L, W, d_b, key, bot, top, stride, relu):
+    def _bind_conv1x1(self, L, W, d_b, key, bot, top, relu):
         """1x1 convolution (stride 1 / 2) as a plain GEMM straight from the c8 tensors (csrc/conv1x1.hip).  fp32 / bf16x3 modes:
         fp32 matrix pipe, fp32 tensors.  f16 mode: packed fp16 input (converted once if a producer left fp32), packed or fp32
         output as planned (_plan_formats), residual in whichever form its producer wrote."""
+        stride = self._conv_geometry(L)[2]
         cout, cin = int(W.shape[0]), int(W.shape[1])
         f16 = self.conv_math == "f16"
-
-        def build():
-            raw = self._upload(W.reshape(cout, cin))
-            packed = self._ctx.alloc(cin * ((cout + 31) // 32) * 32 * (2 if f16 else 4))
-            _lib.call("mnc_pack_conv1x1", self._h(), raw, packed, cout, cin, 1 if f16 else 0)
-            self._ctx.free(raw)
-            return packed
-        d_w = self._dev_param(key + ("w", "1x1", "f16" if f16 else "fp32"), build)
+        d_w = self._dev_param(key + ("w", "1x1", "f16" if f16 else "fp32"), lambda: self._pack(
+            self._upload(W.reshape(cout, cin)), cin * ((cout + 31) // 32) * 32 * (2 if f16 else 4), "mnc_pack_conv1x1", cout, cin,
+            1 if f16 else 0))
         res = self.blobs[L.residual] if L.residual else None
 
         def run():
             N, _, H, Wd = bot.shape
             OH, OW = (H - 1) // stride + 1, (Wd - 1) // stride + 1
-            if res is not None and tuple(res.shape) != (N, cout, OH, OW):
-                raise ValueError("Convolution %s: residual %r has shape %r, expected %r" % (L.name, res.name, res.shape,
-                                                                                            (N, cout, OH, OW)))
+            self._check_residual(L, res, (N, cout, OH, OW))
             if not f16:
                 src = bot.dev_in("c8")
                 rsrc = res.dev_in("c8") if res is not None else None
                 top.reshape(N, cout, OH, OW)
                 dst = top.dev_out("c8")
-                for n in range(N):
-                    _lib.call("mnc_conv1x1", self._h(), src + n * cin * H * Wd * 4, d_w, d_b,
-                              (rsrc + n * cout * OH * OW * 4) if rsrc is not None else None, dst + n * cout * OH * OW * 4,
-                              H, Wd, cin, cout, stride, relu)
+                for s, r, d in _images_res(N, src, cin * H * Wd * 4, rsrc, cout * OH * OW * 4, dst, cout * OH * OW * 4):
+                    _lib.call("mnc_conv1x1", self._h(), s, d_w, d_b, r, d, H, Wd, cin, cout, stride, relu)
                 return
             src = bot.dev_in("c8h")
             res_h = res is not None and res._dev_valid and res.layout == "c8h"
@@ -1078,10 +1116,9 @@ class Net(object):
             rb, ob = (2 if res_h else 4), (2 if L.out_h else 4)
             top.reshape(N, cout, OH, OW)
             dst = top.dev_out("c8h" if L.out_h else "c8")
-            for n in range(N):
-                _lib.call("mnc_conv1x1_f16_pk", self._h(), src + n * cin * H * Wd * 2, d_w, d_b,
-                          (rsrc + n * cout * OH * OW * rb) if rsrc is not None else None, dst + n * cout * OH * OW * ob,
-                          H, Wd, cin, cout, stride, relu, 1 if res_h else 0, 1 if L.out_h else 0)
+            for s, r, d in _images_res(N, src, cin * H * Wd * 2, rsrc, cout * OH * OW * rb, dst, cout * OH * OW * ob):
+                _lib.call("mnc_conv1x1_f16_pk", self._h(), s, d_w, d_b, r, d, H, Wd, cin, cout, stride, relu, 1 if res_h else 0,
+                          1 if L.out_h else 0)
         return run
 
     def _bind_ReLU(self, L, i):
@@ -1248,8 +1285,8 @@ class Net(object):
     def _sm_format(self, blob, M, K, C):
         """Second output of a per-RoI producer (ROIWarping / Pooling / MaskPooling) -> 0 none, 1 f16, 2 bf16x3, 3 bf16: the stage-major
         2-byte form (Blob._sm) when an InnerProduct that reads `blob` will run on the reduced-precision kernels for this M
-        (same rule as _bind_InnerProduct.weights_for), so that it does not have to convert the fp32 rows itself.  MNC_FC_SM=0
-        switches the second outputs off."""
+        (_fc_kind), so that it does not have to convert the fp32 rows itself: for each such consumer, its kind's format if C fits
+        (the last one that has a format wins).  MNC_FC_SM=0 switches the second outputs off."""
         if self.fc_math == "fp32" or M <= 0 or os.environ.get("MNC_FC_SM", "1") == "0":
             return 0
         fmt = 0
@@ -1257,19 +1294,7 @@ class Net(object):
             L = self._layers[i]
             if L.type != "InnerProduct" or L.skip or L.group is not None or L.group_leader is not None:
                 continue
-            n_out = L.msg.get1("inner_product_param").get1("num_output")
-            if 2.0 * M * n_out * K < _X3_MIN_FLOPS:
-                continue
-            fm = "bf16x3" if (self.math == "mixed" and K > 50000) else self.fc_math      # (weights_for's rule)
-            if fm == "f8":             # e4m3 (K % 128 == 0) multiplies from the fp16 panel too; other K: the f16 rules
-                fm = "f16"
-            if fm == "f16" and K % 64 == 0 and C % 64 == 0:
-                fmt = 1
-            elif fm == "bf16":                            # round 6: format 3 = fp16's layout, bf16 values (mnc_fc_bf16_ex)
-                if K % 64 == 0 and C % 64 == 0:
-                    fmt = 3
-            elif K % 32 == 0 and C % 32 == 0 and not (fm == "f16" and K % 64 == 0):
-                fmt = 2
+            fmt = _fc_sm_format(_fc_kind(self.math, self.fc_math, M, self._layer_nout(L), K), K, C) or fmt
         return fmt
 
     def _sm_only_ok(self, blob):
@@ -1369,6 +1394,24 @@ class Net(object):
                 _lib.call("mnc_mask_pool", self._h(), d_feat, d_mask, dst, R, PH, PW, C, pool2)
         return run
 
+    def _fc_weights(self, key, W, n_out, shape, kind):
+        """-> (device weights of an InnerProduct in the packed form of `kind`, layout its rows are read in, address of the rows'
+        exponents behind e4m3 codes or None).  Caffe flattens (C,PH,PW); the engine's per-RoI features are (PH,PW,C): permute the
+        columns once, then the kind's precision pack (x3: the weights pre-split into hi/lo bf16)."""
+        fk, K = _FC_KINDS[kind], W.shape[1]
+        geo = (shape[1], shape[2], shape[3]) if len(shape) == 4 and shape[2] * shape[3] > 1 else None
+        code_bytes = _lib.load().mnc_pack_fc_f8_bytes(n_out, K) if fk.wexp else None
+
+        def packed():
+            d_w = self._upload(W)
+            if geo:
+                d_w = self._pack(d_w, W.nbytes, "mnc_pack_fc_weights", n_out, *geo)
+            if fk.wexp:                            # codes, then the rows' exponents
+                return self._pack(d_w, code_bytes + (n_out + 255) // 256 * 256 * 4, fk.pack, n_out, K, second=code_bytes)
+            return self._pack(d_w, (n_out + 127) // 128 * 128 * K * fk.bytes, fk.pack, n_out, K) if fk.pack else d_w
+        d_w = self._dev_param(key + ("w",) + (geo or ("plain",)) + (() if kind == "fp32" else (kind,)), packed)
+        return d_w, "rhwc" if geo else "plain", d_w + code_bytes if fk.wexp else None
+
     def _bind_InnerProduct(self, L, i):
         if L.group_leader is not None:                 # computed by the group's leader
             W, b = self._layer_weights(L)
@@ -1376,10 +1419,10 @@ class Net(object):
             return None
         if L.group is not None:
             return self._bind_ip_group(L)
-        n_out = L.msg.get1("inner_product_param").get1("num_output")
+        n_out = self._layer_nout(L)
         W, b = self._layer_weights(L)
         self.params[L.name] = [_Param(W), _Param(b)]
-        key = tuple(L.param_names) if L.param_names and all(L.param_names) else (L.name,)
+        key = self._param_key(L)
         d_b = self._dev_param(key + ("b",), lambda: self._upload(b))
         bot = self.blobs[L.bottoms[0]]
         top = self.blobs[L.out_name or L.tops[0]]
@@ -1387,74 +1430,25 @@ class Net(object):
         K = W.shape[1]
         state = {}
 
-        def weights_for(shape, M):
-            """Caffe flattens (C,PH,PW); the engine's per-RoI features are (PH,PW,C): permute the columns once.  In
-            bf16x3 mode the large products additionally get the weights pre-split into hi/lo bf16."""
-            big = 2.0 * M * n_out * K >= _X3_MIN_FLOPS
-            # mixed: an InnerProduct over more than 50 000 inputs (fc6_maskest: 100 352) stays split-bf16 (pipeline.hip: prepare_fc)
-            fm = "bf16x3" if (self.math == "mixed" and K > 50000) else self.fc_math
-            if fm == "f8" and not (big and K % 128 == 0):      # f8: only the large products over whole 128-value stages;
-                fm = "f16"                                     # otherwise the f16 rules (pipeline.hip: prepare_fc)
-            if fm == "f8":
-                def finish8(d_w):
-                    code_bytes = _lib.load().mnc_pack_fc_f8_bytes(n_out, K)
-                    packed = self._ctx.alloc(code_bytes + (n_out + 255) // 256 * 256 * 4)      # codes, then the rows' exponents
-                    _lib.call("mnc_pack_fc_f8", self._h(), d_w, packed, packed + code_bytes, n_out, K)
-                    self._ctx.free(d_w)
-                    return packed
-                state["wexp_off"] = _lib.load().mnc_pack_fc_f8_bytes(n_out, K)
-                if len(shape) == 4 and shape[2] * shape[3] > 1:
-                    geo8 = (shape[1], shape[2], shape[3])
-
-                    def build8():
-                        raw = self._upload(W)
-                        perm = self._ctx.alloc(W.nbytes)
-                        _lib.call("mnc_pack_fc_weights", self._h(), raw, perm, n_out, geo8[0], geo8[1], geo8[2])
-                        self._ctx.free(raw)
-                        return finish8(perm)
-                    return self._dev_param(key + ("w",) + geo8 + ("f8",), build8), "rhwc", "mnc_fc_f8"
-                return self._dev_param(key + ("w", "plain", "f8"), lambda: finish8(self._upload(W))), "plain", "mnc_fc_f8"
-            bf = fm == "bf16" and K % 64 == 0 and big          # plain bf16: the fp16 kernel's layout and launcher
-            f16 = (fm == "f16" and K % 64 == 0 and big) or bf
-            x3 = (not f16) and fm in ("bf16x3", "f16") and K % 32 == 0 and big
-            tag = ("bf16",) if bf else ("f16",) if f16 else ("x3",) if x3 else ()
-            fn = "mnc_fc_bf16" if bf else "mnc_fc_f16" if f16 else "mnc_fc_bf16x3" if x3 else "mnc_fc"
-
-            def finish(d_w):
-                if not (x3 or f16):
-                    return d_w
-                packed = self._ctx.alloc((n_out + 127) // 128 * 128 * K * (2 if f16 else 4))
-                _lib.call("mnc_pack_fc_bf16" if bf else "mnc_pack_fc_f16" if f16 else "mnc_pack_fc_bf16x3", self._h(), d_w, packed, n_out, K)
-                self._ctx.free(d_w)
-                return packed
-
-            if len(shape) == 4 and shape[2] * shape[3] > 1:
-                geo = (shape[1], shape[2], shape[3])
-
-                def build():
-                    raw = self._upload(W)
-                    packed = self._ctx.alloc(W.nbytes)
-                    _lib.call("mnc_pack_fc_weights", self._h(), raw, packed, n_out, geo[0], geo[1], geo[2])
-                    self._ctx.free(raw)
-                    return finish(packed)
-                return self._dev_param(key + ("w",) + geo + tag, build), "rhwc", fn
-            return self._dev_param(key + ("w", "plain") + tag, lambda: finish(self._upload(W))), "plain", fn
-
-        LOWP_PAIR = {"mnc_fc_bf16x3": 0, "mnc_fc_f16": 1, "mnc_fc_bf16": 2}          # mnc_fc_lowp_pair's mode per single-call entry point
+        def resolve(M):
+            """Decided by the first forward with rows, which knows M and the bottom's shape: the kernel family and its weights."""
+            state["kind"] = _fc_kind(self.math, self.fc_math, M, n_out, K)
+            state["fk"] = _FC_KINDS[state["kind"]]
+            state["w"], state["layout"], state["wexp"] = self._fc_weights(key, W, n_out, bot.shape, state["kind"])
 
         def lowp_args(M):
             """(fp32 rows or None, stage-major rows or None, dst, second-output format, second output or None) of this layer's
             reduced-precision call, with its top made ready: the rows arrive in the kernel's own 2-byte form when the producer
             wrote them (Blob._sm: no conversion pass), and leave in the NEXT InnerProduct's form as well when one will read them."""
-            want = {"mnc_fc_f16": 1, "mnc_fc_bf16x3": 2, "mnc_fc_bf16": 3, "mnc_fc_f8": 1}.get(state.get("fn"), 0)
+            fk = state["fk"]
             sm = bot._sm
-            pre = bool(want and sm is not None and sm["fmt"] == want and sm["M"] == M and sm["K"] == K
+            pre = bool(sm is not None and sm["fmt"] == fk.sm and sm["M"] == M and sm["K"] == K
                        and (bot._dev_valid or bot._sm_only) and bot.layout == state["layout"])
             src = None if pre else bot.dev_in(state["layout"])
             top.reshape(M, n_out)
             dst = top.dev_out("plain")
-            ofmt = self._sm_format(top.name, M, n_out, n_out) if (want and top._view is None) else 0
-            if state.get("fn") == "mnc_fc_f8" and ofmt != 1:   # (mnc_fc_f8_ex writes the fp16 panel only)
+            ofmt = self._sm_format(top.name, M, n_out, n_out) if top._view is None else 0
+            if fk.wexp and ofmt != 1:                          # (mnc_fc_f8_ex writes the fp16 panel only)
                 ofmt = 0
             return src, (sm["ptr"] if pre else None), dst, ofmt, (top.sm_out(ofmt, M, n_out) if ofmt else None)
 
@@ -1466,56 +1460,53 @@ class Net(object):
                 L.pair_done = False
                 return
             if M and "w" not in state:
-                state["w"], state["layout"], state["fn"] = weights_for(bot.shape, M)
+                resolve(M)
             P = L.pair
-            if M and state.get("fn") == "mnc_fc_f8":           # e4m3: single launches (no paired form)
+            if M and state["fk"].sm:               # a reduced-precision kind
+                fk = state["fk"]
                 src, pre, dst, ofmt, osm = lowp_args(M)
-                _lib.call("mnc_fc_f8_ex", self._h(), src, pre, M, state["w"], state["w"] + state["wexp_off"], d_b, dst, M, n_out, K,
-                          top._ld(), act, osm, ofmt)
-                return
-            if M and state.get("fn") in LOWP_PAIR and P is not None and P.ip_prepare is not None:
-                src, pre, dst, ofmt, osm = lowp_args(M)
-                other = P.ip_prepare(M, K, state["fn"])
-                if other is not None and other["ofmt"] == ofmt and other["ld"] == top._ld():
-                    _lib.call("mnc_fc_lowp_pair", self._h(), LOWP_PAIR[state["fn"]], src, pre, other["src"], other["pre"], M, state["w"],
-                              other["w"], d_b, other["b"], dst, other["dst"], M, n_out, K, top._ld(), act, osm, other["osm"], ofmt)
-                    P.pair_done = True
-                    return
-                _lib.call(state["fn"] + "_ex", self._h(), src, pre, M, state["w"], d_b, dst, M, n_out, K, top._ld(), act, osm, ofmt)
-                return
-            if M and state.get("fn") in LOWP_PAIR:
-                src, pre, dst, ofmt, osm = lowp_args(M)
-                _lib.call(state["fn"] + "_ex", self._h(), src, pre, M, state["w"], d_b, dst, M, n_out, K, top._ld(), act, osm, ofmt)
+                if fk.pair is not None and P is not None and P.ip_prepare is not None:
+                    other = P.ip_prepare(M, K, state["kind"])
+                    if other is not None and other["ofmt"] == ofmt and other["ld"] == top._ld():
+                        _lib.call("mnc_fc_lowp_pair", self._h(), fk.pair, src, pre, other["src"], other["pre"], M, state["w"],
+                                  other["w"], d_b, other["b"], dst, other["dst"], M, n_out, K, top._ld(), act, osm, other["osm"], ofmt)
+                        P.pair_done = True
+                        return
+                if fk.wexp:                        # e4m3: the rows' exponents go with the codes
+                    _lib.call(fk.entry, self._h(), src, pre, M, state["w"], state["wexp"], d_b, dst, M, n_out, K, top._ld(), act,
+                              osm, ofmt)
+                else:
+                    _lib.call(fk.entry, self._h(), src, pre, M, state["w"], d_b, dst, M, n_out, K, top._ld(), act, osm, ofmt)
                 return
             src = bot.dev_in(state["layout"]) if M else 0
             top.reshape(M, n_out)
             dst = top.dev_out("plain")
             if not M:
                 return
-            if P is not None and state["fn"] == "mnc_fc" and P.ip_prepare is not None:
+            if P is not None and state["kind"] == "fp32" and P.ip_prepare is not None:
                 other = P.ip_prepare(M, K)
                 if other is not None:
                     _lib.call("mnc_fc_pair", self._h(), src, state["w"], d_b, dst, other[0], other[1], other[2], other[3], M, n_out,
                               K, top._ld(), act)
                     P.pair_done = True
                     return
-            _lib.call(state["fn"], self._h(), src, state["w"], d_b, dst, M, n_out, K, top._ld(), act)
+            _lib.call(state["fk"].entry, self._h(), src, state["w"], d_b, dst, M, n_out, K, top._ld(), act)
 
-        def prepare(M_leader, K_leader, fn_leader="mnc_fc"):
+        def prepare(M_leader, K_leader, kind_leader="fp32"):
             """As the second member of a pair: (src, weights, bias, dst) of this layer's own mnc_fc call with its top made ready
-            (a dict of its mnc_fc_lowp_pair arguments for the reduced-precision entry points), or None when it cannot share the
+            (a dict of its mnc_fc_lowp_pair arguments for the reduced-precision kinds), or None when it cannot share the
             leader's launch (other row count, other kernel, other leading dimension / activation)."""
             M = bot.shape[0]
             if M != M_leader or K != K_leader or int(np.prod(bot.shape[1:])) != K or not (bot._dev_valid or bot._host_valid or bot._sm_only):
                 return None
             if "w" not in state:
-                state["w"], state["layout"], state["fn"] = weights_for(bot.shape, M)
-            if state["fn"] != fn_leader:
+                resolve(M)
+            if state["kind"] != kind_leader:
                 return None
             lead_top = self.blobs[L.pair_leader.out_name or L.pair_leader.tops[0]]
             if (1 if L.pair_leader.relu else L.pair_leader.act) != act:
                 return None
-            if fn_leader in LOWP_PAIR:
+            if state["fk"].pair is not None:
                 src, pre, dst, ofmt, osm = lowp_args(M)
                 return {"src": src, "pre": pre, "w": state["w"], "b": d_b, "dst": dst, "ofmt": ofmt, "osm": osm, "ld": top._ld()}
             src = bot.dev_in(state["layout"])
@@ -1538,7 +1529,7 @@ class Net(object):
             bs.append(b)
             widths.append(W.shape[0])
         K, total = Ws[0].shape[1], sum(widths)
-        key = tuple(p for m in members for p in (m.param_names if m.param_names and all(m.param_names) else [m.name]))
+        key = tuple(p for m in members for p in self._param_key(m))
         d_w = self._dev_param(key + ("w", "group"), lambda: self._upload(np.concatenate(Ws, 0)))
         d_b = self._dev_param(key + ("b", "group"), lambda: self._upload(np.concatenate(bs, 0)))
         bot = self.blobs[L.bottoms[0]]

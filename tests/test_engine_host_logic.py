@@ -111,6 +111,52 @@ def test_reduced_graph_every_blob(fake_gpu, monkeypatch, fuse, math):
     net.close()
 
 
+def test_fc_kind_table(monkeypatch):
+    """The InnerProduct precision rule (engine._fc_kind) and the stage-major format its producers write (engine._FC_KINDS through
+    _fc_sm_format, and Net._sm_format on top of it), against the values the two earlier statements of the rule -- the binder's
+    weight packing and Net._sm_format's own if/elif chain -- gave, written out by hand.  They agreed on every row."""
+    from types import SimpleNamespace
+    from mnc_amd import engine
+    Ks = [32, 64, 96, 128, 4096, 50048, 100352]
+    # kind of a product above the flops threshold, per math mode, for each K of Ks
+    kinds = {"fp32": ["fp32", "fp32", "fp32", "fp32", "fp32", "fp32", "fp32"],
+             "bf16x3": ["x3", "x3", "x3", "x3", "x3", "x3", "x3"],
+             "f16": ["x3", "f16", "x3", "f16", "f16", "f16", "f16"],
+             "mixed": ["x3", "f16", "x3", "f16", "f16", "x3", "x3"],            # more than 50 000 inputs stay split bf16
+             "bf16": ["fp32", "bf16", "fp32", "bf16", "bf16", "bf16", "bf16"],
+             "f8": ["x3", "f16", "x3", "f8", "f8", "f8", "f8"]}                 # K % 128 != 0: the f16 rules
+    # stage-major format per kind for a producer with C = 32, 64, 96 channels (0 none, 1 f16, 2 bf16x3, 3 bf16)
+    formats = {"fp32": [0, 0, 0], "x3": [2, 2, 2], "f16": [0, 1, 0], "bf16": [0, 3, 0], "f8": [0, 1, 0]}
+    assert engine._X3_MIN_FLOPS == 2.0e9
+    ip = SimpleNamespace(type="InnerProduct", skip=False, group=None, group_leader=None)
+    rows = 0
+    for thr in (2.0e9, 0.0):
+        monkeypatch.setattr(engine, "_X3_MIN_FLOPS", thr)                       # (read when the rule is asked, not at import)
+        for math in engine.MATH_MODES:
+            _, _, fc_math = engine.math_modes(math)
+            net = SimpleNamespace(math=math, fc_math=fc_math, _consumers={"x": [0]}, _layers=[ip], _layer_nout=lambda L: 256)
+            for M in (0, 1, 300):
+                if M == 0 and thr == 0.0:
+                    continue                      # no rows: nothing is launched, and no threshold separates 0 flops from 0
+                for K, big_kind in zip(Ks, kinds[math]):
+                    kind = big_kind if 2.0 * M * 256 * K >= thr else "fp32"       # below the threshold: the fp32 kernel
+                    assert engine._fc_kind(math, fc_math, M, 256, K) == kind, (thr, math, M, K)
+                    for C, fmt in zip((32, 64, 96), formats[kind]):
+                        assert engine._fc_sm_format(kind, K, C) == fmt, (thr, math, M, K, C)
+                        assert engine.Net._sm_format(net, "x", M, K, C) == fmt, (thr, math, M, K, C)
+                        rows += 1
+    assert rows == 6 * 7 * 3 * 5
+    # the rows the rule is known by
+    monkeypatch.setattr(engine, "_X3_MIN_FLOPS", 0.0)
+    one = lambda math, K, C: (engine._fc_kind(math, engine.math_modes(math)[2], 300, 256, K),
+                              engine._fc_sm_format(engine._fc_kind(math, engine.math_modes(math)[2], 300, 256, K), K, C))
+    assert one("mixed", 100352, 64) == ("x3", 2) and one("f8", 64, 64) == ("f16", 1) and one("f8", 128, 64) == ("f8", 1)
+    assert one("f16", 32, 32) == ("x3", 2) and one("f16", 96, 96) == ("x3", 2) and one("bf16", 32, 32) == ("fp32", 0)
+    monkeypatch.setattr(engine, "_X3_MIN_FLOPS", 2.0e9)
+    assert all(one(m, 4096, 64) == ("fp32", 0) for m in engine.MATH_MODES)      # 2 * 300 * 256 * 4096 = 6.3e8 flops
+    assert one("mixed", 100352, 64) == ("x3", 2) and one("f8", 50048, 64) == ("f8", 1)
+
+
 def test_fusion_plan(fake_gpu):
     from mnc_amd.engine import Net
     path = models.write_mnc_5stage_test_prototxt(width_div=8)

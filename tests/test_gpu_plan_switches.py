@@ -20,7 +20,7 @@ default plan of the native net where the launchers run the same additions in the
   * FC_SM / fp32, bf16x3, f16, mixed -- at this width no InnerProduct leaves kind 0 in any math mode: pipeline.hip prepare_fc():
     `const bool big = 2.0 * n->cfg.post_nms_topn * (double)N * (double)K >= 2.0e9` is false for all of them (the largest, fc6 /
     fc6_mask: 2 * 300 * 512 * 3136 = 9.6e8), so `fc->kind = ... : 0`, and sm_format() ends in `return 0` for kind 0 whatever
-    `n->fc_sm` says; engine.py _sm_format(): `if 2.0 * M * n_out * K < _X3_MIN_FLOPS: continue` leaves fmt = 0 the same way.  The
+    `n->fc_sm` says; engine.py _fc_kind(): `if 2.0 * M * n_out * K < _X3_MIN_FLOPS: return "fp32"` leaves _sm_format() at 0 the same way.  The
     switch needs fc6 at >= 2 GFLOP (width_div <= 4).  test_fc_sm_is_a_no_op_at_this_width holds the claim itself: the day the bar
     moves and FC_SM starts to act here, that test fails and the four pairs belong into SETTING_MATH.  FC_SM=0 still rides along
     in ALL.
