@@ -21,6 +21,12 @@ LOWP = {"bf16x3": 0, "f16": 1, "bf16": 2}                 # mode number of mnc_c
 # ---- shapes (the smallest at which each plan is still reached; none is the workload's own) ----
 CONV3 = [(5, 3, 8, 32), (6, 37, 16, 64), (9, 70, 8, 32), (13, 33, 128, 256), (4, 32, 8, 512), (38, 63, 64, 128)]      # H, W, Cin, Cout
 WINO4_REDUCE = (37, 63, 256, 512)                         # F(4x4)'s in-launch reduction (five uneven K ranges)
+# mnc_conv3x3_wino4_split (conv_wino4_split.hip: the 36 transform positions as ONE batched launch of the LDS-DMA InnerProduct kernel,
+# whose rows are the 4x4 tiles): ragged tiles both ways, one K stage | 19 x 17 = 323 tiles = 304 + 19 under the 304-row cut, two
+# column tiles | the same cut with 8 K stages (the loop's steady state) and three column tiles | 25 x 25 = 625 tiles: the cut is
+# off, 320 + 305 rows, Cout below one column tile | 26 x 26 = 676 tiles: three blocks under the cut, 304 + 304 + 68
+WINO4_SPLIT = [(7, 9, 32, 128), (76, 68, 64, 256), (76, 68, 256, 384), (97, 99, 32, 32), (102, 103, 32, 64)]
+FC_BATCH = [(323, 384, 256), (625, 96, 32), (676, 130, 64)]            # M, N, K of mnc_fc_batch: the row counts above
 LOWP_PLAN = (23, 70, 64, 128)                             # test_conv3x3_lowp_every_plan's shape, plans 0..3
 C3 = [(20, 33, 64), (20, 33, 16), (20, 33, 48), (20, 33, 8), (20, 33, 72)]      # H, W, Cout of mnc_conv3x3_c3
 # H, W, Cin, Cout, stride, residual: the rows of test_gpu_ops.C11 below the 800 x 1333 ResNet grids (H >= 100)
@@ -305,6 +311,37 @@ def wino_f32(x, w, m, order):
         part = np.matmul(U[:, :, idx], V[:, idx, :])
         M = part if M is None else M + part
     return wino_output(M, m, tiles, x.shape[1], x.shape[2])
+
+
+def dma_k_order(K):
+    """The order in which fc_mfma_dma16_kernel adds the K values of one output (gemm.hip): stages of 32, two groups of 16 per stage,
+    MFMA q = 0..3 of a group multiplies k = q, 4 + q, 8 + q, 12 + q -- (k0, k4, k8, k12, k1, ...)."""
+    assert K % 32 == 0
+    return np.array([32 * s + 16 * G + 4 * g + q for s in range(K // 32) for G in range(2) for q in range(4) for g in range(4)])
+
+
+def batch_row_blocks(M, first=None):
+    """fc_batch_launch's row blocks as (first row, rows): 304 rows each (the last 16-row sub-tile of the 320 dropped) when that needs
+    no more blocks than 320-row ones, else 320.  first: the distance between the first rows of neighbouring blocks, when it is
+    stated apart from the rows a block owns (a defect: the blocks then leave rows out)."""
+    step = 304 if -(-M // 304) == -(-M // 320) else 320
+    first = step if first is None else first
+    return [(b * first, min(M - b * first, step)) for b in range(-(-M // step)) if b * first < M]
+
+
+def wino4_split_f32(x, w, order, first=None):
+    """conv_wino4_split.hip in float32 from the standard matrices: V[p][tile][ci] and U[p][co][ci], M[p][tile][co] filled row block
+    by row block (batch_row_blocks; what no block writes stays NaN, as in the NaN-filled workspace of the GPU test), the channel sum
+    in the given order (as wino_f32), the output transform.  Without the bias."""
+    U, V, tiles = wino_operands(x.astype(np.float32), w, 4)
+    M = np.full((36, w.shape[0], V.shape[2]), np.nan, np.float32)
+    for m0, rows in batch_row_blocks(V.shape[2], first):
+        acc = None
+        for idx in order:
+            part = np.matmul(U[:, :, idx], V[:, idx, m0:m0 + rows])
+            acc = part if acc is None else acc + part
+        M[:, :, m0:m0 + rows] = acc
+    return wino_output(M, 4, tiles, x.shape[1], x.shape[2])
 
 
 @functools.lru_cache(maxsize=6)

@@ -106,3 +106,10 @@ def sweep_conv_cases():
                 seen.add(key)
                 out.append((name,) + key)
     return out
+
+
+def split_cases():
+    """The cases of sweep_conv_cases() the default (throughput) plan runs as transform passes around one batched InnerProduct
+    launch (csrc/conv_wino4_split.hip): 512 channels in and out on a map of at least 304 4x4 tiles -- stated here from the shapes
+    alone; tests/test_gpu_size_sweep.py holds the library's own rule (mnc_conv3x3_wino4_split_selected) to this list."""
+    return [c for c in sweep_conv_cases() if c[4] >= 512 and c[5] >= 512 and -(-c[2] // 4) * -(-c[3] // 4) >= 304]

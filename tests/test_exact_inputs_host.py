@@ -4,7 +4,10 @@
   * the method is sound: a float32 numpy evaluation of each family -- operands split / rounded as the mode does, the K sum forward,
     shuffled, and cut into ranges that are summed afterwards; Winograd from the standard matrices -- gives exactly the reference;
   * the method has teeth: the same evaluation with one defect each is caught at every shape;
-  * every plan of fc_plan.h is reached by one of the InnerProduct shapes (through the CPU plan shim).
+  * every plan of fc_plan.h is reached by one of the InnerProduct shapes (through the CPU plan shim);
+  * the unfused F(4x4) path (transform passes around one batched InnerProduct launch) has the same one right answer on its cases, in
+    the LDS-DMA kernel's K order and in the batched launch's row blocks, and a second block that starts at row 320 under the
+    304-row cut is reported.
 
 Defects and the existing range-relative bar (gpu_util.err(...)[1] < 1e-4), as measured here on the exact inputs (each row's test prints
 its own figures; this is their summary over all rows): the bar would have passed NONE of the five defects on these inputs --
@@ -155,6 +158,54 @@ def test_winograd_in_float32_gives_the_reference_in_any_order():
             twice = list(orders(Cin, rng)["ranges"])
             twice.append(twice[len(twice) // 2])
             assert not E.same(E.wino_f32(c.a, c.w, m, twice) + c.b[:, None, None], c.want), c.what
+
+
+def test_the_dma_kernels_k_order_and_the_batched_launchs_row_blocks():
+    assert E.dma_k_order(64)[:9].tolist() == [0, 4, 8, 12, 1, 5, 9, 13, 2] and E.dma_k_order(64)[16:20].tolist() == [16, 20, 24, 28]
+    assert sorted(E.dma_k_order(256).tolist()) == list(range(256))
+    # the tile counts E.WINO4_SPLIT and E.FC_BATCH are chosen for
+    assert E.batch_row_blocks(63) == [(0, 63)] and E.batch_row_blocks(304) == [(0, 304)] and E.batch_row_blocks(320) == [(0, 320)]
+    assert E.batch_row_blocks(323) == [(0, 304), (304, 19)] and E.batch_row_blocks(608) == [(0, 304), (304, 304)]
+    assert E.batch_row_blocks(625) == [(0, 320), (320, 305)] and E.batch_row_blocks(676) == [(0, 304), (304, 304), (608, 68)]
+    assert E.batch_row_blocks(323, first=320) == [(0, 304), (320, 3)]
+    tiles = [-(-H // 4) * -(-W // 4) for H, W, _, _ in E.WINO4_SPLIT]
+    assert tiles == [6, 323, 323, 625, 676] and sorted(set(tiles[1:])) == [M for M, _, _ in E.FC_BATCH]
+
+
+@pytest.mark.parametrize("H,W,Cin,Cout", E.WINO4_SPLIT)
+def test_split_winograd_in_float32_gives_the_reference(H, W, Cin, Cout):
+    """The cases of test_gpu_exact_arithmetic.py::test_conv3x3_wino4_split have one right answer for the unfused decomposition too
+    (V and M through memory, M filled in fc_batch_launch's row blocks): in float32, with the channels in natural order and in the
+    LDS-DMA kernel's K order, plus the bias it is c.want.  Teeth: the same statement with the second row block of the 304-row cut
+    starting at row 320 is reported (at the shapes that have a second block under the cut)."""
+    for relu in (0, 1) if (H, W, Cin, Cout) == E.WINO4_SPLIT[1] else (0,):
+        c = E.wino_case(4, H, W, Cin, Cout, relu=relu)
+        assert c.bits > 0, c.what
+        print(c.what)
+        finish = lambda y: np.maximum(y + c.b[:, None, None], 0) if relu else y + c.b[:, None, None]
+        for name, order in (("natural", [np.arange(Cin)]), ("dma", [E.dma_k_order(Cin)])):
+            got = finish(E.wino4_split_f32(c.a, c.w, order))
+            assert got.dtype == np.float32 and E.same(got, c.want), (c.what, name)
+            assert E.same(finish(E.wino_f32(c.a, c.w, 4, order)), c.want), (c.what, name)
+        blocks = E.batch_row_blocks(-(-H // 4) * -(-W // 4))
+        if len(blocks) > 1 and blocks[0][1] == 304 and not relu:
+            wrong = finish(E.wino4_split_f32(c.a, c.w, [E.dma_k_order(Cin)], first=320))
+            assert not E.same(wrong, c.want), c.what
+            bad = np.argwhere(~(wrong == c.want))
+            print("  second block from row 320: %d of %d values differ, first at %s" % (len(bad), wrong.size, bad[0].tolist()))
+
+
+@pytest.mark.parametrize("M,N,K", E.FC_BATCH)
+def test_fc_batch_cases_hold_their_preconditions(M, N, K):
+    """The products of test_gpu_exact_arithmetic.py::test_fc_batch: the builders assert representability and headroom; without the
+    bias (mnc_fc_batch adds none) the expected value is still an fp32 value, in the DMA kernel's K order too."""
+    for family in E.families("fp32"):
+        for seed in (0, 1, 2):
+            c = E.fc_case(family, "fp32", M, N, K, seed=seed)
+            want = c.want.astype(np.float64) - c.b.astype(np.float64)
+            assert np.array_equal(want.astype(np.float32).astype(np.float64), want), c.what
+            idx = E.dma_k_order(K)
+            assert E.same(np.matmul(c.a[:, idx], c.w[:, idx].T), want), c.what
 
 
 # defect -> (the families that must catch it, the modes it exists in, convolutions only)

@@ -23,6 +23,10 @@ Plans, as the launchers read (wino4_plan, wino_impl, sw_plan, fc_plan.h through 
   mnc_fc 300x1024x25088     DMA16 kernel, 32 K ranges, in-launch slab reduction; FC_DMA's shapes under FC_TILE=10, FC_DMA=1: 16 / 8 ranges
   mnc_fc_pair 300x1024x4096 one paired DMA16 launch, 16 ranges
   lowp fc 300x4096x4096     256-column kernel, 2 ranges; the pair there one launch without ranges; 640x512x8192 paired with 16 ranges
+  F(4x4) split 76x68 256->384   input transform, 36 positions x (304 + 19 rows) x 3 column tiles = 216 workgroups of the DMA16
+                            kernel's BATCH build with 8 K stages each, output transform; 102x103 32->64: 36 x 3 row blocks, one stage
+  fc_f8 300x256x4480        quantiser, product kernel in 2 K ranges (18 + 17 stages), f8_reduce_kernel; 321x256x1024: two row blocks
+                            by two ranges; 300x441x512: one range, fused epilogue (two launches)
 
 The bandwidth disturber is mnc_add (with it and the other two every case below reaches the share; mnc_roi_warp was not needed).
 Measured on an MI355X, one run (disturbed launches of 16, median contended / median solo duration, wall time of the test, which
@@ -49,6 +53,9 @@ where it exceeds a second is the CPU's for the exact cases; fp32 / bf16x3 / f16 
   fc_lowp_pair f16 300x4096x4096                    16               2.47x                0.97
   fc_lowp_pair bf16x3 300x4096x4096                 16               1.64x                (below 1.7, the same later run)
   fc_lowp_pair 640x512x8192 (f16, bf16x3)           16, 16           4.80x, 3.70x         0.76, 1.19
+  wino4_split 76x68 256->384, _pool                 16, 16           2.86x, 3.20x         1.90, 0.10   (these six: a later run)
+  wino4_split 102x103 32->64                        16               8.94x                0.22
+  fc_f8 300x256x4480, 321x256x1024, 300x441x512     16, 16, 16       4.69x, 6.17x, 2.53x  0.81, 0.21, 0.17
   proposal 38x63 (wide, single-workgroup top-K)     16, 16           4.43x, 1.82x         0.22, 0.03
   vote_instances 600 @ 600x1000                     15               1.29x                1.96
 The shares of the small kernels move from run to run (launches of 10 .. 20 us against a bar that is the slowest of sixteen): the
@@ -65,6 +72,7 @@ import pytest
 
 import contention as CT
 import exact_inputs as E
+import f8_inputs as F8
 import golden_inputs as GI
 import mnc_amd
 from gpu_util import Dev, from_c8, to_c8
@@ -131,6 +139,59 @@ def wino(m, shape, pool=False):
                        lambda i, o: dev.call(fn, ins[i][0], ins[i][1], ins[i][2], o[0], H, W, Cin, Cout, 0), wants,
                        lambda a: [from_c8(a[0], Cout, OH, OW)])
     return build
+
+
+def wino4_split(shape, pool=False):
+    """mnc_conv3x3_wino4_split / _split_pool: every context has ONE workspace (V and M of conv_wino4_split.hip), which both
+    alternating inputs go through, as a net's layers do; it starts NaN-filled."""
+    H, W, Cin, Cout = shape
+    fn = "mnc_conv3x3_wino4_split" + ("_pool" if pool else "")
+    OH, OW = ((H + 1) // 2, (W + 1) // 2) if pool else (H, W)
+
+    def build(dev, seeds, slots):
+        cs = [case("wino_case", 4, H, W, Cin, Cout, seed=s) for s in seeds]
+        ins = []
+        for c in cs:
+            d_u = dev.empty((36 * Cout * Cin,), fill=np.nan)
+            dev.call("mnc_pack_conv3x3_wino4_split", dev.put(c.w), d_u, Cout, Cin)
+            ins.append((dev.put(to_c8(c.a)), d_u, dev.put(c.b)))
+        nb = int(_lib.load().mnc_conv3x3_wino4_split_ws_bytes(H, W, Cin, Cout))
+        assert nb > 0
+        d_ws = dev.empty((nb // 4,), fill=np.nan)
+        wants = [[E.maxpool2_ceil(c.want) if pool else c.want] for c in cs]
+        return running(dev, slots, [((Cout * OH * OW,), np.float32)],
+                       lambda i, o: dev.call(fn, ins[i][0], ins[i][1], ins[i][2], o[0], d_ws, H, W, Cin, Cout, 0), wants,
+                       lambda a: [from_c8(a[0], Cout, OH, OW)])
+    return build
+
+
+def fc_f8(row):
+    """mnc_fc_f8 on fp32 rows with ldc = N + 2 (weights packed once per input): the row quantiser, the product kernel and, with K
+    ranges, f8_reduce_kernel, chained through the context's scratch.  Compared as bits with f8_inputs.exact_case's integer answer."""
+    M, N, K = row
+    ld = N + 2
+
+    def build(dev, seeds, slots):
+        cs = [f8_case(M, N, K, s) for s in seeds]
+        nb, tiles = _lib.load().mnc_pack_fc_f8_bytes(N, K), -(-N // 256)
+        assert nb == tiles * 256 * K
+        ins = []
+        for c in cs:
+            d_q, d_e = dev.alloc(nb), dev.alloc(tiles * 256 * 4)
+            dev.call("mnc_pack_fc_f8", dev.put(c.w), d_q, d_e, N, K)
+            ins.append((dev.put(c.a), d_q, d_e, dev.put(c.bias)))
+        wants = [[c.want.astype(np.float32).view(np.uint32), np.ones((M, 2), bool)] for c in cs]
+        return running(dev, slots, [((M, ld), np.float32)],
+                       lambda i, o: dev.call("mnc_fc_f8", ins[i][0], ins[i][1], ins[i][2], ins[i][3], o[0], M, N, K, ld, 0), wants,
+                       lambda a: [a[0].view(np.uint32)[:, :N], np.isnan(a[0][:, N:])])
+    return build
+
+
+def f8_case(M, N, K, seed):
+    key = ("f8", M, N, K, seed)
+    if key not in _CASES:
+        _CASES[key] = F8.exact_case(M, N, K, seed=seed, small=True)
+    return _CASES[key]
 
 
 def words(mode, n):
@@ -290,6 +351,24 @@ def test_wino4_separate_reduction_kernel(dev, disturbers):
     """mnc_conv3x3_wino4 with FC_REDUCE=0: the separate reduction kernel reads slabs.  Hazard: per-context scratch beside another
     context's (the twin runs the same plan on its own scratch)."""
     CT.contended_kernel(dev, disturbers, wino(4, E.WINO4_REDUCE), "wino4 FC_REDUCE=0 %dx%d %d->%d" % E.WINO4_REDUCE, [("FC_REDUCE", "0")])
+
+
+@pytest.mark.parametrize("shape,pool", [(E.WINO4_SPLIT[2], False), (E.WINO4_SPLIT[2], True), (E.WINO4_SPLIT[4], False)])
+def test_wino4_split(dev, disturbers, shape, pool):
+    """mnc_conv3x3_wino4_split / _split_pool: three dependent launches through one workspace per context, the middle one
+    fc_mfma_dma16_kernel's BATCH instantiation.  Hazards: the steady-state loop's waits and barriers of that instantiation (eight K
+    stages at 256 input channels) against slow waves; the next launch's input transform overwriting V, and its batched launch M,
+    behind the previous launch's readers (stream order is all that separates them); per-context workspace beside another's."""
+    CT.contended_kernel(dev, disturbers, wino4_split(shape, pool), "wino4_split%s %dx%d %d->%d" % (("_pool" if pool else "",) + tuple(shape)))
+
+
+@pytest.mark.parametrize("row", [(300, 256, 4480), (321, 256, 1024), (300, 441, 512)])
+def test_fc_f8(dev, disturbers, row):
+    """mnc_fc_f8: K ranges of 18 and 17 stages plus the reduction; two row blocks by two ranges; one range with the fused epilogue.
+    Hazards: the quantised rows, their exponents and the partial sums live in the context's scratch and are re-used by the next
+    launch (stream order alone separates the quantiser, the product kernel and the reduction); the product kernel's pipelined LDS
+    stages against slow waves; per-context scratch beside another context's."""
+    CT.contended_kernel(dev, disturbers, fc_f8(row), "fc_f8 %dx%dx%d ldc+2" % tuple(row))
 
 
 def test_wino2_tail_plan_reduce(dev, disturbers):

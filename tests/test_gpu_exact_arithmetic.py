@@ -4,7 +4,12 @@ of units below 2^24).  fp32 MFMA, Winograd, split-K with slabs, the bf16x3 split
 bit for bit, in any summation order -- so every comparison here is np.array_equal on an output buffer pre-filled with NaN, and a
 kernel that is wrong by one unit anywhere fails.  Launcher choices are forced through mnc_ctx_set_tuning exactly where the
 tolerance tests (test_gpu_ops.py, test_gpu_conv_sw.py) force them.  tests/test_exact_inputs_host.py shows on the CPU that the method
-is sound and which defects it catches that the range-relative bar does not."""
+is sound and which defects it catches that the range-relative bar does not.
+The unfused F(4x4) path of the throughput plan (test_conv3x3_wino4_split, test_fc_batch) was run once on a scratch build whose
+batched launch takes the first row of a block under the 304-row cut as block x 320: the three convolutions and the two products
+with a second block under the cut failed (NaN from row 304 on: 65536 of 1323008 values at 76x68 64->256), this module's fused F(4x4)
+and fp32 InnerProduct tests passed (the others were not run), and so did test_gpu_wino_split.py's five convolutions (at most 320 tiles, one block); of that module only the
+batched launch's own test at K = 64 saw it (M = 608 and 330)."""
 import numpy as np
 import pytest
 
@@ -137,6 +142,33 @@ def test_conv3x3_winograd_f4(dev, tune, H, W, Cin, Cout):
                 exact(_wino_run(dev, "mnc_conv3x3_wino4", c, d_x, d_w, d_b, True), E.maxpool2_ceil(c.want), what + " pool")
             tune("FC_REDUCE", "0")
             exact(_wino_run(dev, "mnc_conv3x3_wino4", c, d_x, d_w, d_b, False), c.want, what + " FC_REDUCE=0")
+
+
+@pytest.mark.parametrize("H,W,Cin,Cout", E.WINO4_SPLIT)
+def test_conv3x3_wino4_split(dev, H, W, Cin, Cout):
+    """mnc_conv3x3_wino4_split / _split_pool (input transform, the 36 positions as one batched launch of the LDS-DMA InnerProduct
+    kernel, output transform) on a NaN-filled workspace of exactly mnc_conv3x3_wino4_split_ws_bytes: one row block, two and three
+    blocks under the 304-row cut, two 320-row blocks; one and eight K stages; a ragged, one and several column tiles.  A row no
+    block writes, a row written from the wrong tile or a position at the wrong stride is a NaN or a wrong integer."""
+    lib = _lib.load()
+    for relu in relus((H, W, Cin, Cout), E.WINO4_SPLIT):
+        c = E.wino_case(4, H, W, Cin, Cout, relu=relu)
+        mark = dev.mark()
+        d_x, d_b = dev.put(to_c8(c.a)), dev.put(c.b)
+        d_u = dev.empty((36 * Cout * Cin,), fill=np.nan)
+        dev.call("mnc_pack_conv3x3_wino4_split", dev.put(c.w), d_u, Cout, Cin)
+        packed = dev.get(d_u, (36 * Cout * Cin,)).astype(np.float64) / c.unit
+        assert np.array_equal(packed, np.round(packed)), c.what + ": the packed G g G^T is not whole"      # (a precondition)
+        nb = int(lib.mnc_conv3x3_wino4_split_ws_bytes(H, W, Cin, Cout))
+        assert nb > 0 and nb % 4 == 0
+        for pool in (False, True):
+            OH, OW = ((H + 1) // 2, (W + 1) // 2) if pool else (H, W)
+            d_ws = dev.empty((nb // 4,), fill=np.nan)
+            d_y = dev.empty((Cout * OH * OW,), fill=np.nan)
+            dev.call("mnc_conv3x3_wino4_split" + ("_pool" if pool else ""), d_x, d_u, d_b, d_y, d_ws, H, W, Cin, Cout, c.relu)
+            exact(from_c8(dev.get(d_y, (Cout * OH * OW,)), Cout, OH, OW), E.maxpool2_ceil(c.want) if pool else c.want,
+                  "%s split%s relu=%d" % (c.what, " pool" if pool else "", relu))
+        dev.free_since(mark)
 
 
 @pytest.mark.parametrize("mode", LOWP_MODES)
@@ -306,6 +338,33 @@ def test_fc_fp32(dev, tune, M, N, K, pad):
                 fc_out(dev, d_o, M, N, ld, c.want, "%s %s" % (c.what, s))
                 for k, _ in s:
                     dev.tune(k, None)
+
+
+@pytest.mark.parametrize("M,N,K", E.FC_BATCH)
+def test_fc_batch(dev, M, N, K):
+    """mnc_fc_batch (fc_mfma_dma16_kernel's BATCH mode: no bias, no activation, no K cut): B = 3 products at strides wider than the
+    products, ldc = N + 8.  304 + 19 rows with three column tiles and eight K stages; 320 + 305 rows; 304 + 304 + 68 rows with a
+    ragged second column tile.  The gaps between the operands hold NaN (a row or a stage read from there poisons its output); the
+    gaps between the results, the columns past N and everything behind the last product still hold the fill."""
+    B, ldc = 3, N + 8
+    sa, sw, so = M * K + 64, N * K + 128, M * ldc + 32
+    for family in E.families("fp32"):
+        cs = [E.fc_case(family, "fp32", M, N, K, seed=s) for s in range(B)]
+        a, w = np.full((B, sa), np.nan, np.float32), np.full((B, sw), np.nan, np.float32)
+        for b, c in enumerate(cs):
+            a[b, :M * K], w[b, :N * K] = c.a.reshape(-1), c.w.reshape(-1)
+        mark = dev.mark()
+        d_o = dev.empty((B + 1, so), fill=np.nan)
+        dev.call("mnc_fc_batch", dev.put(a), sa, dev.put(w), sw, d_o, so, B, M, N, K, ldc)
+        got = dev.get(d_o, (B + 1, so))
+        dev.free_since(mark)
+        for b, c in enumerate(cs):
+            want = (c.want.astype(np.float64) - c.b.astype(np.float64)).astype(np.float32)      # (exact: multiples of the unit below 2^24)
+            o = got[b, :M * ldc].reshape(M, ldc)
+            exact(o[:, :N], want, "%s product %d of the batch" % (c.what, b))
+            assert np.isnan(o[:, N:]).all(), c.what + ": wrote beyond the column slice"
+            assert np.isnan(got[b, M * ldc:]).all(), c.what + ": wrote between the products"
+        assert np.isnan(got[B]).all(), cs[0].what + ": wrote behind the last product"
 
 
 @pytest.mark.parametrize("M,N,K,pad", E.FC_PAIR + E.FC_MORE[1:])

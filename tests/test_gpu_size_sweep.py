@@ -26,6 +26,9 @@ Figures (MI355X, profiles/size_sweep_report.txt -- every stage of every size, ev
       conv1_2 6.3e-06 / 5.8e-06   conv2_1 5.9e-06 / 5.5e-06   conv2_2 9.5e-06 / 9.0e-06   conv3_1 8.6e-06 / 6.9e-06
       conv3_2, 3_3 1.2e-05 / 1.1e-05   conv4_1 1.2e-05 / 1.1e-05   conv4_2, 4_3 1.4e-05 / 1.3e-05   conv5_x 6.7e-06 / 5.8e-06
       (conv1_1, the direct kernel, on pixels minus means: 2.8e-07)
+  The 16 cases the default (throughput) plan runs unfused (size_sweep_inputs.split_cases(): conv4_2 / conv4_3 on 361 .. 576 tiles, two
+  row blocks of the batched InnerProduct launch under its 304-row cut) are run through mnc_conv3x3_wino4_split / _split_pool too,
+  against the same fp64 reference: worst whole map 1.4e-05 (75x100, 75x113), worst edge strip 1.3e-05 (71x125) -- the fused kernel's.
   -- the ~1e-5 quoted for zero-mean input holds for positive-mean input at every shape of the sweep: no finding about the kernel's
   accuracy on real activations, no shape within a factor 7 of the bar.
   Run time: the module 41 s, test_gpu_parity8's fp32 case 13 s in the same run.  The op-level list and the reduced modes were cut for
@@ -41,7 +44,7 @@ import torch.nn.functional as F
 import mnc_amd
 import size_sweep_inputs as S
 from gpu_util import Dev, err, from_c8, to_c8
-from mnc_amd import models, synth
+from mnc_amd import _lib, models, synth
 from mnc_amd.instances import split_records
 from mnc_amd.native_net import ImageStream, NativeNet
 from oracle import host as ohost
@@ -257,6 +260,7 @@ def _strips(H, W):
 
 
 _CASES = S.sweep_conv_cases()
+_SPLIT = S.split_cases()
 
 
 @pytest.mark.parametrize("layer,kind,H,W,Cin,Cout", _CASES, ids=["%s-%dx%d" % (c[0], c[2], c[3]) for c in _CASES])
@@ -299,4 +303,33 @@ def test_trunk_conv_at_the_shapes_the_sweep_launches(scoped, layer, kind, H, W, 
         dev.call("mnc_conv3x3_wino4_pool", d_x, d_w, d_b, d_p, H, W, Cin, Cout, 1)
         pooled = from_c8(dev.get(d_p, (Cout * OH * OW,)), Cout, OH, OW)
         ref = F.max_pool2d(torch.from_numpy(got)[None], 2, 2, ceil_mode=True)[0].numpy()
+        assert pooled.shape == ref.shape and np.array_equal(pooled, ref), line
+    # The form the default (throughput) plan runs this layer in: transform passes around one batched InnerProduct launch
+    # (csrc/conv_wino4_split.hip) exactly where the library's own rule says so on this untuned context -- and that is the list
+    # size_sweep_inputs.split_cases() states from the shapes alone, so a changed rule cannot silently skip this leg.
+    lib = _lib.load()
+    split = bool(lib.mnc_conv3x3_wino4_split_selected(dev.h, H, W, Cin, Cout))
+    assert split == ((layer, kind, H, W, Cin, Cout) in _SPLIT), line
+    if not split:
+        return
+    d_raw = dev.put(w)
+    d_u = dev.empty((36 * Cout * Cin,), fill=np.nan)
+    dev.call("mnc_pack_conv3x3_wino4_split", d_raw, d_u, Cout, Cin)
+    d_ws = dev.empty((int(lib.mnc_conv3x3_wino4_split_ws_bytes(H, W, Cin, Cout)) // 4,), fill=np.nan)
+    d_ys = dev.empty((Cout, H, W), fill=-7.0)
+    dev.call("mnc_conv3x3_wino4_split", d_x, d_u, d_b, d_ys, d_ws, H, W, Cin, Cout, 1)
+    got_s = from_c8(dev.get(d_ys, (Cout * H * W,)), Cout, H, W)
+    assert np.isfinite(got_s).all()
+    d = np.abs(got_s - want)
+    figs = [("whole map", float(d.max() / want.max()))] + [(n, float(d[s].max() / want[s].max())) for n, s in _strips(H, W)]
+    line = "%-7s %-5s %4dx%-4d %3d->%-3d split: " % (layer, kind, H, W, Cin, Cout) + "  ".join("%s %.2e" % f for f in figs)
+    print(line)
+    _log([line])
+    for name, rel in figs:
+        assert rel < 1e-4, (name, line)
+    if kind == "pool":
+        d_ps = dev.empty((Cout, OH, OW), fill=-7.0)
+        dev.call("mnc_conv3x3_wino4_split_pool", d_x, d_u, d_b, d_ps, d_ws, H, W, Cin, Cout, 1)
+        pooled = from_c8(dev.get(d_ps, (Cout * OH * OW,)), Cout, OH, OW)
+        ref = F.max_pool2d(torch.from_numpy(got_s)[None], 2, 2, ceil_mode=True)[0].numpy()
         assert pooled.shape == ref.shape and np.array_equal(pooled, ref), line

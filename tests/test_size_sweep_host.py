@@ -78,6 +78,21 @@ def test_trunk_shapes_follow_the_prototxt():
     assert not any(c[2:] in base for c in cases)
 
 
+def test_the_cases_the_throughput_plan_runs_in_the_split_form():
+    """conv4_2 (plain) and conv4_3 (pool) of eight net inputs: 361 to 576 tiles, always two row blocks under the batched launch's
+    304-row cut, K = N = 512.  conv4_1 (256 channels in), every conv5 map and the two panoramas' conv4 maps (below 304
+    tiles) stay fused."""
+    cases = S.split_cases()
+    maps = [(75, 100), (90, 75), (75, 113), (125, 71), (100, 75), (71, 125), (75, 75), (113, 75)]
+    assert cases == [(layer, kind, H, W, 512, 512) for H, W in maps for layer, kind in (("conv4_2", "plain"), ("conv4_3", "pool"))]
+    assert len(cases) == 16 and len(S.sweep_conv_cases()) == 94
+    tiles = [-(-c[2] // 4) * -(-c[3] // 4) for c in cases]
+    assert min(tiles) == 361 and max(tiles) == 576
+    assert all(-(-t // 304) == -(-t // 320) == 2 for t in tiles)          # two blocks, the 304-row cut on
+    rest = [c for c in S.sweep_conv_cases() if c not in cases]
+    assert all(c[4] < 512 or -(-c[2] // 4) * -(-c[3] // 4) < 304 for c in rest)
+
+
 def test_the_entries_with_fewer_anchors_than_pre_nms_top_n():
     sizes = [(a, b) for a, b, _ in S.SIZES]
     assert S.UNDER_6000 in sizes and S.FEW_ROIS in sizes
