@@ -1084,6 +1084,60 @@ MNC_API int mnc_mask_pred_overlaps(const int* gt_bounds, const long long* gt_off
 MNC_API int mnc_mask_targets_timing(int on, double* last_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n24 The differentiable half of the training graph that is MNC's own: the backward passes of ROIWarping (with respect to the
+ *     feature map AND to the box: "enables gradient back-propagation with respect to RoI coordinates", arXiv:1512.04412 section
+ *     3), of the MAX 2x2/2 pooling behind the 28x28 warp, of MaskResize and of MaskPooling (csrc/roi_backward.hip).  Device-pointer
+ *     graph ops on an engine context (declared further down), in the style of mnc_roi_warp; the statements of the rules are
+ *     mnc_amd/backward.py: roi_warp_backward_numpy, maxpool2_backward_numpy, mask_resize_backward_numpy, mask_pool_backward_numpy.
+ *     All rules are the derivatives of oracle/SPEC.md sections 1-3 under the SPEC's default conventions; floor is piecewise
+ *     constant, so x0, y0 are constants and the sample position enters only through ax = sx - x0, ay = sy - y0.  No
+ *     floating-point atomics anywhere: two calls on the same inputs give the same bytes.
+ *
+ *     ROIWarping backward.  Grid PH x PW (the unfused layer); F is zero outside the map.  For RoI r and cell (ph, pw) the float32
+ *     quantities x1s, y1s, bw, bh, sx, sy, x0, y0, ax, ay are the FORWARD'S OWN: the identical expressions in the identical order
+ *     as mnc_roi_warp / orc_roi_warp.  g = dtop[r][ph][pw][c].
+ *       dfeat[c][y][x] = the sum of w * g over all (r, ph, pw, tap) whose tap lands on (y, x); w00 = (1-ax)(1-ay), w01 = ax(1-ay),
+ *         w10 = (1-ax)ay, w11 = ax ay, each formed as in the forward and then multiplied by g; taps outside the map are dropped.
+ *         ORDER OF SUMMATION, part of the rule: ascending r, then ph, then pw, within one sample 00, 01, 10, 11; float32, from
+ *         +0.0f, no contraction.  The kernel equals the float32 statement bit for bit.
+ *       drois[r][0] = 0.  Per sample dsx_c = (1-ay)(F01-F00) + ay(F11-F10), dsy_c = (1-ax)(F10-F00) + ax(F11-F01), Gx = sum_c g dsx_c,
+ *         Gy = sum_c g dsy_c; drois[r][1] += scale (1-tx) Gx, [3] += scale tx Gx, [2] += scale (1-ty) Gy, [4] += scale ty Gy, with
+ *         tx = pw / PW when the width is FREE, else 0 (ty alike): free iff the float32 value x2s - x1s + 1 is >= 1, the max(., 1)
+ *         clamp inactive or tied (the sub-gradient of torch's clamp(min=1)); a clamped width sends all of Gx to x1.  The order of
+ *         this sum is the launch geometry's: one workgroup per RoI, one fixed reduction tree.
+ *     MAX 2x2/2 backward: the gradient of an output goes to the FIRST maximum of its window in the order (0,0), (0,1), (1,0),
+ *       (1,1) -- a later element wins only when strictly greater, the forward's max4 order and Caffe's rule -- the other three
+ *       inputs get +0.0f.  The argmax is recomputed from the forward's input; no index tensor exists.  Bit-exact.
+ *     MaskResize backward: din[r][iy][ix] = the sum over output cells (h, w), ascending h then w, of weight * dout[r][h][w], the
+ *       weight of the input cell in that output exactly SPEC section 2's: the bilinear four, or 1 on the nearest cell when
+ *       sx == IW - 1 or sy == IH - 1.  Bit for bit with the statement.
+ *     MaskPooling backward: dfeat[r][h][w][c] = dtop[r][h][w][c] * mask[r][h][w] (bit-exact); dmask[r][h][w] = sum_c dtop * feat,
+ *       one wave per position in a fixed order.
+ *
+ *     Every output is fully written, zeros included.  The entries make their forward entries' argument checks: MNC_ERR_INVALID
+ *     before any launch.  MNC_ERR_UNSUPPORTED, before any launch too, when the context carries a convention other than the SPEC's
+ *     for the layer in question (mnc_layer_conventions: the four warp_ fields; resize_mode; maskpool_binary).  RoI coordinates
+ *     are expected finite.
+ * ------------------------------------------------------------------------------------------------------------- */
+struct mnc_ctx;   /* the engine context, declared below */
+/* d_feat_c8 and d_dfeat_c8 [C/8][H][W][8], the forward's input layout; d_dtop [R][PH][PW][C], its output layout; d_drois [R][5].
+ * d_dfeat_c8 or d_drois may be NULL to skip that half (not both; d_feat_c8 is read for d_drois only and may be NULL without it).
+ * R == 0 writes a zero dfeat and returns.  MNC_ERR_INVALID also for PH or PW >= 32768.  The pixel-major copies and the range
+ * tables live in the context's scratch arena. */
+MNC_API int mnc_roi_warp_backward(struct mnc_ctx* ctx, const float* d_feat_c8, int C, int H, int W, const float* d_rois, int R, int PH,
+                                  int PW, float spatial_scale, const float* d_dtop, float* d_dfeat_c8, float* d_drois);
+/* d_in [R][PH][PW][C] = the forward's input (PH, PW even, as mnc_maxpool2_rhwc takes them), d_dout [R][PH/2][PW/2][C] ->
+ * d_din [R][PH][PW][C]. */
+MNC_API int mnc_maxpool2_rhwc_backward(struct mnc_ctx* ctx, const float* d_in, const float* d_dout, float* d_din, int R, int PH, int PW,
+                                       int C);
+/* d_dout [R][OH][OW] -> d_din [R][IH][IW]. */
+MNC_API int mnc_mask_resize_backward(struct mnc_ctx* ctx, const float* d_dout, float* d_din, int R, int IH, int IW, int OH, int OW);
+/* d_feat, d_dtop, d_dfeat [R][PH][PW][C]; d_mask, d_dmask [R][PH][PW].  d_dfeat or d_dmask may be NULL to skip that half (not
+ * both); d_mask is read for d_dfeat only, d_feat for d_dmask only. */
+MNC_API int mnc_mask_pool_backward(struct mnc_ctx* ctx, const float* d_feat, const float* d_mask, const float* d_dtop, float* d_dfeat,
+                                   float* d_dmask, int R, int PH, int PW, int C);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */
