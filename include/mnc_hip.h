@@ -1138,6 +1138,58 @@ MNC_API int mnc_mask_pool_backward(struct mnc_ctx* ctx, const float* d_feat, con
                                    float* d_dmask, int R, int PH, int PW, int C);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * n25 The loss layers that end the five stages of models/VGG16/mnc_5stage/train.prototxt -- SoftmaxWithLoss, SmoothL1Loss,
+ *     SigmoidCrossEntropyLoss: the value and the gradient with respect to the prediction -- and the backward passes of ReLU and
+ *     Sigmoid that carry that gradient to the next InnerProduct (csrc/loss.hip).  Device-pointer graph ops on an engine context
+ *     like n24: everything is stream-ordered on the context's stream, no entry reads anything back or synchronises (the
+ *     context's scratch arena is grown on first use, as for every entry that uses it).  The statements of the rules are
+ *     mnc_amd/losses.py: softmax_loss_numpy, smooth_l1_loss_numpy, sigmoid_ce_loss_numpy, eltwise_backward_numpy; the rules are
+ *     public BVLC Caffe's and py-faster-rcnn's (caffe-mnc's own layer sources are not available); what those leave open is a
+ *     CHOICE of DESIGN.md.  All tensors are float32; labels are float32 as in a Caffe blob and are cast with (int).  exp of a
+ *     float32 is np_exp_f32 (csrc/np_exp.h) and the file is compiled without contraction: every gradient, the probabilities
+ *     and the SmoothL1 terms equal the float32 statement BIT FOR BIT; the softmax and sigmoid terms differ from it by logf.
+ *
+ *     d_result, 16 bytes on the device: float loss (unweighted, Caffe's top), float normaliser, int32 count, int32 status.
+ *     The loss is a sum of per-workgroup partials in a fixed geometry, added in index order by one workgroup: no floating-point
+ *     atomics, the same bytes on every run.  At most three launches per entry.  A null optional output is skipped; a call
+ *     with d_result alone writes nothing else.  MNC_ERR_INVALID before any launch: a null ctx, d_result or input; a shape
+ *     outside the limits.  A zero-size call (outer * inner == 0; N == 0; count == 0) zeroes the 16 bytes and launches nothing.
+ *
+ *     SoftmaxWithLoss on score [outer][C][inner], label [outer][inner]; 1 <= C <= 4096, outer * inner < 2^31.  m = max_c score;
+ *       e_c = exp(score_c - m); s = the sum of e_c in ASCENDING c from +0.0; p_c = e_c / s.  li = (int)label.  A position is
+ *       ignored when has_ignore and li == ignore_label; otherwise INVALID when the label is non-integral, outside [0, C), NaN or
+ *       outside int's range: never used as an index, counted as ignored, bit 0 of the status set.  term = -log(max(p_li,
+ *       FLT_MIN)) at valid positions, 0 elsewhere; count = the valid positions; normaliser = max(count, 1) when normalize, else
+ *       outer; loss = sum of terms / normaliser.  dscore_c = (p_c - [c == li]) * (loss_weight / normaliser) at valid positions,
+ *       +0.0 in all C channels elsewhere.  Scores are expected finite.  Two layouts: one lane per position with class stride
+ *       inner (inner > 1), one wave per position (inner == 1); the same bits.
+ *     SmoothL1Loss on count elements: s2 = sigma * sigma, thr = 1 / s2, d = (pred - target) * w_in,
+ *       term = (|d| < thr ? 0.5 * s2 * d * d : |d| - 0.5 / s2) * w_out, operations left to right, the comparison strict;
+ *       loss = sum / N; dpred = (|d| < thr ? s2 * d : (0 < d) - (d < 0)) * w_in * w_out * (loss_weight / N).  The gradient with
+ *       respect to target is its negation and has no output.  count of the result = the elements.
+ *     SigmoidCrossEntropyLoss on count elements: pos = [x >= 0], term = -(x * (t - pos) - log(1 + exp(x - 2 * x * pos))) * w,
+ *       loss = sum / N, dx = (1 / (1 + exp(-x)) - t) * w * (loss_weight / N); d_w NULL = ones.  exp(-x) may be +inf: dx is then
+ *       -t * w * (loss_weight / N).
+ *     Activation backward from the layer's OUTPUT y: ReLU dx = y > 0 ? dy : +0.0; Sigmoid dx = (dy * y) * (1 - y).
+ * ------------------------------------------------------------------------------------------------------------- */
+/* d_prob and d_dscore [outer][C][inner], d_terms [outer][inner]; each may be NULL. */
+MNC_API int mnc_softmax_loss(struct mnc_ctx* ctx, const float* d_score, const float* d_label, int outer, int C, int inner, int has_ignore,
+                             int ignore_label, int normalize, float loss_weight, float* d_prob, float* d_terms, float* d_dscore,
+                             void* d_result);
+/* For tools/loss_bench.py and the tests.  plan = 1: the following calls of mnc_softmax_loss, on every context of the process, run
+ * the one-lane-per-position layout on any shape; plan = 2: the one-wave-per-position layout; plan = 0: by inner (the default).
+ * MNC_ERR_INVALID: any other value. */
+MNC_API int mnc_softmax_loss_plan(int plan);
+/* All five tensors hold count elements, count < 2^31; N = shape[0] of the layer's bottoms.  d_terms and d_dpred may be NULL. */
+MNC_API int mnc_smooth_l1_loss(struct mnc_ctx* ctx, const float* d_pred, const float* d_target, const float* d_w_in, const float* d_w_out,
+                               int N, long long count, float sigma, float loss_weight, float* d_terms, float* d_dpred, void* d_result);
+/* d_w NULL: no weight bottom.  d_terms and d_dx may be NULL. */
+MNC_API int mnc_sigmoid_ce_loss(struct mnc_ctx* ctx, const float* d_x, const float* d_t, const float* d_w, int N, long long count,
+                                float loss_weight, float* d_terms, float* d_dx, void* d_result);
+/* op as mnc_eltwise: 1 ReLU, 2 Sigmoid.  d_y is the forward's output; count == 0 launches nothing. */
+MNC_API int mnc_eltwise_backward(struct mnc_ctx* ctx, const float* d_y, const float* d_dy, float* d_dx, size_t count, int op);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * n3  The input edge of the CFM task: the MCG proposal maskdb of one image, the validation branch of
  *     tools/prepare_mcg_maskdb.py:55-97 (csrc/mcg_maskdb.hip).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -2,7 +2,7 @@
 
     python -m mnc_amd._build [--force]
 
-hipcc cross-compiles without a GPU.  nms.hip / mv.hip / mv_image.hip / sds_eval.hip / render.hip / inst_masks.hip / mask_targets.hip / mask_overlaps.hip / mask_match.hip / coco_accum.hip / bbox.hip / roi.hip / roi_backward.hip are compiled with -ffp-contract=off: their float expressions must be evaluated
+hipcc cross-compiles without a GPU.  nms.hip / mv.hip / mv_image.hip / sds_eval.hip / render.hip / inst_masks.hip / mask_targets.hip / mask_overlaps.hip / mask_match.hip / coco_accum.hip / bbox.hip / roi.hip / roi_backward.hip / loss.hip are compiled with -ffp-contract=off: their float expressions must be evaluated
 operation by operation to stay bit-exact with the reference (nms, mv) resp. the oracle's SPEC (roi: a contracted
 sample coordinate moves the bilinear weights by 1 ulp, 2e-5 in the output); all of them are HBM/latency-bound.
 """
@@ -19,7 +19,7 @@ ARCH = "gfx950"
 # (mcg_maskdb.hip is not listed: its only float64 product, dx * ifx, is followed by floor -- there is nothing to contract it with;
 # mask_rle.hip, mask_boundary.hip, mask_components.hip, mask_contours.hip, mask_distance.hip, mask_shape.hip, mask_algebra.hip, mask_warp.hip, mask_labels.hip, mask_pixels.hip, mask_surface.hip, mask_tight.hip and scan.hip are not listed: they have no floating-point arithmetic at all; mask_poly.hip is: the doubles of rleFrPoly's walk keep
 # their published order, on the host side of the file (the rounding of the vertices) as in its kernels)
-NO_CONTRACT = {"nms.hip", "mv.hip", "mv_image.hip", "sds_eval.hip", "render.hip", "inst_masks.hip", "mask_overlaps.hip", "mask_match.hip", "mask_poly.hip", "coco_accum.hip", "bbox.hip", "roi.hip", "proposal.hip", "prep.hip", "mask_targets.hip", "roi_backward.hip"}
+NO_CONTRACT = {"nms.hip", "mv.hip", "mv_image.hip", "sds_eval.hip", "render.hip", "inst_masks.hip", "mask_overlaps.hip", "mask_match.hip", "mask_poly.hip", "coco_accum.hip", "bbox.hip", "roi.hip", "proposal.hip", "prep.hip", "mask_targets.hip", "roi_backward.hip", "loss.hip"}
 # conv_wino4.hip: the transform arithmetic runs beside MFMAs as one-lane fma / add; hipcc's SLP pass would pair scalar operations of
 # different window elements into v_pk_* and pay for every pair with register moves (and packed fp32 beside MFMAs costs more issue
 # time than the two scalar operations: MI355X_MICROARCH.md, per-instruction constants)
